@@ -15,6 +15,7 @@ workload ("vc"); the same line carries a fixed three-point sweep (low / vc / hig
     python bench.py --gpus 8             # re-executes itself under torch.distributed.run, one rank per GPU
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8     # what the driver does: same thing
     python bench.py --variant dense      # + rgb in, byte mask, xyz f32, rgba out
+    python bench.py --dump-outputs DIR   # + what the timed path returned in its last step, as DIR/<name>.npy
 
 With --gpus N every rank processes its own batch of the same size (weak scaling, pairs shard embarrassingly) and
 the per-pair records of the whole job are collated with one RCCL all_gather inside the timed region.  On a box
@@ -37,7 +38,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.join(ROOT, "multi-spatialmllm_amd"), ROOT]
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")     # before the first HIP call: the from-disk legs overlap ten decode streams (mspa/__init__.py)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is achievable
 H, W = 480, 640
@@ -119,6 +119,9 @@ def parse_args():
     ap.add_argument("--no-sweep", action="store_true", help="skip the low / high overlap legs of the sweep")
     ap.add_argument("--also", default="compact:fast,corr:exact,dense:fast,dense_xyz:fast,dense:exact,minimal:fast",
                     help="comma list of extra variant:mode legs timed briefly on rank 0 ('none' = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: per-pixel outputs at a fixed, seeded sample of positions)")
     return ap.parse_args()
 
 
@@ -155,6 +158,71 @@ def _scene_cache_dir():
     except OSError:
         return None
     return d
+
+
+DUMP_BUDGET = 64 << 20         # bytes --dump-outputs may write in all
+DUMP_SAMPLE = 1 << 20          # (pair, pixel) positions kept of a per-pixel output
+DUMP_ARRAY_CAP = 32 << 20      # a whole-kept output larger than this is cut to a seeded sample of its rows
+
+
+def _dump_sample(n, k, seed):
+    """A fixed, seeded, sorted sample of k of the flat indices 0..n-1 (all of them when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def _dump_rows(a, cap=DUMP_ARRAY_CAP, seed=7):
+    """`a` whole, or a seeded sample of its rows when it is larger than `cap` bytes."""
+    if a.nbytes <= cap:
+        return a
+    return a[_dump_sample(a.shape[0], max(1, cap // max(1, a[0].nbytes)), seed)]
+
+
+def pair_outputs_for_dump(out, n_pairs):
+    """The outputs of the pair path (alloc_pair_outputs / alloc_pair_correspondences) as float32 / float64 host arrays: the
+    per-pair counters whole, per-pixel outputs at one fixed, seeded sample of (pair, pixel) positions (`pixel_sample_index` =
+    pair * P + pixel), the visibility bitset unpacked to one 0/1 per pixel, compacted entries past a tile's count (unspecified
+    by the kernel) as -1.  Integers that do not fit float32 exactly go to float64."""
+    import torch
+    dev = out["counts"].device
+    idx_np = _dump_sample(n_pairs * P, DUMP_SAMPLE, 2024)
+    idx = torch.from_numpy(idx_np).to(dev)
+    res = {"pixel_sample_index": idx_np.astype(np.float64)}
+    for name, t in out.items():
+        if name in ("counts", "tile_counts"):
+            res[name] = t.cpu().numpy().astype(np.float64)
+        elif name == "vis_bits":
+            px = idx % P
+            word = t[idx // P, px >> 6]
+            res["vis"] = ((word >> (px & 63)) & 1).to(torch.float32).cpu().numpy()
+        elif name == "cpix":
+            n, nt, cap, _ = t.shape
+            e_np = _dump_sample(n * nt * cap, DUMP_SAMPLE, 2025)
+            e = torch.from_numpy(e_np).to(dev)
+            v = t.reshape(-1, 2)[e].to(torch.float32)
+            v[(e % cap) >= out["tile_counts"].reshape(-1)[e // cap].to(torch.int64)] = -1.0
+            res["cpix"] = v.cpu().numpy()
+            res["cpix_sample_index"] = e_np.astype(np.float64)
+        else:
+            v = t.reshape(n_pairs * P, -1)[idx]
+            if name == "rgba":                               # uint32 words in an int32 tensor
+                v = v.to(torch.int64) & 0xFFFFFFFF
+            wide = v.dtype in (torch.int32, torch.int64, torch.float64)
+            res[name] = v.to(torch.float64 if wide else torch.float32).squeeze(1).cpu().numpy()
+    return res
+
+
+def dump_outputs(path, arrays):
+    """Write {name: array} as path/<name>.npy, within DUMP_BUDGET bytes in all."""
+    arrays = {k: _dump_rows(np.ascontiguousarray(v)) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
 
 
 def make_base_scene(args, rank):
@@ -846,6 +914,8 @@ def run_scene_workload(args, rank, world, device, dist_ctx, share):
         dist_ctx.barrier()
     wall = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pair_table": table.cpu().numpy()})
     rank_walls, rows_all = [wall], [n_rows]
     if dist_ctx is not None:
         t = torch.tensor([wall, float(n_rows)], dtype=torch.float64, device=dist_ctx.collective_device)
@@ -1115,6 +1185,8 @@ def main():
         del _cold_out
     wall, kern_ms, out = time_variant(args.variant, args.mode, depth, mats, rgb, pairs, args.steps, args.warmup,
                                       dist_ctx, stream, spinup_ms=args.spinup_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pair_outputs_for_dump(out, args.pairs))
     rank_walls = None
     if dist_ctx is not None:
         # every rank's own wall time of the timed region (they all include the same final barrier; what differs is how long a

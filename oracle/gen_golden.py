@@ -560,6 +560,33 @@ def golden_sens(ns):
     print("sens.npz:", {k: getattr(v, "shape", None) for k, v in out.items()})
 
 
+SAMPLING_CASES = [(0, 5000, 600, 40, 6, 35, 1), (1, 800, 900, 0, 0, 100, 5), (2, 300, 50, 10, 6, 35, 1), (3, 50, 10, 5, 40, 60, 2)]
+SAMPLING_NP_SEED = 123
+
+
+def sampling_frame(seed, n):
+    """The pair table tests/test_sampling_vs_reference.py samples from: row k has image_id1 = str(k)."""
+    import pandas as pd
+    rng = np.random.default_rng(seed)
+    ov = rng.gamma(2.0, 8.0, n)
+    ov[rng.random(n) < 0.2] = 0.0
+    ov[rng.random(n) < 0.01] = np.nan
+    return pd.DataFrame({"scene_id": "s", "image_id1": np.arange(n).astype(str), "image_id2": "x", "overlap": ov,
+                         "distance": rng.random(n), "yaw": rng.random(n), "pitch": rng.random(n)})
+
+
+def golden_sampling(ns):
+    """CME.sample_dataframe on the SAMPLING_CASES tables (global NumPy seed SAMPLING_NP_SEED): the rows it returns, in order,
+    as their image_id1 values."""
+    out = {"meta": _meta(), "cases": np.array(SAMPLING_CASES, dtype=np.int64)}
+    for k, (seed, n, total, zeros, lo, hi, step) in enumerate(SAMPLING_CASES):
+        np.random.seed(SAMPLING_NP_SEED)
+        want = ns.CME.sample_dataframe(sampling_frame(seed, n), total, zeros, lo, hi, step)
+        out[f"rows_{k}"] = want["image_id1"].astype(np.int64).to_numpy()
+    np.savez_compressed(os.path.join(GOLDEN_DIR, "sampling.npz"), **out)
+    print("sampling.npz:", {k: getattr(v, "shape", None) for k, v in out.items()})
+
+
 def main():
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     ns = RH.import_reference()
@@ -577,6 +604,8 @@ def main():
         return golden_k3_near_plane(ns)
     if len(sys.argv) > 1 and sys.argv[1] == "k1_near_vertex":
         return golden_k1_near_vertex(ns)
+    if len(sys.argv) > 1 and sys.argv[1] == "sampling":
+        return golden_sampling(ns)
     golden_scene(ns, "scene_ident", 2001, (48, 64), (48, 64), n_points=700, n_frames=6, with_color=True)
     golden_scene(ns, "scene_scaled", 2002, (73, 98), (48, 64), n_points=700, n_frames=6, with_color=False)
     golden_ties(ns)
@@ -588,6 +617,7 @@ def main():
     golden_k3_640x480(ns)
     golden_k3_near_plane(ns)
     golden_k1_near_vertex(ns)
+    golden_sampling(ns)
 
 
 if __name__ == "__main__":

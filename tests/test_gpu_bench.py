@@ -153,3 +153,45 @@ def test_bench_informational_legs_run_small():
     assert all(v is not None and v >= 0 for v in busy.values()) and len(busy) == 6
     k5 = bench.time_track_geometry(torch.device("cuda", 0), T=60, P=32, n_scenes=4, reps=2)
     assert k5["batched"]["frames"] == 240 and k5["one_block"]["frac"] > 0
+
+
+def _load_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f), allow_pickle=False) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def test_bench_dump_outputs_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: what the timed path returned in its last step, float32 / float64 within 64 MB; two runs of the same
+    command dump the same arrays, and --steps K really times K steps."""
+    import numpy as np
+    dumps = []
+    for k, steps in enumerate(("3", "5")):
+        d = str(tmp_path / f"run{k}")
+        args = list(SMALL)
+        args[args.index("--steps") + 1] = steps
+        j = run([sys.executable, "bench.py", "--gpus", "1", "--no-sweep", "--no-cpu-baseline", "--variant", "compact",
+                 "--dump-outputs", d] + args)
+        assert j["steps"] == int(steps) and j["ms_per_step"] > 0
+        dumps.append(_load_dump(d))
+    a, b = dumps
+    assert {"counts", "vis", "cpix", "tile_counts", "pixel_sample_index", "cpix_sample_index"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    assert a["counts"].shape == (96, 2) and a["counts"][:, 1].sum() > 0
+    assert np.array_equal(a["tile_counts"].sum(axis=1), a["counts"][:, 1])
+    # the sampled bitset against the per-pair counters: a seeded sample of 2^20 of the 96 x 307 200 pixels
+    assert a["vis"].size == 1 << 20 and set(np.unique(a["vis"]).tolist()) <= {0.0, 1.0}
+    assert abs(a["vis"].mean() - a["counts"][:, 1].sum() / (96 * 640 * 480)) < 0.01
+    assert np.all((a["cpix"] >= -1) & (a["cpix"] < 640))
+
+
+def test_bench_dump_outputs_scene_workload(tmp_path):
+    import numpy as np
+    d = str(tmp_path / "scenes")
+    j = run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", d] + SCENES_SMALL)
+    check_scene_line(j, 1)
+    t = np.load(os.path.join(d, "pair_table.npy"))
+    assert t.dtype == np.float64 and t.shape[1] == 7 and t.shape[0] > 10000
+    assert sorted(np.unique(t[:, 0]).astype(int).tolist()) == [0, 1, 2]

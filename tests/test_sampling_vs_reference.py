@@ -1,27 +1,30 @@
-"""mspa.sampling.sample_dataframe against the reference's (same global NumPy seed, same rows out)."""
+"""mspa.sampling.sample_dataframe against the reference's (same global NumPy seed, same rows out).
+
+The reference's rows are frozen in tests/golden/sampling.npz (oracle/gen_golden.py); where the reference is mounted it is
+also run live, and its rows must still be the frozen ones."""
 import numpy as np
 import pandas as pd
 import pytest
 
+from golden_util import GOLDEN_DIR
 from mspa.sampling import sample_dataframe
 from oracle import ref_harness as RH
-
-pytestmark = [pytest.mark.reference,
-              pytest.mark.skipif(not RH.reference_available(), reason="/root/reference not mounted")]
+from oracle.gen_golden import SAMPLING_CASES, SAMPLING_NP_SEED, sampling_frame
 
 
-@pytest.mark.parametrize("seed,n,total,zeros,lo,hi,step", [(0, 5000, 600, 40, 6, 35, 1), (1, 800, 900, 0, 0, 100, 5),
-                                                           (2, 300, 50, 10, 6, 35, 1), (3, 50, 10, 5, 40, 60, 2)])
-def test_sample_dataframe(seed, n, total, zeros, lo, hi, step, capsys):
-    ref = RH.import_reference()
-    rng = np.random.default_rng(seed)
-    ov = rng.gamma(2.0, 8.0, n)
-    ov[rng.random(n) < 0.2] = 0.0
-    ov[rng.random(n) < 0.01] = np.nan
-    df = pd.DataFrame({"scene_id": "s", "image_id1": np.arange(n).astype(str), "image_id2": "x", "overlap": ov,
-                       "distance": rng.random(n), "yaw": rng.random(n), "pitch": rng.random(n)})
-    np.random.seed(123)
-    want = ref.CME.sample_dataframe(df, total, zeros, lo, hi, step)
-    np.random.seed(123)
+@pytest.mark.parametrize("case", range(len(SAMPLING_CASES)),
+                         ids=["-".join(str(v) for v in c) for c in SAMPLING_CASES])
+def test_sample_dataframe(case, capsys):
+    seed, n, total, zeros, lo, hi, step = SAMPLING_CASES[case]
+    df = sampling_frame(seed, n)
+    gold = np.load(f"{GOLDEN_DIR}/sampling.npz")
+    assert gold["cases"][case].tolist() == list(SAMPLING_CASES[case])
+    want = df.iloc[gold[f"rows_{case}"]].reset_index(drop=True)
+    if RH.reference_available():
+        ref = RH.import_reference()
+        np.random.seed(SAMPLING_NP_SEED)
+        live = ref.CME.sample_dataframe(df, total, zeros, lo, hi, step)
+        pd.testing.assert_frame_equal(live.reset_index(drop=True), want)
+    np.random.seed(SAMPLING_NP_SEED)
     got = sample_dataframe(df, total, zeros, lo, hi, step)
-    pd.testing.assert_frame_equal(got.reset_index(drop=True), want.reset_index(drop=True))
+    pd.testing.assert_frame_equal(got.reset_index(drop=True), want)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Do per-scene decode launches on separate HIP streams overlap?  S scenes of F frames each: one launch of S*F streams, S launches
-on one stream, S launches on S streams (optionally GPU_MAX_HW_QUEUES set by the caller).
+on one stream, S launches on S streams.
     python tools/device_ingest_streams.py [--scenes 10] [--frames 320]"""
 import argparse, json, os, shutil, sys, tempfile, time
 import numpy as np
@@ -63,7 +63,7 @@ def main():
                     engine.inflate_blocks_device(src, off, nb, block, raw, stt)
                     engine.png_unfilter_device(raw, H, W, stt, out)
 
-        res = {"scenes": a.scenes, "frames_per_scene": F, "GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}
+        res = {"scenes": a.scenes, "frames_per_scene": F}
         for name, fn in (("one_launch", one_launch), ("same_stream", same_stream), ("many_streams", many_streams)):
             fn()
             torch.cuda.synchronize()
