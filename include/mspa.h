@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 160            /* 0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
+#define MSPA_VERSION 170            /* 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
+                                       0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
 
 #define MSPA_OK 0
@@ -430,6 +431,43 @@ int mspa_png_unfilter_device(const void *raw_dev, int64_t raw_pitch, int64_t n_i
 int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_files, int32_t h, int32_t w, void *dst_host,
                             int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
                             int64_t *capacity_needed, int32_t n_threads);
+
+/*
+ * Colour-frame decode ON THE DEVICE (csrc/jpeg_decode.hip, arithmetic in csrc/jpeg_core.h): the per-frame JPEG decode of
+ * SceneInfoHandler.get_color_image (`cv2.imread` + BGR -> RGB, ops.py:265-266) and of the .sens colour payloads
+ * (extract_posed_images.py), with the COMPRESSED bytes crossing PCIe and [H, W, 3] uint8 RGB landing in HBM -- the layout
+ * mspa_pair_reproject's `rgb` reads.  Output is bit-identical to libjpeg-turbo's default decompression (JDCT_ISLOW, fancy
+ * upsampling) for every image that gets status 0.
+ *
+ * mspa_jpeg_parse_host     n payloads (nbytes_host[k] bytes at src_host[k]) -> n descriptors of MSPA_JPEG_DESC_BYTES each at
+ *   desc_host, and status_host[k]: 0 decodable on the device; 1 not a JPEG, truncated or malformed header, invalid table;
+ *   2 a JPEG outside the accepted subset.  Accepted: SOF0 (baseline, 8-bit, Huffman), one scan holding every component,
+ *   greyscale, or YCbCr (JFIF, or no Adobe marker and component ids other than 'R','G','B') with luma sampling 1x1, 2x1 or 2x2
+ *   and chroma 1x1; any DQT / DHT / APPn / COM / DRI segments before SOS.  Reads only [src, src + nbytes).
+ *   Descriptor fields (little endian; the rest is the kernel's tables):
+ *     int32 [0] status [1] h [2] w [3] components [4] restart interval (MCUs; 0 none) [5] max h sampling [6] max v sampling
+ *           [7] MCUs per row [8] MCU rows [9] coefficient blocks
+ *     int64 at byte 48: offset of the entropy-coded segment in the payload; at byte 56: its length (to the payload's end)
+ *     int32 at byte 64: h sampling[3], v sampling[3], quantisation table id[3], DC table id[3], AC table id[3]
+ *     uint16 at byte 192: [3][64] each component's quantisation table in natural (row-major) order
+ * mspa_jpeg_workspace_bytes  bytes of scratch a decode of n_images h x w images needs (coefficients and component planes).
+ * mspa_jpeg_decode_device  n_images payloads resident on the device (payload k = src_bytes_dev[k] bytes at src_dev +
+ *   src_offsets_dev[k]; src_dev 4-byte aligned; the kernel reads the aligned 4-byte words that hold a payload's bytes, all of
+ *   which must lie inside src_capacity) with their descriptors (desc_dev, 16-byte aligned) -> out_dev[k] = [h, w, 3] uint8 RGB
+ *   (greyscale: R = G = B).  status_dev[k] (written for every k): 0 decoded exactly -- every MCU from real data, restart markers
+ *   present and in sequence, valid codes only, no coefficient past index 63, the segment consumed up to EOI with at most seven
+ *   1-bits of padding, every block inside the range in which all forms of the IDCT agree; otherwise the parse status, 3 another
+ *   size than h x w, 4 bad entropy-coded data, 5 a restart marker missing or out of sequence, 6 data after the last MCU or no
+ *   EOI, 7 a block out of range.  A non-zero image's output is unspecified: decode that frame on the host.  Images of one
+ *   call share (h, w); sampling and tables may differ.  workspace: caller-owned, 16-byte aligned, at least
+ *   mspa_jpeg_workspace_bytes(n_images, h, w) bytes; contents undefined afterwards.  n_images <= 65 535.
+ */
+#define MSPA_JPEG_DESC_BYTES 4224
+int mspa_jpeg_parse_host(const void *const *src_host, const int64_t *nbytes_host, int64_t n, void *desc_host, int32_t *status_host);
+int64_t mspa_jpeg_workspace_bytes(int64_t n_images, int32_t h, int32_t w);
+int mspa_jpeg_decode_device(const void *src_dev, const int64_t *src_offsets_dev, const int64_t *src_bytes_dev, int64_t src_capacity,
+                            const void *desc_dev, int64_t n_images, int32_t h, int32_t w, uint8_t *out_dev, int32_t *status_dev,
+                            void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * K4 -- per-pair camera relations: the distance / yaw / pitch columns of CFR.process_scene's pair

@@ -16,6 +16,7 @@ PAIR_FAST = 1
 PAIR_STREAM = 2
 PAIR_WORD_STRIPES = 0x200
 CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
+JPEG_DESC_BYTES = 4224
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)
 
 
@@ -84,6 +85,10 @@ _SIGNATURES = {
     "mspa_png_unfilter_device": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "mspa_png_pack_idat_host": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                         POINTER(c_int64), c_int32]),
+    "mspa_jpeg_parse_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mspa_jpeg_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "mspa_jpeg_decode_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_int64, c_void_p]),
     "mspa_check_visibility": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "mspa_pair_pose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p,

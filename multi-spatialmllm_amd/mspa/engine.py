@@ -204,6 +204,73 @@ def png_unfilter_device(raw: torch.Tensor, h: int, w: int, status: torch.Tensor,
     return out
 
 
+JPEG_STATUS = {0: "decoded", 1: "not a JPEG / malformed header", 2: "outside the accepted subset", 3: "another size",
+               4: "bad entropy-coded data", 5: "restart marker missing or out of sequence", 6: "no EOI after the last MCU",
+               7: "block out of range"}
+
+
+def jpeg_parse_host(payloads: Sequence) -> Tuple[np.ndarray, np.ndarray]:
+    """Headers of n JPEG payloads (bytes-like or uint8 arrays) -> (descriptors [n, MSPA_JPEG_DESC_BYTES] uint8, status [n]
+    int32) through mspa_jpeg_parse_host: status 0 = the device decodes this image, anything else = decode it on the host."""
+    n = len(payloads)
+    keep = [np.frombuffer(p, dtype=np.uint8) if not isinstance(p, np.ndarray) else np.ascontiguousarray(p, dtype=np.uint8)
+            for p in payloads]
+    desc = np.zeros((n, _lib.JPEG_DESC_BYTES), dtype=np.uint8)
+    status = np.zeros((n,), dtype=np.int32)
+    if n:
+        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data if a.size else None for a in keep])
+        lens = np.array([a.size for a in keep], dtype=np.int64)
+        _lib.check(_lib.load().mspa_jpeg_parse_host(ptrs, lens.ctypes.data, n, desc.ctypes.data, status.ctypes.data))
+    return desc, status
+
+
+def jpeg_desc_fields(desc: np.ndarray) -> Dict[str, np.ndarray]:
+    """The documented fields of parsed descriptors (include/mspa.h): per image h, w, components, restart interval, sampling
+    factors, quantisation tables (natural order) and the entropy-coded segment's offset / length in the payload."""
+    d = np.ascontiguousarray(np.asarray(desc, dtype=np.uint8).reshape(-1, _lib.JPEG_DESC_BYTES))
+    i32 = d[:, :192].view(np.int32)
+    i64 = d[:, 48:64].view(np.int64)
+    return {"status": i32[:, 0].copy(), "h": i32[:, 1].copy(), "w": i32[:, 2].copy(), "ncomp": i32[:, 3].copy(),
+            "restart_interval": i32[:, 4].copy(), "mcus_x": i32[:, 7].copy(), "mcus_y": i32[:, 8].copy(),
+            "samp_h": i32[:, 16:19].copy(), "samp_v": i32[:, 19:22].copy(), "tq": i32[:, 22:25].copy(),
+            "scan_offset": i64[:, 0].copy(), "scan_bytes": i64[:, 1].copy(),
+            "qt": d[:, 192:576].view(np.uint16).reshape(-1, 3, 64).copy()}
+
+
+def jpeg_decode_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, descriptors: torch.Tensor, hw: Tuple[int, int],
+                       out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """``len(offsets)`` JPEG payloads resident on the device -- payload k = ``src[offsets[k] : offsets[k] + nbytes[k]]`` (uint8,
+    ``src`` a multiple of 4 bytes long) -- with their descriptors (``jpeg_parse_host``, uploaded: [n, MSPA_JPEG_DESC_BYTES]
+    uint8) decoded into ``out[k]`` = [H, W, 3] uint8 RGB (mspa_jpeg_decode_device; replaces the per-frame cv2.imread /
+    Pillow decode of the colour frames).  Returns (out, status): status 0 = bit-identical to libjpeg-turbo's decode;
+    anything else = decode that frame on the host.  Only enqueues; read ``status`` after a synchronisation."""
+    _require_gpu()
+    n = int(offsets.shape[0])
+    H, W = int(hw[0]), int(hw[1])
+    _require(H > 0 and W > 0, "hw: a positive (H, W)")
+    _require(src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1 and src.numel() % 4 == 0,
+             "src: a flat uint8 device tensor, a multiple of 4 bytes long")
+    _require(offsets.is_cuda and offsets.dtype == torch.int64 and nbytes.is_cuda and nbytes.dtype == torch.int64
+             and nbytes.shape[0] == n, "offsets / nbytes: int64 device tensors of one length")
+    _require(descriptors.is_cuda and descriptors.dtype == torch.uint8 and descriptors.is_contiguous()
+             and tuple(descriptors.shape) == (n, _lib.JPEG_DESC_BYTES), "descriptors: [n, JPEG_DESC_BYTES] uint8 on the device")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=src.device)
+    _require(out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape[1:]) == (H, W, 3)
+             and out.shape[0] >= n, "out: [n, H, W, 3] uint8 on the device")
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=src.device)
+    _require(status.is_cuda and status.dtype == torch.int32 and status.shape[0] >= n, "status: int32 [n] on the device")
+    if n == 0:
+        return out, status
+    lib = _lib.load()
+    ws_bytes = int(lib.mspa_jpeg_workspace_bytes(n, H, W))
+    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=src.device).view(torch.uint8)   # 16-byte aligned
+    _lib.check(lib.mspa_jpeg_decode_device(_ptr(src), _ptr(offsets), _ptr(nbytes), int(src.numel()), _ptr(descriptors), n, H, W,
+                                           _ptr(out), _ptr(status), work.data_ptr(), int(work.numel()), _stream_ptr()))
+    return out, status
+
+
 def _require_pinhole(mats: torch.Tensor):
     """MSPA_PAIR_FAST reads the camera-2 depth off the third image row: K's third row must be 0 0 1 0 in EVERY frame record
     (include/mspa.h).  The records live on the device, so the check is one read-back of all frames' rows the first time a

@@ -266,3 +266,78 @@ def read_depth_frames_device(paths: Sequence[str], device="cuda", n_threads: int
         host = read_depth_frames([paths[int(k)] for k in bad], n_threads, general_reader=general_reader)
         frames[torch.from_numpy(bad).to(device)] = torch.from_numpy(host.view(np.int16)).to(device)
     return frames[:F]
+
+
+def _pillow_rgb(path: str) -> np.ndarray:
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def decode_jpegs_device(stage, offsets: np.ndarray, nbytes: np.ndarray, device, host_decode: Callable[[int], np.ndarray]):
+    """JPEG payloads packed in the flat uint8 tensor ``stage`` (payload k at ``offsets[k]``, ``nbytes[k]`` long; page-locked
+    for an asynchronous copy) -> [F, H, W, 3] uint8 RGB on ``device``: one header parse on the host, one H2D copy of the
+    COMPRESSED bytes, one decode (mspa_jpeg_decode_device), one synchronisation to read the statuses.  (H, W) is the first
+    decodable payload's; a frame the parser or the device declines is decoded by ``host_decode(k)`` and uploaded into its row,
+    so the result is the host path's for every input.  ``stage`` may be reused once this returns."""
+    import torch
+    from . import engine
+    F = len(offsets)
+    host = stage.numpy()
+    desc, st = engine.jpeg_parse_host([host[int(o):int(o) + int(n)] for o, n in zip(offsets, nbytes)])
+    fields = engine.jpeg_desc_fields(desc)
+    ok = np.nonzero(st == 0)[0]
+    dev = torch.device(device)
+    if len(ok) == 0:
+        frames = [np.asarray(host_decode(k)) for k in range(F)]
+        return torch.from_numpy(np.stack(frames)).to(dev)
+    H, W = int(fields["h"][ok[0]]), int(fields["w"][ok[0]])
+    cap = (int((offsets + nbytes).max()) + 15) // 16 * 16
+    src = stage[:cap].to(dev, non_blocking=True)
+    out, status = engine.jpeg_decode_device(src, torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev),
+                                            torch.from_numpy(np.ascontiguousarray(nbytes, dtype=np.int64)).to(dev),
+                                            torch.from_numpy(desc).to(dev), (H, W))
+    bad = np.nonzero(status.cpu().numpy())[0]               # (synchronises: the copy out of `stage` is done)
+    for k in bad:
+        img = np.asarray(host_decode(int(k)))
+        if img.shape != (H, W, 3) or img.dtype != np.uint8:
+            raise ValueError(f"colour frame {int(k)}: the host reader gives {img.dtype} {img.shape}, the batch is ({H}, {W}, 3) uint8")
+        out[int(k)] = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+    return out
+
+
+def read_color_frames_device(paths: Sequence[str], device="cuda", n_threads: int = 8,
+                             general_reader: Optional[Callable[[str], np.ndarray]] = None):
+    """[F, H, W, 3] uint8 device tensor (RGB): the colour JPEGs at ``paths`` DECODED ON THE DEVICE -- the colour twin of
+    ``read_depth_frames_device``.  ``n_threads`` threads read the files into one page-locked buffer (file reads release the
+    interpreter lock), the headers are parsed in one native call, one H2D copy carries the compressed bytes, one kernel
+    sequence decodes them bit-identically to libjpeg-turbo.  A frame the device declines (progressive, damaged, another
+    size, a file that cannot be read here) is decoded by ``general_reader(path)`` -- default Pillow's ``convert("RGB")`` --
+    and uploaded into its row.  Synchronises once."""
+    import os
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    paths = list(paths)
+    F = len(paths)
+    reader = general_reader or _pillow_rgb
+    if F == 0:
+        return torch.zeros((0, 0, 0, 3), dtype=torch.uint8, device=device)
+    sizes = np.array([os.path.getsize(p) if p and os.path.isfile(p) else 0 for p in paths], dtype=np.int64)
+    offsets = np.zeros(F, dtype=np.int64)
+    offsets[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
+    total = int(offsets[-1] + (sizes[-1] + 15) // 16 * 16) + 16
+    stage = PINNED_POOL.take(total)
+    host = stage.numpy()
+
+    def load(k):
+        n = int(sizes[k])
+        if n:
+            with open(paths[k], "rb", buffering=0) as f:
+                got = f.readinto(memoryview(host[int(offsets[k]):int(offsets[k]) + n]))
+            sizes[k] = got
+    try:
+        with ThreadPoolExecutor(max_workers=max(1, int(n_threads))) as pool:
+            list(pool.map(load, range(F)))
+        return decode_jpegs_device(stage, offsets, sizes, device, lambda k: reader(paths[k]))
+    finally:
+        PINNED_POOL.give(stage)

@@ -47,7 +47,13 @@ class SceneOnDevice:
         self.frame_mats = torch.from_numpy(engine.frame_matrices(self.K, self.A, [E[k] for k in self.ids])).to(device)
         self.cam_mats = torch.from_numpy(engine.camera_matrices(self.K, self.E_aligned)).to(device)
         self.rgb = None
-        if color:
+        if isinstance(color, torch.Tensor):
+            # colour already decoded on the device (mspa.ingest.read_color_frames_device): [F, H, W, 3] uint8 in `ids` order, used as is
+            if not (color.is_cuda and color.dtype == torch.uint8 and color.dim() == 4 and color.shape[0] == len(self.ids)
+                    and color.shape[3] == 3 and color.is_contiguous()):
+                raise ValueError("color: a contiguous [F, H, W, 3] uint8 device tensor with one frame per valid image id")
+            self.rgb = color
+        elif color:
             self.rgb = torch.from_numpy(np.stack([color[k] for k in self.ids])).to(device)
         self.xyz = None
         if points_xyz is not None:

@@ -51,6 +51,7 @@ class SensScene:
     color_jpeg: Optional[List[bytes]]  # undecoded payloads (None if not requested)
     export_position: Optional[List[int]] = None   # position of each kept frame among the frames upstream exports (names)
     depth_device: object = None        # [F,DH,DW] int16 device tensor (the uint16 values) when the frames were inflated on the GPU
+    color_device: object = None        # [F,CH,CW,3] uint8 RGB device tensor when the colour payloads were decoded on the GPU
 
     @staticmethod
     def index_to_str(index: int) -> str:
@@ -58,7 +59,8 @@ class SensScene:
 
 
 def read_sens(path: str, frame_skip: int = 1, want_color: bool = False, keep_every: int = 1, n_threads: int = 0,
-              native: Optional[bool] = None, want_depth: bool = True, depth_to_device=None) -> SensScene:
+              native: Optional[bool] = None, want_depth: bool = True, depth_to_device=None,
+              color_to_device=None) -> SensScene:
     """Parse a .sens file keeping every ``frame_skip``-th frame (SENS:106-116) -- the frames upstream exports -- and, of
     those, only every ``keep_every``-th (UPD:20-68 keeps every 5th exported frame; the others need not be inflated at
     all).  One pass over the memory-mapped file collects the frame headers; the kept depth payloads are then inflated
@@ -71,7 +73,10 @@ def read_sens(path: str, frame_skip: int = 1, want_color: bool = False, keep_eve
     cross PCIe once and are inflated ON THE DEVICE, one wave per frame (``mspa_inflate_blocks_device``: the per-frame
     ``zlib.decompress`` of extract_posed_images.py:49-57) -- ``depth_device`` holds the [F, DH, DW] frames, ``depth`` stays empty.
     A frame the device declines (damaged stream, wrong size, checksum) is inflated by zlib on the host and uploaded on its own;
-    if zlib rejects it too the error is zlib's."""
+    if zlib rejects it too the error is zlib's.
+    ``color_to_device`` (a torch device; JPEG colour streams): the kept frames' JPEG payloads cross PCIe still compressed and
+    are decoded ON THE DEVICE (``mspa.ingest.decode_jpegs_device``, bit-identical to libjpeg-turbo) into ``color_device``
+    [F, CH, CW, 3] uint8 RGB; a payload the device declines is decoded by Pillow and uploaded on its own."""
     import mmap
     with open(path, "rb") as f:
         size = os.fstat(f.fileno()).st_size
@@ -193,6 +198,29 @@ def read_sens(path: str, frame_skip: int = 1, want_color: bool = False, keep_eve
                     if len(raw) != frame_bytes:
                         raise ValueError(f"{path}: frame {keep[k]} inflates to {len(raw)} bytes, expected {frame_bytes}")
                     depth[k] = np.frombuffer(raw, dtype="<u2").reshape(dh, dw)
+        color_device = None
+        if color_to_device is not None and color_compression == "jpeg" and F > 0:
+            from . import ingest
+            offs = np.zeros(F, dtype=np.int64)
+            total = 0
+            for k in range(F):
+                offs[k] = total
+                total += (c_len[k] + 15) // 16 * 16
+            stage = ingest.PINNED_POOL.take(total + 16)
+            host = stage.numpy()
+            whole = np.frombuffer(view, dtype=np.uint8)
+            for k in range(F):
+                host[offs[k]:offs[k] + c_len[k]] = whole[c_off[k]:c_off[k] + c_len[k]]
+            del whole
+
+            def pillow(k):
+                from PIL import Image
+                with Image.open(io.BytesIO(bytes(view[c_off[k]:c_off[k] + c_len[k]]))) as im:
+                    return np.asarray(im.convert("RGB"))
+            try:
+                color_device = ingest.decode_jpegs_device(stage, offs, np.asarray(c_len, dtype=np.int64), color_to_device, pillow)
+            finally:
+                ingest.PINNED_POOL.give(stage)
         view.release()
     finally:
         try:
@@ -200,7 +228,7 @@ def read_sens(path: str, frame_skip: int = 1, want_color: bool = False, keep_eve
         except BufferError:                   # a view escaped (error path): the mapping goes with the garbage collector
             pass
     return SensScene(name, mats[0], mats[1], mats[2], mats[3], color_compression, depth_compression, (ch, cw), (dh, dw),
-                     float(shift), int(n_frames), keep, poses, stamps, depth, jpeg, positions, depth_device)
+                     float(shift), int(n_frames), keep, poses, stamps, depth, jpeg, positions, depth_device, color_device)
 
 
 def text_roundtrip(matrix: np.ndarray) -> np.ndarray:

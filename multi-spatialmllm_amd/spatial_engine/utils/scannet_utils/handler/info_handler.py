@@ -278,6 +278,16 @@ class SceneInfoHandler:
         return np.where(mask_image == target_id + 1, 1, 0)
 
     # ---- resident scene (what the per-scene scripts use) -----------------------------------------
+    def color_frames_device(self, scene_id, image_ids=None, device="cuda", num_workers=8):
+        """[F, H, W, 3] uint8 RGB device tensor of the scene's colour frames (``image_ids``, default every image), the JPEG files
+        decoded ON THE DEVICE (``mspa.ingest.read_color_frames_device``); a frame the device declines is read by the host
+        colour reader (``_images.read_color_rgb``, the one ``project_image_to_3d_with_mask(with_color=True)`` uses).  No
+        reference counterpart: the reference decodes one frame per call on the host."""
+        from mspa import ingest
+        ids = self.get_all_image_ids(scene_id) if image_ids is None else list(image_ids)
+        paths = [self.get_image_path(scene_id, i) for i in ids]
+        return ingest.read_color_frames_device(paths, device, num_workers, general_reader=_images.read_color_rgb)
+
     def host_scene(self, scene_id, num_workers=8, with_points=True, decode=None, prepare=False):
         """The scene in host memory (``mspa.sweep.HostScene``): poses, the axis-aligned vertices and the depth frames of the
         frames with a finite pose (one ``cv2.imread`` per frame upstream, IH:149-155).
