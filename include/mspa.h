@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 170            /* 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
+#define MSPA_VERSION 180            /* 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+                                       mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
 
@@ -468,6 +469,41 @@ int64_t mspa_jpeg_workspace_bytes(int64_t n_images, int32_t h, int32_t w);
 int mspa_jpeg_decode_device(const void *src_dev, const int64_t *src_offsets_dev, const int64_t *src_bytes_dev, int64_t src_capacity,
                             const void *desc_dev, int64_t n_images, int32_t h, int32_t w, uint8_t *out_dev, int32_t *status_dev,
                             void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Annotated-image writes ON THE DEVICE (csrc/jpeg_encode.hip, arithmetic in csrc/jpeg_encode_core.h): the drawing and the
+ * JPEG encode of mspa/annotate.py's PillowAnnotator, byte for byte.
+ *
+ * mspa_jpeg_encode_capacity  worst-case bytes of one file of h x w at `subsampling` (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0, Pillow's
+ *   numbering); -1 for a bad argument.  1 <= h, w <= 65535.
+ * mspa_jpeg_encode_workspace_bytes  bytes of scratch an encode of n_images h x w images needs; -1 for a bad argument.
+ * mspa_jpeg_encode_header_host  the file's bytes up to the end of SOS (SOI, APP0 JFIF 1.1 with density 1:1 and no units, DQT
+ *   luma, DQT chroma, SOF0, DHT DC0 / AC0 / DC1 / AC1, SOS) into dst (capacity >= 623); *nbytes = its length.
+ * mspa_jpeg_encode_device  rgb_dev = [n_images, h, w, 3] uint8 RGB -> out_dev + k * out_pitch = image k's whole file (header,
+ *   entropy-coded data, EOI), equal to Pillow 12 / libjpeg-turbo `Image.fromarray(rgb).save(f, "JPEG", quality=quality,
+ *   subsampling=subsampling)`: standard Huffman tables, JDCT_ISLOW, no restart markers.  out_bytes_dev[k] (int64) = the file's
+ *   length; a file longer than out_pitch is written up to out_pitch only (a pitch of mspa_jpeg_encode_capacity never
+ *   truncates).  quality 1..100.  workspace: caller-owned, 16-byte aligned, at least mspa_jpeg_encode_workspace_bytes bytes;
+ *   contents undefined afterwards.  n_images <= 65 535.  Only enqueues on `stream`.
+ * mspa_draw_spans_device  n_spans int32 records (image, y, x0, x1, 0xRRGGBB) painted into images_dev = [n_images, h, w, 3] uint8:
+ *   pixels x0..x1 (inclusive, clipped) of row y take the colour.  Records must be grouped by (image, y) with call order kept
+ *   inside a group; the last record of a group that covers a pixel wins.  Records outside the images are ignored.
+ * mspa_blend_masks_device  n_labels int64 records (image, x, y, mask w, mask h, 0xRRGGBB ink, mask offset, 0): the 8-bit mask at
+ *   masks_dev + offset ([mask h, mask w], row-major) blended onto the image at (x, y), clipped at the borders, with Pillow's
+ *   arithmetic t = ink * m + px * (255 - m) + 128, px' = ((t >> 8) + t) >> 8.  Records must be grouped by image with call order
+ *   kept inside a group; overlapping labels blend in that order.  A record whose mask lies outside [0, masks_bytes) is ignored.
+ */
+int64_t mspa_jpeg_encode_capacity(int32_t h, int32_t w, int32_t subsampling);
+int64_t mspa_jpeg_encode_workspace_bytes(int64_t n_images, int32_t h, int32_t w, int32_t subsampling);
+int mspa_jpeg_encode_header_host(int32_t h, int32_t w, int32_t quality, int32_t subsampling, uint8_t *dst, int64_t capacity,
+                                 int64_t *nbytes);
+int mspa_jpeg_encode_device(const uint8_t *rgb_dev, int64_t n_images, int32_t h, int32_t w, int32_t quality, int32_t subsampling,
+                            uint8_t *out_dev, int64_t out_pitch, int64_t *out_bytes_dev, void *workspace, int64_t workspace_bytes,
+                            void *stream);
+int mspa_draw_spans_device(const int32_t *spans_dev, int64_t n_spans, uint8_t *images_dev, int64_t n_images, int32_t h, int32_t w,
+                           void *stream);
+int mspa_blend_masks_device(const int64_t *labels_dev, int64_t n_labels, const uint8_t *masks_dev, int64_t masks_bytes,
+                            uint8_t *images_dev, int64_t n_images, int32_t h, int32_t w, void *stream);
 
 /*
  * K4 -- per-pair camera relations: the distance / yaw / pitch columns of CFR.process_scene's pair

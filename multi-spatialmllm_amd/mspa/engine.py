@@ -271,6 +271,94 @@ def jpeg_decode_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.T
     return out, status
 
 
+JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+
+
+def _subsampling(subsampling) -> int:
+    if isinstance(subsampling, str):
+        _require(subsampling in JPEG_SUBSAMPLING, f"subsampling: one of {sorted(JPEG_SUBSAMPLING)}")
+        return JPEG_SUBSAMPLING[subsampling]
+    _require(int(subsampling) in (0, 1, 2), "subsampling: 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)")
+    return int(subsampling)
+
+
+def jpeg_encode_capacity(hw: Tuple[int, int], subsampling="4:2:0") -> int:
+    """Worst-case bytes of one baseline JPEG file of ``hw`` (mspa_jpeg_encode_capacity)."""
+    n = int(_lib.load().mspa_jpeg_encode_capacity(int(hw[0]), int(hw[1]), _subsampling(subsampling)))
+    _require(n > 0, "hw: 1 <= H, W <= 65535")
+    return n
+
+
+def jpeg_encode_header_host(hw: Tuple[int, int], quality: int = 95, subsampling="4:2:0") -> bytes:
+    """The bytes up to the end of SOS of the file ``jpeg_encode_device`` (and Pillow) writes for this shape, quality and
+    subsampling (mspa_jpeg_encode_header_host)."""
+    buf = np.zeros((1024,), dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().mspa_jpeg_encode_header_host(int(hw[0]), int(hw[1]), int(quality), _subsampling(subsampling),
+                                                         buf.ctypes.data, buf.size, ctypes.byref(n)))
+    return buf[:n.value].tobytes()
+
+
+def jpeg_encode_device(rgb: torch.Tensor, quality: int = 95, subsampling="4:2:0", out: Optional[torch.Tensor] = None,
+                       nbytes: Optional[torch.Tensor] = None):
+    """[n, H, W, 3] uint8 RGB on the device -> (out [n, pitch] uint8, nbytes [n] int64): row k holds image k's whole baseline
+    JPEG file, byte for byte what Pillow's ``Image.fromarray(rgb[k]).save(f, "JPEG", quality=quality,
+    subsampling=subsampling)`` writes (mspa_jpeg_encode_device).  The default ``out`` has the worst-case pitch
+    (``jpeg_encode_capacity``); with a narrower one, a file longer than the pitch is cut off there and its ``nbytes`` says how
+    long it is.  Only enqueues; read ``nbytes`` after a synchronisation."""
+    _require_gpu()
+    _require(rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3,
+             "rgb: a contiguous [n, H, W, 3] uint8 device tensor")
+    n, H, W = int(rgb.shape[0]), int(rgb.shape[1]), int(rgb.shape[2])
+    _require(1 <= H <= 65535 and 1 <= W <= 65535, "rgb: 1 <= H, W <= 65535")
+    _require(isinstance(quality, (int, np.integer)) and 1 <= int(quality) <= 100, "quality: an integer in 1..100")
+    _require(n <= 65535, "at most 65 535 images in one call")
+    ss = _subsampling(subsampling)
+    if out is None:
+        out = torch.empty((n, jpeg_encode_capacity((H, W), ss)), dtype=torch.uint8, device=rgb.device)
+    _require(out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] >= n and out.is_contiguous(),
+             "out: a contiguous [n, pitch] uint8 device tensor")
+    if nbytes is None:
+        nbytes = torch.empty((n,), dtype=torch.int64, device=rgb.device)
+    _require(nbytes.is_cuda and nbytes.dtype == torch.int64 and nbytes.is_contiguous() and nbytes.shape[0] >= n,
+             "nbytes: int64 [n] on the device")
+    if n == 0:
+        return out, nbytes
+    lib = _lib.load()
+    ws_bytes = int(lib.mspa_jpeg_encode_workspace_bytes(n, H, W, ss))
+    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=rgb.device).view(torch.uint8)   # 16-byte aligned
+    _lib.check(lib.mspa_jpeg_encode_device(_ptr(rgb), n, H, W, int(quality), ss, _ptr(out), int(out.shape[1]),
+                                           _ptr(nbytes), work.data_ptr(), int(work.numel()), _stream_ptr()))
+    return out, nbytes
+
+
+def draw_spans_device(images: torch.Tensor, spans: torch.Tensor) -> None:
+    """Paint int32 span records [S, 5] = (image, y, x0, x1, 0xRRGGBB) into ``images`` ([n, H, W, 3] uint8, in place;
+    mspa_draw_spans_device).  Records grouped by (image, y), call order kept inside a group (``annotate.pack_spans``)."""
+    _require_gpu()
+    _require(images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3,
+             "images: a contiguous [n, H, W, 3] uint8 device tensor")
+    _require(spans.is_cuda and spans.dtype == torch.int32 and spans.is_contiguous() and spans.dim() == 2 and spans.shape[1] == 5,
+             "spans: a contiguous [S, 5] int32 device tensor")
+    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    _lib.check(_lib.load().mspa_draw_spans_device(_ptr(spans), int(spans.shape[0]), _ptr(images), n, H, W, _stream_ptr()))
+
+
+def blend_masks_device(images: torch.Tensor, labels: torch.Tensor, masks: torch.Tensor) -> None:
+    """Blend 8-bit label masks into ``images`` ([n, H, W, 3] uint8, in place) with Pillow's arithmetic
+    (mspa_blend_masks_device): int64 records [L, 8] = (image, x, y, mask w, mask h, 0xRRGGBB, offset into ``masks``, 0), grouped
+    by image with call order kept inside a group (``annotate.DeviceAnnotator`` packs them)."""
+    _require_gpu()
+    _require(images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3,
+             "images: a contiguous [n, H, W, 3] uint8 device tensor")
+    _require(labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[1] == 8,
+             "labels: a contiguous [L, 8] int64 device tensor")
+    _require(masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 1, "masks: a flat uint8 device tensor")
+    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    _lib.check(_lib.load().mspa_blend_masks_device(_ptr(labels), int(labels.shape[0]), _ptr(masks), int(masks.numel()), _ptr(images),
+                                                   n, H, W, _stream_ptr()))
+
+
 def _require_pinhole(mats: torch.Tensor):
     """MSPA_PAIR_FAST reads the camera-2 depth off the third image row: K's third row must be 0 0 1 0 in EVERY frame record
     (include/mspa.h).  The records live on the device, so the check is one read-back of all frames' rows the first time a

@@ -35,7 +35,7 @@ class DepthCoorEngineBase:
         self.visibility_info = VisibilityInfoHandler(visibility_info_path)
         self.max_samples = -1
         self.templates = self.TEMPLATE_SET
-        self.annotator = None          # dot variants: mspa.annotate.PillowAnnotator() unless the caller sets another one
+        self.annotator = None          # dot variants: mspa.annotate.default_annotator() unless the caller sets another one
 
     # -- helpers ------------------------------------------------------------------------------
     def _warn(self, message):
@@ -68,9 +68,15 @@ class DepthCoorEngineBase:
 
     def _annotator(self):
         if self.annotator is None:
-            from mspa.annotate import PillowAnnotator
-            self.annotator = PillowAnnotator()
+            from mspa.annotate import default_annotator
+            self.annotator = default_annotator()
         return self.annotator
+
+    def _flushed(self, records):
+        """``records`` once every annotated file named while building them exists with its final bytes."""
+        from mspa.annotate import flush_annotator
+        flush_annotator(self.annotator)
+        return records
 
     def generate_qa_training_single_scene(self, scene_id):
         raise NotImplementedError

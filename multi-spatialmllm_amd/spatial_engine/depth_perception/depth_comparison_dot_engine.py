@@ -38,11 +38,11 @@ class DepthComparisonDotQAEngine(DepthCoorEngineBase):
             numeric_fn, image_hw = None, self.scene_info.get_image_shape(scene_id)
         else:
             image_ids, n_visible, numeric_fn, image_hw = self._scene_inputs(scene_id, scene)
-        return heads.depth_comparison_records(
+        return self._flushed(heads.depth_comparison_records(
             scene_id, image_ids, n_visible, numeric_fn, image_hw, self.max_samples, self.templates, random,
             self.max_n_points_per_image, dot=True, on_mark=self._mark, dry_run=dry_run,
             on_skip=lambda s, img, v: self._warn(f"Warning: Points {v} in image {img} in scene {s} have the same depth.\n"
-                                                 " Skip this pair."))
+                                                 " Skip this pair.")))
 
     def generate_qa_training_single_scene(self, scene_id):
         return self._scene_records_on(None, scene_id, None)

@@ -34,10 +34,10 @@ class DepthEstimationDotQAEngine(DepthCoorEngineBase):
 
     def _scene_records_on(self, scene, scene_id, draws):
         image_ids, n_visible, numeric_fn, image_hw = self._scene_inputs(scene_id, scene)
-        return heads.depth_estimation_records_fn(
+        return self._flushed(heads.depth_estimation_records_fn(
             scene_id, image_ids, n_visible, numeric_fn, image_hw, self.max_samples, self.templates, random,
             self.max_n_points_per_image, dot=True, on_mark=self._mark, draws=draws,
-            on_skip=lambda s, img, v: self._warn(f"Warning: Point-Id {v[0]} is not visible in image {img} in scene {s}.\n"))
+            on_skip=lambda s, img, v: self._warn(f"Warning: Point-Id {v[0]} is not visible in image {img} in scene {s}.\n")))
 
     def generate_qa_training_single_scene(self, scene_id):
         return self._scene_records_on(None, scene_id, self._scene_draws(scene_id))

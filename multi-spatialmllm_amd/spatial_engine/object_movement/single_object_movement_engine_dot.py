@@ -10,7 +10,7 @@ import torch
 
 from mspa import engine, heads
 from mspa import templates as T
-from mspa.annotate import Mark
+from mspa.annotate import Mark, flush_annotator
 from mspa.hostinfo import quietly
 from spatial_engine.object_movement.single_object_movement_engine_coord import (TwoFrameVideoQAEngine, filter_large_groups,
                                                                                 jpeg_size, rigid_body_segmentation,
@@ -33,8 +33,8 @@ class TwoFrameVideoQAEngineDot(TwoFrameVideoQAEngine):
 
     def _annotator(self):
         if self.annotator is None:
-            from mspa.annotate import PillowAnnotator
-            self.annotator = PillowAnnotator()
+            from mspa.annotate import default_annotator
+            self.annotator = default_annotator()
         return self.annotator
 
     def format_training_samples(self, sample_pairs, intrinsics, scene_id, points_pos_world, points_pos_cam, image_height,
@@ -45,8 +45,10 @@ class TwoFrameVideoQAEngineDot(TwoFrameVideoQAEngine):
         os.makedirs(save_dir, exist_ok=True)
         radius = int(image_width) // 100
 
-        def needs(name):
-            return not os.path.exists(os.path.join(save_dir, name))
+        def needs(name):                    # a file still queued in a batching annotator counts as written
+            path = os.path.join(save_dir, name)
+            pending = getattr(self.annotator, "pending", None)
+            return not (os.path.exists(path) or (pending is not None and pending(path)))
 
         def on_mark(frame1, frame2, point_index, pixel, color):
             if color is not None:
@@ -56,11 +58,13 @@ class TwoFrameVideoQAEngineDot(TwoFrameVideoQAEngine):
             if needs(f"{frame2:05d}.jpg"):
                 self._annotator().copy(os.path.join(base_img_dir, scene_id, f"{frame2:05d}.jpg"),
                                        os.path.join(save_dir, f"{frame2:05d}.jpg"))
-        return heads.object_movement_records(scene_id, np.asarray(points_pos_cam), np.asarray(extrinsics_w2c), intrinsics,
+        records = heads.object_movement_records(scene_id, np.asarray(points_pos_cam), np.asarray(extrinsics_w2c), intrinsics,
                                              (int(image_height), int(image_width)), sample_pairs, self.question_type,
                                              self.templates, random, dot=True, needs_annotation=needs, on_mark=on_mark,
                                              obj_threshold=self.object_not_moving_threshold,
                                              cam_threshold=self.camera_not_moving_threshold)
+        flush_annotator(self.annotator)     # every file named above exists with its final bytes
+        return records
 
     def generate_qa_training_single_scene(self, input_file, base_img_dir, npoints_per_group=5, npairs_per_bin=1e8,
                                           img_output_dir="", augment=True, augment_ratio=1.0, _loaded=None):

@@ -10,7 +10,7 @@ import numpy as np
 
 from mspa import heads
 from mspa import templates as T
-from mspa.annotate import Mark
+from mspa.annotate import Mark, flush_annotator
 from mspa.sampling import sample_dataframe  # noqa: F401
 from spatial_engine.visual_correspondence.visual_correspondence_qa_engine_coor_2_coor import (_ResidentScenes, _load_visibility,
                                                                                                _shuffle_and_write)
@@ -21,14 +21,14 @@ np.random.seed(2)
 TEMPLATE_SET = T.VISUAL_CORRESPONDENCE_DOT
 USE_PICKLE = True
 DEBUG = False
-ANNOTATOR = None          # mspa.annotate.PillowAnnotator() unless the caller installs another one
+ANNOTATOR = None          # mspa.annotate.default_annotator() unless the caller installs another one
 
 
 def _annotator():
     global ANNOTATOR
     if ANNOTATOR is None:
-        from mspa.annotate import PillowAnnotator
-        ANNOTATOR = PillowAnnotator()
+        from mspa.annotate import default_annotator
+        ANNOTATOR = default_annotator()
     return ANNOTATOR
 
 
@@ -54,8 +54,10 @@ def _records(rows, scene_infos, visibility_info_dict, warning_file, image_output
         with open(warning_file, "a") as wf:
             wf.write(message)
     backend = heads.GpuCorrespondenceBackend(resident.get, resident.get_bits)
-    return heads.visual_correspondence_dot_dataset(rows, backend, TEMPLATE_SET, random, warn, _marker(scene_infos, image_output_dir),
-                                                   ctx=ctx, transform=transform)
+    out = heads.visual_correspondence_dot_dataset(rows, backend, TEMPLATE_SET, random, warn, _marker(scene_infos, image_output_dir),
+                                                  ctx=ctx, transform=transform)
+    flush_annotator(ANNOTATOR)              # every file named so far exists with its final bytes
+    return out
 
 
 def build_training_sample(scene_infos, row, idx: int, visibility_info_dict, warning_file, max_points_per_pair=1,
