@@ -408,7 +408,8 @@ int mspa_inflate_zlib_fast_host(const void *src_host, int64_t src_bytes, void *d
  * mspa_png_unfilter_device     n_images inflated scanline blocks (h rows of 1 filter byte + 2 w sample bytes, image k at raw_dev +
  *   k * raw_pitch) -> out_dev[k, h, w] uint16 in host byte order: the five PNG row filters (None / Sub / Up / Average / Paeth)
  *   undone, big-endian samples swapped.  Images whose status_dev[k] is non-zero on entry are skipped; an image with a filter
- *   byte > 4 gets status 3.
+ *   byte > 4 gets status 3.  raw_pitch >= h * (2 w + 1) and a multiple of 4, raw_dev 4-byte aligned (MSPA_EINVAL otherwise);
+ *   out_dev needs no more than the 2-byte alignment of uint16.
  * mspa_png_pack_idat_host      the host half: the n_files 16-bit greyscale non-interlaced h x w PNG files are read by up to
  *   n_threads threads and the payloads of their IDAT chunks -- the scanlines' zlib stream -- packed into dst_host (pinned memory
  *   the H2D copy reads) at offsets_host[k] (multiples of 16), bytes_host[k] long.  Call with dst_host == NULL first: only the

@@ -878,7 +878,7 @@ __device__ void unfilter_rows(const uint8_t *__restrict__ raw, int64_t raw_pitch
     uint32_t prior[8];
 #pragma unroll
     for (int d = 0; d < 8; ++d) prior[d] = 0u;
-    const int64_t last = (raw_pitch - 4) & ~(int64_t)3;          // no load past the image's own block
+    const int64_t last = (raw_pitch - 4) & ~(int64_t)3;          // no load past the image's own block (the ABI takes raw_pitch % 4 == 0 only)
     uint32_t v[9], vn[9];
     auto load_row = [&](int y, uint32_t *dstv) {
         const int64_t a0 = (int64_t)y * stride + 1;
@@ -970,7 +970,7 @@ constexpr int kUpRowPairs = 2048;                                // widest image
 __device__ void unfilter_skewed_pairs(const uint8_t *__restrict__ raw, int64_t raw_pitch, int64_t stride, int32_t h, int32_t w,
                                       uint16_t *__restrict__ out, int lane, uint32_t *up_row) {
     const int wp = w >> 1;                                       // pixel pairs per row
-    const int64_t last = (raw_pitch - 4) & ~(int64_t)3;          // no load past the image's own block
+    const int64_t last = (raw_pitch - 4) & ~(int64_t)3;          // no load past the image's own block (the ABI takes raw_pitch % 4 == 0 only)
     uint32_t *const out32 = (uint32_t *)out;
     for (int y0 = 0; y0 < h; y0 += 64) {
         const int y = y0 + lane;
@@ -1182,8 +1182,12 @@ extern "C" int mspa_png_unfilter_device(const void *raw_dev, int64_t raw_pitch, 
                                         uint16_t *out_dev, int32_t *status_dev, void *stream) {
     if (n_images < 0 || h <= 0 || w <= 0 || raw_pitch < (int64_t)h * ((int64_t)w * 2 + 1))
         return fail(MSPA_EINVAL, "mspa_png_unfilter_device: bad size");
+    // Both fast paths load aligned dwords clamped to the image's last one, (raw_pitch - 4) & ~3: with a pitch that is not a multiple
+    // of 4 the dword holding the last row's final bytes lies past it and is read from the wrong place
+    if (raw_pitch & 3) return fail(MSPA_EINVAL, "mspa_png_unfilter_device: raw_pitch must be a multiple of 4");
     if (n_images == 0) return MSPA_OK;
     if (!raw_dev || !out_dev || !status_dev) return fail(MSPA_EINVAL, "mspa_png_unfilter_device: null pointer");
+    if ((uintptr_t)raw_dev & 3u) return fail(MSPA_EINVAL, "mspa_png_unfilter_device: raw_dev must be 4-byte aligned");
     if (n_images > 0x7fffffffll) return fail(MSPA_EINVAL, "mspa_png_unfilter_device: too many images");
     hipLaunchKernelGGL(dinf::png_unfilter_kernel, dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)stream, (const uint8_t *)raw_dev,
                        raw_pitch, h, w, out_dev, status_dev);

@@ -189,11 +189,14 @@ def inflate_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torc
 def png_unfilter_device(raw: torch.Tensor, h: int, w: int, status: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``raw[k, : h * (2 w + 1)]`` -- the inflated scanlines of n 16-bit greyscale PNG images -- to ``out[k, h, w]`` (int16
     storage of the uint16 depth values, like every depth tensor here): the five PNG row filters undone on the device
-    (mspa_png_unfilter_device).  Images with ``status[k] != 0`` are skipped; a filter byte > 4 sets status 3."""
+    (mspa_png_unfilter_device).  Images with ``status[k] != 0`` are skipped; a filter byte > 4 sets status 3.  ``raw`` starts
+    4-byte aligned and its pitch is a multiple of 4 (MspaError otherwise, as from the C ABI)."""
     _require_gpu()
     n = int(raw.shape[0])
     _require(raw.is_cuda and raw.dtype == torch.uint8 and raw.dim() == 2 and raw.is_contiguous()
              and raw.shape[1] >= h * (2 * w + 1), "raw: [n, pitch] uint8 with pitch >= h * (2 w + 1)")
+    if raw.data_ptr() % 4 or int(raw.shape[1]) % 4:
+        raise _lib.MspaError(_lib.MSPA_EINVAL, "png_unfilter_device: raw must start 4-byte aligned, with a pitch that is a multiple of 4")
     _require(status.is_cuda and status.dtype == torch.int32 and status.shape[0] >= n, "status: int32 [n] on the device")
     if out is None:
         out = torch.empty((n, h, w), dtype=torch.int16, device=raw.device)

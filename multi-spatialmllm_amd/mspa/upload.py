@@ -140,10 +140,14 @@ class UploadSlot:
             # copies below run on `copy_stream`: order them behind everything already enqueued on the allocation stream.
             copy_stream.wait_stream(torch.cuda.current_stream(self.device))
 
-    def _ensure_decode(self, n_frames, depth_hw, comp_bytes):
+    def _ensure_decode(self, n_frames, depth_hw, comp_bytes) -> bool:
+        """Scanline scratch, status and compressed-byte buffers for ``n_frames`` frames of ``depth_hw``; True when any of them
+        was (re)allocated -- a new depth shape changes the scanline pitch."""
         h, w = depth_hw
         pitch = (h * (2 * w + 1) + 255) // 256 * 256
+        grown = False
         if self.d_raw is None or self.d_raw.shape[0] < n_frames or self.d_raw.shape[1] != pitch:
+            grown = True
             self.d_raw = torch.empty((max(n_frames, self.cap_frames), pitch), dtype=torch.uint8, device=self.device)
             self.d_status = torch.zeros((self.d_raw.shape[0],), dtype=torch.int32, device=self.device)
             self.d_off = torch.zeros((self.d_raw.shape[0],), dtype=torch.int64, device=self.device)
@@ -152,17 +156,17 @@ class UploadSlot:
             self.h_off = torch.zeros((self.d_raw.shape[0],), dtype=torch.int64).pin_memory()
             self.h_nb = torch.zeros_like(self.h_off).pin_memory()
         if self.d_comp is None or self.d_comp.numel() < comp_bytes:
+            grown = True
             self.d_comp = torch.empty(((int(comp_bytes) + (16 << 20) - 1) // (16 << 20) * (16 << 20),), dtype=torch.uint8,
                                       device=self.device)
+        return grown
 
     def _upload_and_decode(self, packed, F, stream):
         """The compressed frames -> ``d_depth[:F]`` on ``stream``: one H2D copy of the packed bytes, one wave per frame inflates
         (mspa_inflate_blocks_device), one wave per frame undoes the row filters (mspa_png_unfilter_device).  The per-frame
         status comes back asynchronously; ``finish_decode`` looks at it once ``ready`` has passed."""
         h, w = packed.hw
-        grown = self.d_raw is None or self.d_raw.shape[0] < F or self.d_comp is None or self.d_comp.numel() < packed.capacity
-        self._ensure_decode(F, (h, w), packed.capacity)
-        if grown:                                    # fresh blocks of the caching allocator: behind whatever the allocating
+        if self._ensure_decode(F, (h, w), packed.capacity):     # fresh blocks of the caching allocator: behind whatever the allocating
             stream.wait_stream(torch.cuda.current_stream(self.device))      # thread's stream still has queued on them
         self.h_off[:F] = torch.from_numpy(packed.offsets)
         self.h_nb[:F] = torch.from_numpy(np.where(packed.status == 0, packed.nbytes, 0))    # a declined file: an empty stream
@@ -195,10 +199,26 @@ class UploadSlot:
             self.d_depth[torch.from_numpy(bad).to(self.device)] = torch.from_numpy(host.view(np.int16)).to(self.device)
         packed.release()
 
+    def drop_decode(self):
+        """Forget a decode nobody will finish (an iteration abandoned with the scene staged, a staging error after the decode was
+        enqueued): its packed buffer goes back to its pool once the slot's stream has read it, and the slot's next user does not
+        look at the old scene's status or write its frames."""
+        if self.pending_decode is not None:
+            packed, _ = self.pending_decode
+            self.pending_decode = None
+            if self.decoded is not None:
+                self.decoded.synchronize()       # (recorded behind the H2D copy that reads the packed buffer)
+            packed.release()
+        self.in_flight_frames = 0
+
     def stage_and_upload(self, sc, copy_stream) -> SceneOnDevice:
         """Fill the pinned buffers from ``sc`` (K, A, E, depth, color_hw, points) and enqueue the copies on ``copy_stream``.
         A scene that carries ``packed`` compressed frames (``sweep.HostScene.packed``) is decoded on the device instead, on
         the slot's own stream, so that several scenes' decodes run side by side."""
+        if self.pending_decode is not None:      # an earlier scene's decode nobody finished: not this scene's
+            in_flight = getattr(self, "in_flight_frames", 0)      # (a prefetcher has set it to THIS scene's frames already)
+            self.drop_decode()
+            self.in_flight_frames = in_flight
         prep = getattr(sc, "prepared", None)
         ids = prep["ids"] if prep is not None else valid_image_ids(sc.E)
         F = len(ids)
@@ -418,6 +438,8 @@ class ScenePrefetcher:
             if worker is not None:
                 worker.join()
             torch.cuda.synchronize(dev_index)           # neither stream touches the slots any more
+            for sl in my_slots:                         # scenes staged but never consumed, or whose staging failed afterwards
+                sl.drop_decode()
             _give_slots(self.device, my_slots)
 
     @staticmethod

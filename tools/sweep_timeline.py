@@ -83,7 +83,8 @@ def main():
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             h, w = packed.hw
             from mspa import engine
-            self._ensure_decode(F, (h, w), packed.capacity)
+            if self._ensure_decode(F, (h, w), packed.capacity):
+                stream.wait_stream(torch.cuda.current_stream(self.device))
             self.h_off[:F] = torch.from_numpy(packed.offsets)
             self.h_nb[:F] = torch.from_numpy(np.where(packed.status == 0, packed.nbytes, 0))
             with torch.cuda.stream(stream):
