@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 180            /* 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 190            /* 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -505,6 +505,33 @@ int mspa_draw_spans_device(const int32_t *spans_dev, int64_t n_spans, uint8_t *i
                            void *stream);
 int mspa_blend_masks_device(const int64_t *labels_dev, int64_t n_labels, const uint8_t *masks_dev, int64_t masks_bytes,
                             uint8_t *images_dev, int64_t n_images, int32_t h, int32_t w, void *stream);
+
+/*
+ * Depth-PNG writes ON THE DEVICE (csrc/png_encode.hip, arithmetic in csrc/png_encode_core.h): 16-bit greyscale, non-interlaced
+ * PNG files whose pixels equal the input and whose filtered scanlines are Pillow's (`Image.fromarray(depth).save(path)`); the
+ * deflate stream is the encoder's own, so the files are not Pillow's byte for byte.  A g++ build of png_encode_core.h is the
+ * reference the device equals byte for byte.
+ *
+ * mspa_png_encode_capacity  worst-case bytes of one file of h x w; -1 for a bad size (1 <= h, w <= 8192).  The bound: the
+ *   filtered stream has N = h (1 + 2 w) bytes in ceil(N / 32768) deflate blocks; a block is written dynamic only when that is
+ *   shorter than 42 + 8 L bits (L its bytes), otherwise stored, which is 3 + <= 7 padding + 32 + 8 L bits; so the deflate stream
+ *   has at most N + ceil(42 blocks / 8) bytes, the zlib stream 6 more (header and Adler-32), and the file adds 33 (signature,
+ *   IHDR), 12 per IDAT chunk of at most 16 384 zlib bytes, and 12 (IEND).
+ * mspa_png_encode_workspace_bytes  bytes of scratch an encode of n frames of h x w needs (about 7 h (2 w + 1) n); -1 for a bad
+ *   argument (n outside 0..65535 or a bad size).
+ * mspa_png_encode_device  depth_dev = [n, h, w] uint16 values stored as int16 (the layout of depth_device /
+ *   read_depth_frames_device), contiguous -> out_dev + k * out_pitch = frame k's whole file, nbytes_dev[k] (int64) = its length.
+ *   Bytes [0, nbytes rounded up to 4) of a row are written (the padding bytes are 0); the rest of the row is left as it was.
+ *   Limits: 1 <= h, w <= 8192, 0 <= n <= 65535 (n = 0 writes nothing and returns MSPA_OK).
+ *   Alignment: depth_dev 2 bytes, out_dev 4 bytes, nbytes_dev 8 bytes, workspace 16 bytes; out_pitch a multiple of 4 and
+ *   >= mspa_png_encode_capacity(h, w).  workspace: caller-owned, >= mspa_png_encode_workspace_bytes(n, h, w); contents
+ *   undefined afterwards.  Anything else (a null pointer included) returns MSPA_EINVAL before anything is enqueued, so the
+ *   outputs are left unwritten.  Only enqueues on `stream`.
+ */
+int64_t mspa_png_encode_capacity(int32_t h, int32_t w);
+int64_t mspa_png_encode_workspace_bytes(int64_t n, int32_t h, int32_t w);
+int mspa_png_encode_device(const int16_t *depth_dev, int64_t n, int32_t h, int32_t w, uint8_t *out_dev, int64_t out_pitch,
+                           int64_t *nbytes_dev, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * K4 -- per-pair camera relations: the distance / yaw / pitch columns of CFR.process_scene's pair

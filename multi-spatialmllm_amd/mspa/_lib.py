@@ -94,6 +94,10 @@ _SIGNATURES = {
     "mspa_jpeg_encode_header_host": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, POINTER(c_int64)]),
     "mspa_jpeg_encode_device": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_int64, c_void_p]),
+    "mspa_png_encode_capacity": (c_int64, [c_int32, c_int32]),
+    "mspa_png_encode_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "mspa_png_encode_device": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
     "mspa_draw_spans_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "mspa_blend_masks_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "mspa_check_visibility": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,

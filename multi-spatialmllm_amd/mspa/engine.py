@@ -335,6 +335,43 @@ def jpeg_encode_device(rgb: torch.Tensor, quality: int = 95, subsampling="4:2:0"
     return out, nbytes
 
 
+def png_encode_capacity(hw: Tuple[int, int]) -> int:
+    """Worst-case bytes of one 16-bit greyscale PNG file of ``hw`` (mspa_png_encode_capacity)."""
+    n = int(_lib.load().mspa_png_encode_capacity(int(hw[0]), int(hw[1])))
+    _require(n > 0, "hw: 1 <= H, W <= 8192")
+    return n
+
+
+def png_encode_device(depth: torch.Tensor, out: Optional[torch.Tensor] = None, nbytes: Optional[torch.Tensor] = None):
+    """[n, H, W] depth on the device (uint16 values stored as int16, as ``depth_device``; uint16 is accepted too) ->
+    (files [n, pitch] uint8, nbytes [n] int64): row k holds frame k's whole 16-bit greyscale PNG file, whose pixels equal
+    the input and whose filtered scanlines are Pillow's (mspa_png_encode_device).  The default ``out`` has the pitch
+    ``png_encode_capacity`` rounded up to 4.  Runs on the current torch stream and only enqueues; read ``nbytes`` after a
+    synchronisation."""
+    _require_gpu()
+    _require(depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous() and depth.dim() == 3,
+             "depth: a contiguous [n, H, W] int16 (or uint16) device tensor")
+    n, H, W = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
+    _require(1 <= H <= 8192 and 1 <= W <= 8192, "depth: 1 <= H, W <= 8192")
+    _require(n <= 65535, "at most 65 535 frames in one call")
+    if out is None:
+        out = torch.empty((n, (png_encode_capacity((H, W)) + 3) // 4 * 4), dtype=torch.uint8, device=depth.device)
+    _require(out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] >= n and out.is_contiguous(),
+             "out: a contiguous [n, pitch] uint8 device tensor")
+    if nbytes is None:
+        nbytes = torch.empty((n,), dtype=torch.int64, device=depth.device)
+    _require(nbytes.is_cuda and nbytes.dtype == torch.int64 and nbytes.is_contiguous() and nbytes.shape[0] >= n,
+             "nbytes: int64 [n] on the device")
+    if n == 0:
+        return out, nbytes
+    lib = _lib.load()
+    ws_bytes = int(lib.mspa_png_encode_workspace_bytes(n, H, W))
+    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=depth.device).view(torch.uint8)   # 16-byte aligned
+    _lib.check(lib.mspa_png_encode_device(_ptr(depth), n, H, W, _ptr(out), int(out.shape[1]), _ptr(nbytes), work.data_ptr(),
+                                          int(work.numel()), _stream_ptr()))
+    return out, nbytes
+
+
 def draw_spans_device(images: torch.Tensor, spans: torch.Tensor) -> None:
     """Paint int32 span records [S, 5] = (image, y, x0, x1, 0xRRGGBB) into ``images`` ([n, H, W, 3] uint8, in place;
     mspa_draw_spans_device).  Records grouped by (image, y), call order kept inside a group (``annotate.pack_spans``)."""

@@ -273,24 +273,71 @@ def depth_frames(sens: SensScene, image_frame_skip: int = 5) -> Dict[str, np.nda
     return {SensScene.index_to_str(e): sens.depth[k] for k, e in _kept(sens, image_frame_skip)}
 
 
-def export_posed_images(sens: SensScene, output_path: str, with_depth_png: bool = True):
+def export_posed_images(sens: SensScene, output_path: str, with_depth_png: bool = True, depth_png: str = "pillow"):
     """The folder extract_posed_images.process_scene leaves behind (SENS:161-178): intrinsic.txt, {idx}.txt,
     {idx}.png (16-bit) and -- when the colour payloads were read -- {idx}.jpg.  The JPEG payload is written as
-    stored in the stream instead of being decoded and re-encoded."""
+    stored in the stream instead of being decoded and re-encoded.  ``depth_png="device"`` encodes the depth PNGs on the GPU
+    (``write_depth_pngs_device``: the same pixels and filtered scanlines as Pillow's files, another deflate stream), from
+    ``sens.depth_device`` when the frames were inflated there, else from ``sens.depth``."""
+    if depth_png not in ("pillow", "device"):
+        raise ValueError("depth_png: 'pillow' or 'device'")
     os.makedirs(output_path, exist_ok=True)
     with open(os.path.join(output_path, "intrinsic.txt"), "w") as f:
         f.write(matrix_text(sens.intrinsic_color))
     pos = sens.export_position if sens.export_position is not None else list(range(len(sens.frame_index)))
+    stems = []
     for k, e in enumerate(pos):
         stem = os.path.join(output_path, SensScene.index_to_str(e))
+        stems.append(stem)
         with open(stem + ".txt", "w") as f:
             f.write(matrix_text(sens.camera_to_world[k]))
         if sens.color_jpeg is not None:
             with open(stem + ".jpg", "wb") as f:
                 f.write(sens.color_jpeg[k])
-        if with_depth_png:
+        if with_depth_png and depth_png == "pillow":
             from PIL import Image
             Image.fromarray(sens.depth[k]).save(stem + ".png")
+    if with_depth_png and depth_png == "device" and stems:
+        depth = sens.depth_device if sens.depth_device is not None else sens.depth
+        write_depth_pngs_device(depth, [s + ".png" for s in stems])
+
+
+def write_depth_pngs_device(depth, paths: Sequence[str], batch: int = 256, device="cuda"):
+    """Write depth[k] ([F, DH, DW]: a uint16 NumPy array, or the int16 device tensor of ``read_sens(depth_to_device=...)``)
+    as the 16-bit PNG file paths[k], encoded on the GPU (``engine.png_encode_device``) ``batch`` frames per call, so that
+    device and host memory stay bounded whatever F is.  Each file is one job of a host thread pool of
+    ``min(8, hostinfo.effective_cpus())`` threads, so the writes run in parallel, and while the next batch encodes."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import engine, hostinfo
+    paths = list(paths)
+    if len(paths) != len(depth):
+        raise ValueError("one path per frame")
+    on_device = isinstance(depth, torch.Tensor)
+    dev = depth.device if on_device else torch.device(device)
+
+    def write(files, nbytes, k, p):
+        with open(p, "wb") as f:
+            f.write(files[k, :nbytes[k]].tobytes())
+
+    batches = []                                            # the write jobs of the batches whose files are still on the host
+    with ThreadPoolExecutor(max(1, min(8, hostinfo.effective_cpus()))) as ex:
+        for b0 in range(0, len(paths), batch):
+            b1 = min(len(paths), b0 + batch)
+            if on_device:
+                d = depth[b0:b1].contiguous()
+            else:
+                d = torch.from_numpy(np.ascontiguousarray(depth[b0:b1], dtype=np.uint16).view(np.int16)).to(dev)
+            files, nbytes = engine.png_encode_device(d)
+            nb = nbytes.cpu().numpy()                       # synchronises with the encode
+            host = files[:, :(int(nb.max()) + 3) // 4 * 4].cpu().numpy()
+            batches.append([ex.submit(write, host, nb, k, p) for k, p in enumerate(paths[b0:b1])])   # one job per file
+            if len(batches) > 1:                            # at most two batches of files held on the host
+                for f in batches.pop(0):
+                    f.result()
+        for jobs in batches:
+            for f in jobs:
+                f.result()
 
 
 def write_sens(path: str, intrinsic_color: np.ndarray, camera_to_world: Sequence[np.ndarray], depth: Sequence[np.ndarray],
