@@ -11,7 +11,8 @@ reference's calculate_camera_overlap) with the reference's own overlap-binned sa
 1 %-wide bins 6..35 % (VC_C:485-505), both frame orders (VC_C:280) -- see mspa/workload.py.  `value` is that
 workload ("vc"); the same line carries a fixed three-point sweep (low / vc / high overlap) in `sweep`.
 
-    python bench.py                      # N=1, 1000 pairs/step, corr variant, vc workload
+    python bench.py                      # N=1, 1000 pairs/step, corr variant, vc workload: the headline only
+    python bench.py --full               # + every informational leg, baseline and in-run check (see below)
     python bench.py --gpus 8             # re-executes itself under torch.distributed.run, one rank per GPU
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8     # what the driver does: same thing
     python bench.py --variant dense      # + rgb in, byte mask, xyz f32, rgba out
@@ -22,9 +23,16 @@ the per-pair records of the whole job are collated with one RCCL all_gather insi
 with fewer GPUs than ranks the ranks share the GPUs that exist and collate over gloo (reported in the line:
 "gpus_shared": true -- a launch check, not a scaling measurement).
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with two extra objects:
-  roofline      algorithmic HBM bytes of the K3 launch / its HIP-event-measured duration vs 8 TB/s
-  cpu_baseline  the NumPy restatement of the reference path (oracle/np_oracle.py) timed on this box
+Prints ONE JSON line on rank 0 (see the contract in the task statement).  A plain run sets up, warms up, times the
+steps, dumps (--dump-outputs) and prints; its `roofline` is the K3 launch's algorithmic HBM bytes / its HIP-event-measured
+duration vs 8 TB/s, with the committed PMC traffic of profiles/traffic.json beside it.  --full adds what takes runs of
+its own (the --no-* options leave parts of it out):
+  cold_ms_per_step  the headline step without clock spin-up, an event pair around every step (run before the headline)
+  sweep, variants   the low / high overlap points, the other variant:mode legs, the scene / ScanNet-shape / pipeline /
+                    from-disk / device-decode legs, the measured HBM ceilings
+  cpu_baseline      the NumPy restatement of the reference path (oracle/np_oracle.py) timed on this box, and
+  parity_in_run     its (n_valid, n_vis) against the timed launch's counts on the same frames (a mismatch fails the run)
+  roofline.traffic  measured in two rocprofv3 --pmc child runs of the headline step
 """
 from __future__ import annotations
 
@@ -122,6 +130,10 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
                          "(float32 / float64, at most 64 MB in all: per-pixel outputs at a fixed, seeded sample of positions)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the cold-clock reading, the overlap sweep, the variant and "
+                         "scene legs, the CPU baseline with its in-run parity check and the live PMC traffic (the --no-* "
+                         "options select among them); without it the run is set-up, warm-up, timed steps, dump and the line")
     return ap.parse_args()
 
 
@@ -143,21 +155,6 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     raise SystemExit(subprocess.call(cmd, env=env))
-
-
-def _scene_cache_dir():
-    """A directory only this user can write (0700, ownership checked): the cached scene is plain arrays (np.load with
-    allow_pickle=False), and nobody else can plant a file under a name the bench will open."""
-    import tempfile
-    d = os.path.join(tempfile.gettempdir(), f"mspa_bench_{os.getuid()}")
-    try:
-        os.makedirs(d, mode=0o700, exist_ok=True)
-        st = os.stat(d)
-        if st.st_uid != os.getuid() or (st.st_mode & 0o077):
-            return None
-    except OSError:
-        return None
-    return d
 
 
 DUMP_BUDGET = 64 << 20         # bytes --dump-outputs may write in all
@@ -225,36 +222,50 @@ def dump_outputs(path, arrays):
         np.save(os.path.join(path, f"{k}.npy"), v)
 
 
+def _render_depth_columns(E_aligned, Kd, depth_hw, boxes):
+    """mspa.synth.render_depth, bit for bit, in a quarter of its time: the same ray directions (the same matrix product), each
+    slab test written per axis over contiguous columns instead of as min / max reductions along a 3-wide row axis.  Every
+    operation is the same IEEE one on the same operands (min / max of three taken in the reductions' order), so the depth
+    comes out identical (tests/test_bench_scene_cpu.py)."""
+    from mspa.synth import ROOM
+    DH, DW = depth_hw
+    xs, ys = np.meshgrid(np.arange(DW, dtype=np.float64), np.arange(DH, dtype=np.float64))
+    dirs_cam = np.stack([(xs - Kd[0, 2]) / Kd[0, 0], (ys - Kd[1, 2]) / Kd[1, 1], np.ones_like(xs)], -1)
+    R, o = E_aligned[:3, :3], E_aligned[:3, 3]
+    d = np.ascontiguousarray((dirs_cam.reshape(-1, 3) @ R.T).T)             # [3, DH*DW]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / d
+        lo, hi = 0.0 - o, ROOM - o
+        t_best = np.maximum(lo[0] * inv[0], hi[0] * inv[0])
+        for k in (1, 2):
+            t_best = np.minimum(t_best, np.maximum(lo[k] * inv[k], hi[k] * inv[k]))
+        for b in boxes:
+            lo, hi = b[0] - o, b[1] - o
+            tn = tf = None
+            for k in range(3):
+                ta, tb = lo[k] * inv[k], hi[k] * inv[k]
+                near, far = np.minimum(ta, tb), np.maximum(ta, tb)
+                tn = near if tn is None else np.maximum(tn, near)
+                tf = far if tf is None else np.minimum(tf, far)
+            hit = (tn <= tf) & (tn > 1e-6)
+            t_best = np.where(hit & (tn < t_best), tn, t_best)
+    return t_best.reshape(DH, DW)
+
+
 def make_base_scene(args, rank):
     """Host-only part of the inputs: the seeded synthetic scene (SURVEY.md 8d recipe; the camera follows a hand-held
-    sweep so that one scene populates every overlap bin the reference samples from).  Rendering 64 frames on the host
-    takes ~20 s, so the finished scene's arrays are cached (profiling runs the same command six times)."""
+    sweep so that one scene populates every overlap bin the reference samples from).  mspa.synth.make_scene renders it, its
+    ray cast swapped for the equivalent _render_depth_columns for the duration of the call: ~5 s for the 64 frames instead of
+    ~20.  Every run renders its own scene: nothing is cached between runs."""
     from mspa import synth
-    d = _scene_cache_dir()
-    key = f"scene_{1000 + rank}_{args.scene_points}_{args.base_frames}_{args.walk_step}_{args.target_step}.npz"
-    path = os.path.join(d, key) if d else None
-    if path and os.path.exists(path):
-        try:
-            z = np.load(path, allow_pickle=False)
-            ids = [str(i) for i in z["ids"]]
-            return synth.SynthScene(scene_id=str(z["scene_id"]), K=z["K"], A=z["A"], E={i: z["E"][k] for k, i in enumerate(ids)},
-                                    points=z["points"], depth={i: z["depth"][k] for k, i in enumerate(ids)}, color={},
-                                    color_hw=(H, W), depth_hw=(H, W), boxes=z["boxes"])
-        except Exception:
-            pass
-    sc = synth.make_scene(1000 + rank, n_points=args.scene_points, n_frames=args.base_frames, color_hw=(H, W),
-                          depth_hw=(H, W), invalid_pose_frac=0.0, with_color=False, trajectory="sweep",
-                          walk_step=args.walk_step, target_step=args.target_step)
-    if path:
-        try:
-            ids = sc.image_ids
-            tmp = path + f".{os.getpid()}.npz"
-            np.savez(tmp, scene_id=np.str_(sc.scene_id), ids=np.array(ids), K=sc.K, A=sc.A, E=np.stack([sc.E[i] for i in ids]),
-                     points=sc.points, depth=np.stack([sc.depth[i] for i in ids]), boxes=sc.boxes)
-            os.replace(tmp, path)
-        except Exception:
-            pass
-    return sc
+    render = synth.render_depth
+    synth.render_depth = _render_depth_columns
+    try:
+        return synth.make_scene(1000 + rank, n_points=args.scene_points, n_frames=args.base_frames, color_hw=(H, W),
+                                depth_hw=(H, W), invalid_pose_frac=0.0, with_color=False, trajectory="sweep",
+                                walk_step=args.walk_step, target_step=args.target_step)
+    finally:
+        synth.render_depth = render
 
 
 def build_inputs(args, rank, device, sc):
@@ -1179,7 +1190,7 @@ def main():
     # spin-up (the part comes straight from the host-side input preparation), an event pair around every step, W warm-up steps.
     # Rank 0 of a single-GPU run only; it runs BEFORE the headline (afterwards the clock would be warm).
     cold_ms = None
-    if world == 1 and not os.environ.get("MSPA_BENCH_FORCE_DIST"):
+    if args.full and world == 1 and not os.environ.get("MSPA_BENCH_FORCE_DIST"):
         _, cold_ms, _cold_out = time_variant(args.variant, args.mode, depth, mats, rgb, pairs, args.steps, args.warmup, None, stream,
                                              spinup_ms=0.0, per_step_events=True)
         del _cold_out
@@ -1272,7 +1283,7 @@ def main():
 
     extra, sweep = {}, {}
     head_vis = vis_fraction(out) if rank == 0 else None
-    if rank == 0 and world == 1:      # informational single-GPU legs; with N > 1 every rank leaves together after the timed job
+    if args.full and rank == 0 and world == 1:   # informational single-GPU legs; with N > 1 every rank leaves together after the timed job
         short = max(3, args.steps // 4)
         if not args.no_sweep:         # the same variant on the other two points of the overlap sweep
             for kind in WORKLOADS:
@@ -1337,7 +1348,7 @@ def main():
                 k1["traffic_source"] = t1["source"]
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # after the GPU legs (the pair list comes from K1 + K2); at N > 1 only the 1-process leg, with half the budget,
         # while the other ranks wait at the final barrier
         cpu = cpu_baseline(sc, base_pairs, args.cpu_seconds if world == 1 else args.cpu_seconds / 2, with_pool=(world == 1),
@@ -1352,7 +1363,7 @@ def main():
         live = None
         under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER")) for k in os.environ) or \
             "rocprof" in os.environ.get("LD_PRELOAD", "")            # never a profiler inside a profiler
-        if world == 1 and not args.no_live_traffic and not under_profiler and not os.environ.get("MSPA_BENCH_FORCE_DIST"):
+        if args.full and world == 1 and not args.no_live_traffic and not under_profiler and not os.environ.get("MSPA_BENCH_FORCE_DIST"):
             live = live_traffic(args)
         if live:
             traffic = live[0]
@@ -1360,14 +1371,14 @@ def main():
                               f"FETCH_SIZE / WRITE_SIZE (separate passes; mean of {live[2]} dispatches of {live[1]}; FETCH_SIZE x 2 KiB + "
                               "WRITE_SIZE x 1 KiB)")
         info = dev_info
-        ceilings = measured_hbm_ceilings(device) if (world == 1 and not args.no_scene_legs) else None
+        ceilings = measured_hbm_ceilings(device) if (args.full and world == 1 and not args.no_scene_legs) else None
         tight = args.mode != "exact"
         line = {
             "metric": "frame-pairs/sec MultiSPA geometry pipe (640x480 RGB-D)",
             "value": round(value, 1), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(wall / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "cold_ms_per_step": None if cold_ms is None else round(cold_ms, 4),
             "cold_method": "no clock spin-up, HIP event pair around every step, mean of the K per-step times after W warm-up "
                            "steps (rounds 1-2's method); `ms_per_step` / `roofline.kernel_ms` are the steady-state reading",

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--steps", "2", "--warmup", "1", "--pairs", "96", "--frames", "64", "--base-frames", "16", "--scene-points", "8192",
          "--no-scene-legs", "--also", "none", "--cpu-seconds", "1", "--no-live-traffic"]
+FULL = SMALL + ["--full"]          # the legs, the CPU baseline and the in-run parity check the lines below assert on
 
 
 def free_port():
@@ -45,19 +46,19 @@ def check_line(j, n):
 
 
 def test_bench_n1_plain_command():
-    j = run([sys.executable, "bench.py", "--gpus", "1"] + SMALL)
+    j = run([sys.executable, "bench.py", "--gpus", "1"] + FULL)
     check_line(j, 1)
     assert set(j["sweep"]) == {"low", "vc", "high"} and j["sweep"]["vc"]["headline"]
     assert j["sweep"]["low"]["visible_fraction"] < j["sweep"]["vc"]["visible_fraction"] < j["sweep"]["high"]["visible_fraction"]
 
 
 def test_bench_n2_self_launch_and_torchrun():
-    j = run([sys.executable, "bench.py", "--gpus", "2"] + SMALL)
+    j = run([sys.executable, "bench.py", "--gpus", "2"] + FULL)
     check_line(j, 2)
     import torch
     assert j["gpus_shared"] == (torch.cuda.device_count() < 2)
     j = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-             "--master-port", str(free_port()), "bench.py", "--gpus", "2"] + SMALL)
+             "--master-port", str(free_port()), "bench.py", "--gpus", "2"] + FULL)
     check_line(j, 2)
 
 
@@ -65,7 +66,7 @@ def test_bench_n1_with_the_rccl_collation_forced():
     """One rank, MSPA_BENCH_FORCE_DIST=1: the communicator is RCCL (backend "nccl"), the job's record table is collated by
     all_gather_into_tensor on DEVICE tensors inside the timed region and the ranks meet at barrier(device_ids=...) -- the
     branch every N > 1 run on real multi-GPU hardware takes, here with a world of one."""
-    j = run([sys.executable, "bench.py", "--gpus", "1"] + SMALL, MSPA_BENCH_FORCE_DIST="1")
+    j = run([sys.executable, "bench.py", "--gpus", "1"] + FULL, MSPA_BENCH_FORCE_DIST="1")
     check_line(j, 1)
     assert j["config"]["collation_backend"] == "nccl" and "RCCL" in j["config"]["collation"]
 
@@ -76,12 +77,27 @@ def test_bench_measures_the_headline_traffic_in_the_run():
     import shutil
     if not (shutil.which("rocprofv3") or os.path.exists("/opt/rocm/bin/rocprofv3")):
         pytest.skip("no rocprofv3 on this box")
-    small = [a for a in SMALL if a != "--no-live-traffic"] + ["--no-sweep", "--no-cpu-baseline"]
+    small = [a for a in FULL if a != "--no-live-traffic"] + ["--no-sweep", "--no-cpu-baseline"]
     j = run([sys.executable, "bench.py", "--gpus", "1"] + small)
     r = j["roofline"]
     assert r["traffic"] is not None and r["traffic_source"].startswith("measured in this run")
     # 96 pairs of 640x480: the two depth frames in, bitset + index table out -- the measured bytes sit near the formula's
     assert 0.5 < r["traffic"] / r["bytes_per_launch"] < 1.5 and r["traffic_frac"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line carries the headline and nothing that takes runs of its own: no cold reading, no sweep or
+    variant legs, no CPU baseline, no live traffic -- the same metric, value, unit and ms_per_step as ever."""
+    j = run([sys.executable, "bench.py", "--gpus", "1"] + SMALL[:-1])           # live traffic not even switched off
+    assert j["full"] is False and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["metric"] == "frame-pairs/sec MultiSPA geometry pipe (640x480 RGB-D)" and j["unit"] == "frame-pairs/s"
+    assert j["higher_is_better"] is True and j["dtype"] == "f64" and j["value"] > 0 and j["ms_per_step"] > 0
+    assert abs(j["value"] - 96 / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-2
+    assert j["cold_ms_per_step"] is None and j["sweep"] == {} and j["variants"] == {}
+    assert j["cpu_baseline"] is None and j["parity_in_run"] is None and j["cpu_baseline_pool"] is None
+    r = j["roofline"]
+    assert r["kernel_ms"] > 0 and r["measured_ceilings_GBs"] is None and r["traffic"] is None   # 96 pairs: no committed profile
+    assert 0 < j["config"]["visible_fraction"] < 1
 
 
 RCCL_WORLD1 = r"""

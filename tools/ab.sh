@@ -3,7 +3,7 @@
 # bench's three-point sweep (+ the variant legs named in $1).  Prints kernel ms per leg.
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT
-ARGS="--steps 30 --warmup 3 --no-cpu-baseline --no-scene-legs --also ${1:-minimal:fast,dense:fast}"
+ARGS="--full --steps 30 --warmup 3 --no-cpu-baseline --no-scene-legs --also ${1:-minimal:fast,dense:fast}"
 for i in 1 2; do
   for lib in tools/ab/libmspa_*.so multi-spatialmllm_amd/libmspa.so; do
     MSPA_LIB=$ROOT/$lib python bench.py $ARGS 2>/dev/null | tail -1 | python -c "

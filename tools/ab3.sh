@@ -4,7 +4,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT
 LEGS=${1:-compact:fast}; shift
-ARGS="--steps 12 --warmup 3 --no-cpu-baseline --no-scene-legs --no-sweep --variant minimal --also $LEGS $*"
+ARGS="--full --steps 12 --warmup 3 --no-cpu-baseline --no-scene-legs --no-sweep --variant minimal --also $LEGS $*"
 for i in 1 2; do
   for lib in tools/ab/libmspa_*.so multi-spatialmllm_amd/libmspa.so; do
     MSPA_LIB=$ROOT/$lib python bench.py $ARGS 2>/dev/null | tail -1 | python -c "

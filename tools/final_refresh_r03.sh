@@ -8,9 +8,9 @@ O=$ROOT/gpurun_out/final_$T
 mkdir -p $O
 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $O/pytest_gpu.txt
 python __graft_entry__.py smoke 2>&1 | tail -1 > $O/smoke.txt
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
-python bench.py --gpus 2 --steps 10 --no-scene-legs > $O/bench_n2.json 2> $O/bench_n2.err
-MSPA_BENCH_FORCE_DIST=1 python bench.py --no-scene-legs --also none --no-sweep > $O/bench_n1_rccl.json 2> $O/bench_n1_rccl.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full --gpus 2 --steps 10 --no-scene-legs > $O/bench_n2.json 2> $O/bench_n2.err
+MSPA_BENCH_FORCE_DIST=1 python bench.py --full --no-scene-legs --also none --no-sweep > $O/bench_n1_rccl.json 2> $O/bench_n1_rccl.err
 bash tools/profile.sh ${T}_corr_vc > /dev/null 2>&1
 bash tools/profile.sh ${T}_corr_low --workload low > /dev/null 2>&1
 bash tools/profile.sh ${T}_corr_high --workload high > /dev/null 2>&1

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/final_r06
 mkdir -p $OUT
 cd $ROOT
 export TMPDIR=/tmp
-( time timeout 600 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err ) 2> $OUT/bench_n1.time
+( time timeout 600 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err ) 2> $OUT/bench_n1.time
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k3_stats -o p -- python $ROOT/bench.py --steps 20 --warmup 5 --no-scene-legs --no-sweep --also none --no-cpu-baseline --no-live-traffic > $OUT/k3_stats.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode_stats -o p -- python $ROOT/tools/device_ingest_bench.py --streams 4096 --reps 3 > $OUT/decode_stats.log 2>&1

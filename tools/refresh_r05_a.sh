@@ -14,7 +14,7 @@ python tools/ab_k1.py > $O/ab_k1.txt 2>&1
 cat $O/ab_k1.txt
 bash tools/pmc_k1_traffic.sh > $O/k1_traffic.md 2> $O/k1_traffic.err
 cat $O/k1_traffic.md
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 python - <<PY
 import json
 j = json.loads(open("$O/bench_n1.json").read().strip().splitlines()[-1])
