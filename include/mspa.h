@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 190            /* 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 200            /* 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -351,6 +351,66 @@ int mspa_format_lists_device(const int64_t *offsets_dev, const int32_t *values_d
                              const int64_t *cost_prefix_dev, const int64_t *nonempty_prefix_dev, const char *tokens_dev,
                              const int32_t *token_offsets_dev, char *out_text_dev, int64_t text_bytes,
                              int32_t *out_text_offsets_dev, mspa_stream_t stream);
+
+/*
+ * K11 -- ScanNet instance data from raw scans (batch_load_scannet_data.py export(), scannet_utils.py extract_bbox), batched:
+ * one launch serves n_scenes scenes whose vertices lie back to back.  DEVICE pointers.  Offset tables shared by the three calls
+ * (int64, n_scenes + 1 entries each): vert_off = prefix sum of the scenes' vertex counts, word_off = prefix sum of
+ * ceil(N_s / 64) (a wave works on 64 consecutive vertices of ONE scene); n_vertices = vert_off[n_scenes], n_waves = word_off[n_scenes].
+ *   mspa_prep_labels   seg [n_vertices] int32 = the scans' segIndices.  Scene s owns rows tab_off[s] .. tab_off[s+1] of seg2inst /
+ *                      seg2label (indexed by segment id; a segment id outside reads as 0 = unannotated) and entries
+ *                      lab_off[s] .. lab_off[s+1] of label_value (entry 0 of every scene: 0).  Writes
+ *                      instance_ids[v] = seg2inst[seg[v]], label_index[v] = seg2label[seg[v]], label_ids[v] = label_value[label_index[v]].
+ *   mspa_prep_align    vertices [n_vertices, 6] float32 (x y z r g b) -> out_aligned [n_vertices, 6] float64; x y z through scene s's
+ *                      row-major 4x4 axis_align[s] in the order m0*x, fma(m1,y,.), fma(m2,z,.), fma(m3,1.0,.) -- the bits of
+ *                      np.dot(pts, A.T) (BL:66-69) for N >= 2; a scene of one vertex takes the order of the
+ *                      vector path np.dot takes then, (m0*x + m2*z) + (m1*y + m3) with every product rounded; colours widened.
+ *   mspa_prep_objects  scene s owns object slots obj_off[s] .. obj_off[s+1] (slot obj_off[s] + k - 1 <-> instance id k); n_objects =
+ *                      obj_off[n_scenes].  Per slot: out_count = vertices with that id, out_lo / out_hi_unaligned [n_objects, 3] = min /
+ *                      max of the float32 x y z (as float64: exact), out_lo / out_hi_aligned the same over out_aligned (+inf / -inf
+ *                      for an object without vertices); out_bits [n_objects, n_words] = the object's membership bitset over its
+ *                      scene's vertices (n_words >= the longest scene's word count; mspa_bits_popcount -> prefix sum ->
+ *                      mspa_bits_expand turn the rows into vertex lists in vertex order: the stable split).  Per scene:
+ *                      out_zero_count = vertices with id 0, out_unique = len(np.unique(instance_ids)).
+ */
+int mspa_prep_labels(const int32_t *seg, const int64_t *vert_off, const int64_t *word_off, int64_t n_scenes, int64_t n_vertices,
+                     int64_t n_waves, const int64_t *tab_off, const int32_t *seg2inst, const int32_t *seg2label,
+                     const int64_t *lab_off, const uint32_t *label_value, uint32_t *out_instance_ids, uint32_t *out_label_ids,
+                     int32_t *out_label_index, mspa_stream_t stream);
+int mspa_prep_align(const float *vertices, const int64_t *vert_off, const int64_t *word_off, int64_t n_scenes, int64_t n_vertices,
+                    int64_t n_waves, const double *axis_align, double *out_aligned, mspa_stream_t stream);
+int mspa_prep_objects(const uint32_t *instance_ids, const float *vertices, const double *aligned, const int64_t *vert_off,
+                      const int64_t *word_off, int64_t n_scenes, int64_t n_vertices, int64_t n_waves, const int64_t *obj_off,
+                      int64_t n_objects, uint64_t *out_bits, int64_t n_words, int32_t *out_count, double *out_lo_unaligned,
+                      double *out_hi_unaligned, double *out_lo_aligned, double *out_hi_aligned, int32_t *out_zero_count,
+                      int32_t *out_unique, mspa_stream_t stream);
+
+/*
+ * JSON integer lists -> int32 (the "segIndices" array of *.segs.json; the inverse of the formatters above).  Array a is the text
+ * BETWEEN its brackets, bytes text_offsets[a] .. text_offsets[a+1] of one concatenated buffer.
+ *   mspa_parse_int_list_host          HOST pointers, up to n_threads pool threads, one array each.  JSON's grammar: white space,
+ *                                     -?(0|[1-9][0-9]*), commas.  Array a's values go to out_values[out_offsets[a] ..], at most
+ *                                     out_offsets[a+1] - out_offsets[a] of them; out_counts[a] = how many.  status[a]: 0 parsed;
+ *                                     1 not such a list; 2 a value outside int32; 16 more values than room.
+ *   mspa_parse_int_list_flags_device  DEVICE pointers; one lane per byte: out_flags[i] = 1 where a number ends, 1 << 32 for a
+ *                                     comma; clears status and raises bit 1 of status[a] for a byte that is no digit, comma
+ *                                     or JSON white space.
+ *   mspa_parse_int_list_device        flags_prefix: exclusive prefix sum of out_flags, n_bytes + 1 entries (the caller's plumbing).
+ *                                     The lane at a number's last digit assembles it from at most 10 digits and stores it at
+ *                                     out_values[numbers in front of it] (arrays back to back; nothing is stored at or beyond
+ *                                     out_capacity); out_offsets [n_arrays + 1] = where each array's values start.  status bits:
+ *                                     2 more than 10 digits or above INT32_MAX, 4 a leading zero, 8 commas and numbers do not
+ *                                     alternate, 16 the count differs from expected_counts[a] (NULL or < 0: not checked).
+ *                                     Non-negative lists only: a '-' declines.  A declined array (status != 0) is the host
+ *                                     parser's; its neighbours' values are intact.
+ */
+int mspa_parse_int_list_host(const char *text_host, const int64_t *text_offsets_host, int64_t n_arrays, int32_t *out_values_host,
+                             const int64_t *out_offsets_host, int64_t *out_counts_host, int32_t *status_host, int32_t n_threads);
+int mspa_parse_int_list_flags_device(const char *text_dev, const int64_t *text_offsets_dev, int64_t n_arrays, int64_t n_bytes,
+                                     int64_t *out_flags_dev, int32_t *status_dev, mspa_stream_t stream);
+int mspa_parse_int_list_device(const char *text_dev, const int64_t *text_offsets_dev, int64_t n_arrays, int64_t n_bytes,
+                               const int64_t *flags_prefix_dev, const int64_t *expected_counts_dev, int32_t *out_values_dev,
+                               int64_t out_capacity, int64_t *out_offsets_dev, int32_t *status_dev, mspa_stream_t stream);
 
 /*
  * Host-side staging of a scene's depth frames (the loop that fills the frame stack in the reference: CFR / MVI read one

@@ -297,3 +297,64 @@ extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_
     HostPool::get().parallel((int)nt, work);
     return MSPA_OK;
 }
+
+
+// JSON integer lists (the "segIndices" array of ScanNet's *.segs.json, 150 k numbers per scan; json.load + a Python loop over every
+// element in the reference, SU:38-50).  Array a is the text BETWEEN its brackets; it is parsed to int32 by one pool thread.
+// The grammar is JSON's: white space, -?(0|[1-9][0-9]*), commas.  Anything else -- a fraction, an exponent, a value outside
+// int32, a stray byte -- declines the array (status != 0) and the caller falls back to json.loads, which then decides.
+static int parse_int_list(const unsigned char *p, const unsigned char *end, int32_t *out, int64_t capacity, int64_t &count) {
+    auto ws = [&]() { while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) ++p; };
+    count = 0;
+    ws();
+    if (p == end) return 0;
+    for (;;) {
+        const bool neg = p < end && *p == '-';
+        if (neg) ++p;
+        if (p == end || *p < '0' || *p > '9') return 1;
+        const unsigned char *first = p;
+        int64_t v = 0;
+        while (p < end && *p >= '0' && *p <= '9') {
+            if (p - first >= 10) return 2;
+            v = v * 10 + (*p - '0');
+            ++p;
+        }
+        if (*first == '0' && p - first > 1) return 1;
+        if (neg) v = -v;
+        if (v > 2147483647LL || v < -2147483648LL) return 2;
+        if (count >= capacity) return 16;
+        out[count++] = (int32_t)v;
+        ws();
+        if (p == end) return 0;
+        if (*p != ',') return 1;
+        ++p;
+        ws();
+    }
+}
+
+extern "C" int mspa_parse_int_list_host(const char *text_host, const int64_t *text_offsets_host, int64_t n_arrays, int32_t *out_values_host,
+                                        const int64_t *out_offsets_host, int64_t *out_counts_host, int32_t *status_host, int32_t n_threads) {
+    if (n_arrays < 0) return fail(MSPA_EINVAL, "mspa_parse_int_list_host: negative size");
+    if (n_arrays == 0) return MSPA_OK;
+    if (!text_offsets_host || !out_offsets_host || !out_counts_host || !status_host)
+        return fail(MSPA_EINVAL, "mspa_parse_int_list_host: null pointer");
+    for (int64_t a = 0; a < n_arrays; ++a)
+        if (text_offsets_host[a] < 0 || text_offsets_host[a + 1] < text_offsets_host[a] || out_offsets_host[a] < 0 ||
+            out_offsets_host[a + 1] < out_offsets_host[a])
+            return fail(MSPA_EINVAL, "mspa_parse_int_list_host: offsets must ascend from a non-negative start");
+    if ((text_offsets_host[n_arrays] > 0 && !text_host) || (out_offsets_host[n_arrays] > 0 && !out_values_host))
+        return fail(MSPA_EINVAL, "mspa_parse_int_list_host: null pointer");
+    const int64_t nt = n_threads < 1 ? 1 : (n_threads > n_arrays ? n_arrays : (int64_t)n_threads);
+    std::atomic<int64_t> next{0};
+    auto work = [&]() {
+        for (;;) {
+            const int64_t a = next.fetch_add(1);
+            if (a >= n_arrays) return;
+            const unsigned char *t = (const unsigned char *)text_host;
+            status_host[a] = parse_int_list(t + text_offsets_host[a], t + text_offsets_host[a + 1], out_values_host + out_offsets_host[a],
+                                            out_offsets_host[a + 1] - out_offsets_host[a], out_counts_host[a]);
+        }
+    };
+    HostPool::get().parallel((int)nt, work);
+    return MSPA_OK;
+}

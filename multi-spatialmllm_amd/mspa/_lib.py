@@ -72,6 +72,15 @@ _SIGNATURES = {
     "mspa_format_list_costs_device": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "mspa_format_lists_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                          c_void_p, c_void_p]),
+    "mspa_prep_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_prep_align": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mspa_prep_objects": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_parse_int_list_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
+    "mspa_parse_int_list_flags_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mspa_parse_int_list_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_void_p]),
     "mspa_gather_blocks_host": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int32]),
     "mspa_inflate_blocks_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32]),
     "mspa_read_depth_png_host": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p]),

@@ -934,3 +934,148 @@ def track_pair_distances(world: torch.Tensor, points: Sequence[int], visible_fra
                                                  int(lens.max()), _ptr(o_off_t), _ptr(out), _stream_ptr()))
     host = out.cpu().numpy()
     return [host[o_off[s]:o_off[s + 1]] for s in range(S)]
+
+
+# ---- K11: ScanNet instance data from raw scans (csrc/scene_prep.hip) -----------------------------------------------------------------
+
+def _ragged_offsets(counts: Sequence[int]) -> np.ndarray:
+    off = np.zeros(len(counts) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(counts, dtype=np.int64), out=off[1:])
+    return off
+
+
+def prep_spans(n_vertices: Sequence[int], device) -> dict:
+    """The two offset tables every K11 launch shares: ``vert_off`` (prefix sum of the scenes' vertex counts) and ``word_off`` (prefix
+    sum of ceil(N / 64): a wave works on 64 consecutive vertices of one scene)."""
+    n = np.asarray(n_vertices, dtype=np.int64)
+    _require(n.ndim == 1 and (n >= 0).all(), "vertex counts: non-negative, one per scene")
+    vert_off, word_off = _ragged_offsets(n), _ragged_offsets((n + 63) // 64)
+    return {"n_scenes": int(n.size), "n_vertices": int(vert_off[-1]), "n_waves": int(word_off[-1]), "max_words": int(((n + 63) // 64).max()) if n.size else 0,
+            "vert_off_host": vert_off, "vert_off": torch.from_numpy(vert_off).to(device), "word_off": torch.from_numpy(word_off).to(device)}
+
+
+def prep_labels(spans: dict, seg: torch.Tensor, tab_off: torch.Tensor, seg2inst: torch.Tensor, seg2label: torch.Tensor,
+                lab_off: torch.Tensor, label_value: torch.Tensor):
+    """Enqueue ``mspa_prep_labels``: (instance_ids, label_ids) as int32 tensors holding uint32 bits, and the label index (int32)."""
+    _require_gpu()
+    S, N = spans["n_scenes"], spans["n_vertices"]
+    _require(seg.dtype == torch.int32 and seg.shape == (N,), "seg: int32 [n_vertices]")
+    _require(tab_off.dtype == torch.int64 and tab_off.shape == (S + 1,) and lab_off.dtype == torch.int64 and lab_off.shape == (S + 1,),
+             "tab_off / lab_off: int64 [n_scenes + 1]")
+    _require(seg2inst.dtype == torch.int32 and seg2label.dtype == torch.int32 and seg2inst.shape == seg2label.shape and seg2inst.dim() == 1,
+             "seg2inst / seg2label: int32 tables of one length")
+    _require(label_value.dtype == torch.int32 and label_value.dim() == 1, "label_value: int32 (uint32 bits)")
+    dev = seg.device
+    inst = torch.empty((N,), dtype=torch.int32, device=dev)
+    label = torch.empty((N,), dtype=torch.int32, device=dev)
+    index = torch.empty((N,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().mspa_prep_labels(_ptr(seg), _ptr(spans["vert_off"]), _ptr(spans["word_off"]), S, N, spans["n_waves"], _ptr(tab_off),
+                                            _ptr(seg2inst), _ptr(seg2label), _ptr(lab_off), _ptr(label_value), _ptr(inst), _ptr(label), _ptr(index),
+                                            _stream_ptr()))
+    return inst, label, index
+
+
+def prep_align(spans: dict, vertices: torch.Tensor, axis_align: torch.Tensor) -> torch.Tensor:
+    """Enqueue ``mspa_prep_align``: [N, 6] float32 -> [N, 6] float64, xyz through each scene's 4x4 (``np.dot(pts, A.T)`` bits)."""
+    _require_gpu()
+    S, N = spans["n_scenes"], spans["n_vertices"]
+    _require(vertices.dtype == torch.float32 and vertices.shape == (N, 6), "vertices: float32 [n_vertices, 6]")
+    _require(axis_align.dtype == torch.float64 and axis_align.shape == (S, 4, 4), "axis_align: float64 [n_scenes, 4, 4]")
+    out = torch.empty((N, 6), dtype=torch.float64, device=vertices.device)
+    _lib.check(_lib.load().mspa_prep_align(_ptr(vertices), _ptr(spans["vert_off"]), _ptr(spans["word_off"]), S, N, spans["n_waves"], _ptr(axis_align),
+                                           _ptr(out), _stream_ptr()))
+    return out
+
+
+def prep_objects(spans: dict, instance_ids: torch.Tensor, vertices: torch.Tensor, aligned: torch.Tensor, n_objects: Sequence[int]) -> dict:
+    """Enqueue ``mspa_prep_objects`` and K9 on its membership rows.  ``n_objects[s]``: object slots of scene s (slot k - 1 <-> id k).
+    Returns device tensors: count [M], lo / hi_unaligned and lo / hi_aligned [M, 3] float64, unique [S], and the stable split as CSR
+    (``offsets`` [M + 1] int64, ``indices`` int32: scene-local vertex numbers, ascending within an object)."""
+    _require_gpu()
+    S, N = spans["n_scenes"], spans["n_vertices"]
+    _require(len(n_objects) == S, "n_objects: one per scene")
+    _require(instance_ids.dtype == torch.int32 and instance_ids.shape == (N,), "instance_ids: int32 [n_vertices]")
+    _require(vertices.dtype == torch.float32 and vertices.shape == (N, 6) and aligned.dtype == torch.float64 and aligned.shape == (N, 6),
+             "vertices float32 / aligned float64 [n_vertices, 6]")
+    dev = instance_ids.device
+    obj_off_host = _ragged_offsets(n_objects)
+    M, n_words = int(obj_off_host[-1]), spans["max_words"]
+    obj_off = torch.from_numpy(obj_off_host).to(dev)
+    bits = torch.empty((M, n_words), dtype=torch.int64, device=dev)
+    count = torch.empty((M,), dtype=torch.int32, device=dev)
+    ext = [torch.empty((M, 3), dtype=torch.float64, device=dev) for _ in range(4)]
+    zero_count = torch.empty((S,), dtype=torch.int32, device=dev)
+    unique = torch.empty((S,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().mspa_prep_objects(_ptr(instance_ids), _ptr(vertices), _ptr(aligned), _ptr(spans["vert_off"]), _ptr(spans["word_off"]), S, N,
+                                             spans["n_waves"], _ptr(obj_off), M, _ptr(bits), n_words, _ptr(count), _ptr(ext[0]), _ptr(ext[1]),
+                                             _ptr(ext[2]), _ptr(ext[3]), _ptr(zero_count), _ptr(unique), _stream_ptr()))
+    offsets, indices = bitset_csr(bits)
+    return {"count": count, "lo_unaligned": ext[0], "hi_unaligned": ext[1], "lo_aligned": ext[2], "hi_aligned": ext[3], "unique": unique,
+            "zero_count": zero_count, "offsets": offsets, "indices": indices, "obj_off_host": obj_off_host}
+
+
+def _int_list_buffers(texts: Sequence[bytes]):
+    off = _ragged_offsets([len(t) for t in texts])
+    return np.frombuffer(bytearray(b"".join(texts) or b"\0"), dtype=np.uint8), off
+
+
+def parse_int_lists_host(texts: Sequence[bytes], capacities: Optional[Sequence[int]] = None, n_threads: Optional[int] = None):
+    """``mspa_parse_int_list_host`` over the pool threads: the text between the brackets of JSON integer lists -> (list of int32
+    arrays, status [n]).  A declined array (status != 0) comes back as None: ``json.loads`` is the caller's fallback."""
+    from . import hostinfo
+    n = len(texts)
+    if n == 0:
+        return [], np.zeros(0, dtype=np.int32)
+    buf, off = _int_list_buffers(texts)
+    cap = _ragged_offsets([(len(t) + 1) // 2 for t in texts] if capacities is None else capacities)
+    out = np.empty(max(int(cap[-1]), 1), dtype=np.int32)
+    counts, status = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.load().mspa_parse_int_list_host(buf.ctypes.data, off.ctypes.data, n, out.ctypes.data, cap.ctypes.data, counts.ctypes.data,
+                                                    status.ctypes.data, int(n_threads or hostinfo.effective_cpus())))
+    return [out[cap[a]:cap[a] + counts[a]] if status[a] == 0 else None for a in range(n)], status
+
+
+def parse_int_lists_device(texts: Sequence[bytes], device, expected_counts: Optional[Sequence[int]] = None):
+    """The same lists parsed on the device (one lane per byte; ``mspa_parse_int_list_flags_device`` -> prefix sum ->
+    ``mspa_parse_int_list_device``).  Returns (values int32 [total] on the device, offsets int64 [n + 1] and status int32 [n] on the
+    host).  Arrays with status != 0 were declined -- non-negative plain lists only -- and belong to the host parser."""
+    _require_gpu()
+    lib = _lib.load()
+    n = len(texts)
+    if n == 0:
+        return torch.zeros((0,), dtype=torch.int32, device=device), np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    buf, off = _int_list_buffers(texts)
+    n_bytes = int(off[-1])
+    _require(n_bytes <= 0x7fffffff, "parse_int_lists_device: more than 2 GiB of text")
+    text = torch.from_numpy(buf).to(device)
+    text_off = torch.from_numpy(off).to(device)
+    status = torch.empty((max(n, 1),), dtype=torch.int32, device=device)
+    flags = torch.empty((max(n_bytes, 1),), dtype=torch.int64, device=device)
+    _lib.check(lib.mspa_parse_int_list_flags_device(_ptr(text), _ptr(text_off), n, n_bytes, _ptr(flags), _ptr(status), _stream_ptr()))
+    T = torch.zeros((n_bytes + 1,), dtype=torch.int64, device=device)                # torch as plumbing: one prefix sum
+    if n_bytes:
+        torch.cumsum(flags[:n_bytes], dim=0, out=T[1:])
+    total = int(T[-1].item()) & 0xffffffff                                             # one small read-back: the size to allocate
+    values = torch.empty((max(total, 1),), dtype=torch.int32, device=device)
+    expected = None if expected_counts is None else torch.from_numpy(np.asarray(expected_counts, dtype=np.int64)).to(device)
+    out_off = torch.empty((n + 1,), dtype=torch.int64, device=device)
+    _lib.check(lib.mspa_parse_int_list_device(_ptr(text), _ptr(text_off), n, n_bytes, _ptr(T), _ptr(expected), _ptr(values), total, _ptr(out_off),
+                                              _ptr(status), _stream_ptr()))
+    return values[:total], out_off.cpu().numpy(), status[:n].cpu().numpy()
+
+
+def parse_int_lists(texts: Sequence[bytes], device=None, expected_counts: Optional[Sequence[int]] = None, n_threads: Optional[int] = None):
+    """JSON integer lists -> list of int32 arrays (None where neither parser takes the text: not a plain list of int32).  ``device``
+    None: the native host threads.  Else the device parses and the host threads take what it declines, so the result is the
+    host parser's for every input."""
+    if device is None:
+        return parse_int_lists_host(texts, expected_counts, n_threads)[0]
+    values, off, status = parse_int_lists_device(texts, device, expected_counts)
+    host = values.cpu().numpy()
+    out = [host[off[a]:off[a + 1]] if status[a] == 0 else None for a in range(len(texts))]
+    declined = [a for a in range(len(texts)) if status[a] != 0]
+    if declined:
+        redo = parse_int_lists_host([texts[a] for a in declined], None, n_threads)[0]
+        for a, r in zip(declined, redo):
+            out[a] = r
+    return out

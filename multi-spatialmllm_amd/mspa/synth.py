@@ -340,3 +340,95 @@ def write_scannet_layout(scenes: Sequence["SynthScene"], root: str, info_name: s
     with open(info_path, "wb") as f:
         pickle.dump(infos, f)
     return {"info_path": info_path, "posed_images_root": posed, "instance_data_root": inst}
+
+
+# ---- raw scans: the four files per scan that batch_load_scannet_data.py reads, plus a label TSV -----------------------------------
+
+RAW_SCAN_LABELS = (("chair", 5), ("table", 7), ("office chair", 5), ("door", 8), ("wall", 1), ("floor", 2), ("cabinet", 3), ("bed", 4),
+                   ("lamp", 35), ("trash can", 39))
+
+
+def write_raw_scan(root, scan_name, n_vertices, n_objects, seed=0, axis_align="z", n_faces=None, quantum=1.0 / 256, ascii=False):
+    """Write ``<root>/<scan_name>/`` as a ScanNet download has it -- ``_vh_clean_2.ply`` (binary, with an ``alpha`` property and a
+    face element), ``_vh_clean_2.0.010000.segs.json``, ``.aggregation.json``, ``.txt`` -- and ``<root>/labels.tsv``; returns the paths.
+
+    The aggregation has what the reference's replay is sensitive to: repeated labels, an object whose only segment a later object
+    lists too (it ends up without vertices), and segments that no object lists.  ``axis_align``: "z" (rotation about z plus a
+    translation, as ScanNet's), "general" (a full affine matrix), None (no axisAlignment line: a test-set scan), or a 4x4."""
+    import json
+    import os
+    rng = np.random.default_rng(seed)
+    d = os.path.join(root, scan_name)
+    os.makedirs(d, exist_ok=True)
+    paths = {"mesh_file": os.path.join(d, scan_name + "_vh_clean_2.ply"), "agg_file": os.path.join(d, scan_name + ".aggregation.json"),
+             "seg_file": os.path.join(d, scan_name + "_vh_clean_2.0.010000.segs.json"), "meta_file": os.path.join(d, scan_name + ".txt"),
+             "label_map_file": os.path.join(root, "labels.tsv")}
+    # segments: runs of consecutive vertices (as a mesh's vertex order has them) with a few strays; sparse ids
+    n_segments = 3 * n_objects + 5
+    seg_ids = np.sort(rng.choice(4 * n_segments + 7, n_segments, replace=False)).astype(np.int64)
+    cuts = np.sort(rng.integers(0, n_vertices + 1, 4 * n_segments)) if n_vertices else np.zeros(0, np.int64)
+    run_seg = rng.integers(0, n_segments, cuts.size + 1)
+    seg_of_vertex = run_seg[np.searchsorted(cuts, np.arange(n_vertices), side="right")]
+    stray = rng.random(n_vertices) < 0.03
+    seg_of_vertex[stray] = rng.integers(0, n_segments, int(stray.sum()))
+    used = np.unique(seg_of_vertex)                                  # only segments with vertices may be listed (else: KeyError)
+    # vertices: a room of 8 x 6 x 3 m on a grid of `quantum`; colours by segment
+    xyz = (np.floor(rng.random((n_vertices, 3)) * (np.array([8.0, 6.0, 3.0]) / quantum)) * quantum).astype(np.float32)
+    rgba = rng.integers(0, 256, (n_segments, 4), dtype=np.uint8)[seg_of_vertex]        # a segment has one colour
+    rgba[:, 3] = 255
+    n_faces = min(n_vertices // 3, 500) if n_faces is None else n_faces
+    faces = rng.integers(0, max(n_vertices, 1), (n_faces, 3), dtype=np.int32)
+    props = [("x", "float"), ("y", "float"), ("z", "float"), ("red", "uchar"), ("green", "uchar"), ("blue", "uchar"), ("alpha", "uchar")]
+    head = ["ply", "format " + ("ascii" if ascii else "binary_little_endian") + " 1.0", "comment synthetic raw scan", f"element vertex {n_vertices}"]
+    head += [f"property {t} {n}" for n, t in props] + [f"element face {n_faces}", "property list uchar int vertex_indices", "end_header"]
+    with open(paths["mesh_file"], "wb") as f:
+        f.write(("\n".join(head) + "\n").encode())
+        if ascii:
+            for p, c in zip(xyz, rgba):
+                f.write((" ".join(repr(float(v)) for v in p) + " " + " ".join(str(int(v)) for v in c) + "\n").encode())
+            for tri in faces:
+                f.write(("3 " + " ".join(str(int(v)) for v in tri) + "\n").encode())
+        else:
+            v = np.empty(n_vertices, dtype=[("xyz", "<f4", (3,)), ("rgba", "u1", (4,))])
+            v["xyz"], v["rgba"] = xyz, rgba
+            f.write(v.tobytes())
+            fc = np.empty(n_faces, dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+            fc["n"], fc["idx"] = 3, faces
+            f.write(fc.tobytes())
+    with open(paths["seg_file"], "w") as f:
+        json.dump({"params": {"kThresh": "0.0001", "segMinVerts": "20"}, "sceneId": scan_name, "segIndices": seg_ids[seg_of_vertex].tolist()}, f)
+    # objects: every object takes 1-3 of the used segments; the last-but-one's only segment is listed by the last one as well;
+    # about a fifth of the used segments stay unlisted; labels repeat
+    groups = []
+    pool = list(rng.permutation(used)[: max(1, int(used.size * 0.8))])
+    for k in range(n_objects):
+        take = [int(seg_ids[pool.pop()]) for _ in range(int(rng.integers(1, 4))) if pool]
+        label = RAW_SCAN_LABELS[int(rng.integers(0, max(2, min(len(RAW_SCAN_LABELS), n_objects // 2))))][0]
+        groups.append({"id": k, "objectId": k, "segments": take, "label": label})
+    if n_objects >= 3:
+        groups[-2]["segments"] = groups[-2]["segments"][:1]
+        groups[-1]["segments"] = groups[-1]["segments"] + groups[-2]["segments"]
+    groups = [g for g in groups if g["segments"]] if used.size else []
+    with open(paths["agg_file"], "w") as f:
+        json.dump({"sceneId": "scannet." + scan_name, "appId": "Aggregator.v2", "segGroups": groups,
+                   "segmentsFile": "scannet." + os.path.basename(paths["seg_file"])}, f)
+    lines = ["colorHeight = 968", "colorWidth = 1296"]
+    if axis_align is not None:
+        if isinstance(axis_align, str):
+            a = rng.uniform(0, 2 * np.pi)
+            m = np.eye(4)
+            m[:2, :2] = [[np.cos(a), np.sin(a)], [-np.sin(a), np.cos(a)]]
+            m[:3, 3] = rng.uniform(-6, 6, 3)
+            if axis_align == "general":
+                m[:3, :3] += rng.normal(0, 0.1, (3, 3))
+        else:
+            m = np.asarray(axis_align, dtype=np.float64)
+        lines.insert(0, "axisAlignment = " + " ".join(f"{v:.6f}" for v in m.reshape(-1)) + " ")
+    lines.append("sceneType = Office")
+    with open(paths["meta_file"], "w") as f:
+        f.write("\n".join(lines) + "\n")
+    with open(paths["label_map_file"], "w") as f:
+        f.write("id\traw_category\tcategory\tcount\tnyu40id\n")
+        for k, (name, nyu) in enumerate(RAW_SCAN_LABELS, 1):
+            f.write(f"{k}\t{name}\t{name}\t{100 - k}\t{nyu}\n")
+    return paths
