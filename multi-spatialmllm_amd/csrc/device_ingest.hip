@@ -48,13 +48,10 @@ namespace mspa {
 namespace dinf {
 
 constexpr int kLitBits = 11, kDistBits = 8;
-#ifndef MSPA_INFLATE_RING
 // 2 KB, not 4: a wave's LDS is 9 KB instead of 11, so that the compute unit holds the 16 waves its registers allow instead of 14
-// (4 096 streams: 85.8 k frames/s against 75.6 k at 3 584; per wave the two sizes decode at the same speed: tools/ab_ring.sh,
+// (4 096 streams: 85.8 k frames/s against 75.6 k at 3 584; per wave the two sizes decoded at the same speed:
 // profiles/r06_sweep_timeline.md).  Distances of 1 791 .. 3 838 take the HBM path with it; the row above (1 281) stays in the ring.
-#define MSPA_INFLATE_RING 2048
-#endif
-constexpr int kRing = MSPA_INFLATE_RING, kRingMask = kRing - 1;
+constexpr int kRing = 2048, kRingMask = kRing - 1;
 static_assert(kRing >= 2048 && (kRing & kRingMask) == 0, "the ring is a power of two that holds a row-to-row distance of a 640-pixel image");
 constexpr int kRingNear = kRing - 258;          // a match at most this far back never reads a ring slot it is overwriting
 // A far match (beyond kRingNear, at most 64 bytes) reads bytes that left the ring as whole 256-byte lines.  When it is looked at,
@@ -100,7 +97,7 @@ __constant__ uint8_t kPreOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 1
 struct __align__(16) WaveLds {
     uint16_t lit[1 << kLitBits];        // 4 096 B (narrow entries)
     uint32_t dist[1 << kDistBits];      // 1 024 B
-    uint8_t ring[kRing];                // 2 048 B (MSPA_INFLATE_RING)
+    uint8_t ring[kRing];                // 2 048 B (kRing)
     uint32_t pre[128];                  //   512 B  code-length code, 7-bit index
     uint16_t sorted[kLitSyms + kDistSyms];   // 640 B  symbols by (code length, symbol), literal/length then distance alphabet
     uint8_t lens[kLitSyms + kDistSyms];      // 320 B

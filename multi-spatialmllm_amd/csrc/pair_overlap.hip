@@ -69,29 +69,11 @@ __global__ __launch_bounds__(kOThreads) void pair_overlap_kernel(OverlapArgs a) 
 // divide, * 100; 0 / 0 -> NaN, CFR:136).  Work is cut this finely because the popcounts are VALU-bound (v_and + v_bcnt per
 // 32 bits, ~7 M wave instructions for 51 040 pairs of 131 072 bits): a 320-frame scene must become several waves per SIMD.
 // ---------------------------------------------------------------------------------------------------------
-#ifndef MSPA_K2_MFMA
-#define MSPA_K2_MFMA 1
-#endif
-#ifndef MSPA_K2_DRY
-#define MSPA_K2_DRY 0          // timing ablations only (results wrong by construction): 1 = no spreading, no MFMA; 2 = spreading only
-#endif
-#ifndef MSPA_K2_ACC2
-#define MSPA_K2_ACC2 0
-#endif
 constexpr int kTile = 32;                  // rows of a and of b per workgroup
-#ifndef MSPA_K2_CHUNK_WORDS
-#define MSPA_K2_CHUNK_WORDS 8
-#endif
-#ifndef MSPA_K2_WAVE_CHUNKS
-#define MSPA_K2_WAVE_CHUNKS 2
-#endif
-#ifndef MSPA_K2_MIN_WAVES
-#define MSPA_K2_MIN_WAVES 5
-#endif
-constexpr int kChunkWords = MSPA_K2_CHUNK_WORDS;          // bitset words staged per step (8: 5 KB of LDS per wave)
+constexpr int kChunkWords = 8;                            // bitset words staged per step (8: 5 KB of LDS per wave)
 constexpr int kRowDw = kChunkWords * 2 + 4;               // LDS row stride in dwords: 16-byte aligned, bank-skewed
 constexpr int kTileWaves = 4;                             // waves per workgroup
-constexpr int kWaveChunks = MSPA_K2_WAVE_CHUNKS;          // chunks per wave; the next chunk's loads fly while this one is counted
+constexpr int kWaveChunks = 2;                            // chunks per wave; the next chunk's loads fly while this one is counted
 constexpr int kSliceWords = kChunkWords * kTileWaves * kWaveChunks;
 constexpr int kLoadsPerChunk = kChunkWords / 2;           // 16-byte loads per lane and chunk (64 rows x kChunkWords x 8 B / 64 lanes)
 constexpr int kLanesPerRow = kChunkWords / 2;             // lanes covering one row's chunk
@@ -163,7 +145,7 @@ __device__ __forceinline__ void count_chunk(uint32_t *my, int lrow, int lcol, in
 // (profiles/r02_valu_rates.txt: 5.7 cycles per instruction at one wave per SIMD, 2.2 at eight), so this popcount-bound
 // kernel needs many resident waves, i.e. few registers (one staged chunk at a time, the next one in flight) and little LDS.
 template <bool ALIGNED16>
-__global__ __launch_bounds__(kTileWaves *kWave, MSPA_K2_MIN_WAVES) void overlap_tile_kernel(TileArgs a) {
+__global__ __launch_bounds__(kTileWaves *kWave, 5) void overlap_tile_kernel(TileArgs a) {
     // tile list: all (ta, tb) for a rectangle; for a symmetric problem only ta <= tb, enumerated row by row of the triangle
     int ta, tb;
     if (a.symmetric) {
@@ -282,9 +264,6 @@ __global__ __launch_bounds__(kTileWaves *kWave) void overlap_tile_mfma_kernel(Ti
     static_assert(kWaveLines * kMfmaChunkWords * kTileWaves == kSliceWords, "the slice splits into whole lines per wave");
     const int64_t w0 = (int64_t)slice * kSliceWords + (int64_t)wave * (kWaveLines * kMfmaChunkWords) + g * (kMfmaChunkWords / 2);
     v16i acc = {};
-#if MSPA_K2_ACC2
-    v16i acc2 = {};
-#endif
     u32x4 ca[kWaveLines][4], cb[kWaveLines][4];
 #pragma unroll
     for (int c = 0; c < kWaveLines; ++c) {
@@ -299,22 +278,10 @@ __global__ __launch_bounds__(kTileWaves *kWave) void overlap_tile_mfma_kernel(Ti
             const uint32_t db[4] = {cb[c][q].x, cb[c][q].y, cb[c][q].z, cb[c][q].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-#if MSPA_K2_DRY == 1
-                acc[0] += (int)(da[e] ^ db[e]);
-#elif MSPA_K2_DRY == 2
-                acc[0] += spread16<0>(da[e])[0] + spread16<0>(db[e])[1] + spread16<1>(da[e])[2] + spread16<1>(db[e])[3] + spread16<0>(da[e])[2] + spread16<0>(db[e])[3] + spread16<1>(da[e])[0] + spread16<1>(db[e])[1];
-#elif MSPA_K2_ACC2
-                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(spread16<0>(da[e]), spread16<0>(db[e]), acc, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(spread16<1>(da[e]), spread16<1>(db[e]), acc2, 0, 0, 0);
-#else
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(spread16<0>(da[e]), spread16<0>(db[e]), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(spread16<1>(da[e]), spread16<1>(db[e]), acc, 0, 0, 0);
-#endif
             }
         }
-#if MSPA_K2_ACC2
-    acc += acc2;
-#endif
     // accumulator register v of lane (r, g) is element (i = 8 (v / 4) + 4 g + v % 4, j = r) of the 32 x 32 product;
     // the four waves' tables are summed through LDS and the block writes one partial table, as the popcount form does
     __shared__ int32_t lds[kTileWaves][kTile * kTile];
@@ -421,12 +388,10 @@ static int launch_tiles(const uint64_t *bits_a, int n_a, const uint64_t *bits_b,
     const int64_t n_tiles = symmetric ? (int64_t)p.tiles_a * (p.tiles_a + 1) / 2 : (int64_t)p.tiles_a * p.tiles_b;
     const dim3 grid((uint32_t)n_tiles, (uint32_t)p.slices);
     const bool aligned = (n_words % 2 == 0) && (((uintptr_t)bits_a & 15u) == 0) && (((uintptr_t)bits_b & 15u) == 0);
-#if MSPA_K2_MFMA
     if (aligned) {                                   // the matrix-core form needs whole 16-byte pieces of every row
         hipLaunchKernelGGL(overlap_tile_mfma_kernel, grid, dim3(kTileWaves * kWave), 0, s, t);
         return check_hip(hipGetLastError(), "overlap_tile_mfma_kernel launch");
     }
-#endif
     if (aligned) hipLaunchKernelGGL(overlap_tile_kernel<true>, grid, dim3(kTileWaves * kWave), 0, s, t);
     else hipLaunchKernelGGL(overlap_tile_kernel<false>, grid, dim3(kTileWaves * kWave), 0, s, t);
     return check_hip(hipGetLastError(), "overlap_tile_kernel launch");

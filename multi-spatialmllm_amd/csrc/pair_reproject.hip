@@ -38,7 +38,7 @@ struct PairArgs {
     double sx, sy;         // dw / W, dh / H  (IH:359-360, OPS:272-273)
     int strips;            // exact kernel: 4096-pixel strips per pair;  fast kernel: groups of 4 wave tiles
     int n_stripes, n_tiles;   // fast kernel: 64-column stripes per row band, wave tiles per pair
-    int n_wave_tiles;         // tight kernel: tile GROUPS per pair (a wave walks TPW vertically adjacent tiles); == n_tiles when TPW == 1
+    int n_wave_tiles;         // == n_tiles
     uint32_t stripe_magic;    // floor(2^32 / n_stripes) + 1
     uint64_t *vis_bits;
     uint8_t *vis_u8;
@@ -712,137 +712,59 @@ __global__ __launch_bounds__(kThreads) void pair_fast_kernel(const uint16_t *__r
 //     vector pipe); risky rows are recorded per wave (ballot -> VGPR lane) instead of per-lane bit masks;
 //   * 48 rows per wave tile amortise the per-tile matrix composition;
 //   * a group of 4 rows none of whose 256 pixels can land in frame 2 skips gather, guard and depth test.
-#ifndef MSPA_TIGHT_ROWS
-#define MSPA_TIGHT_ROWS 48
-#endif
-#ifndef MSPA_TIGHT_BLOCK_WAVES
-#define MSPA_TIGHT_BLOCK_WAVES 0       // 0 = per output set (tight_bw_of)
-#endif
-#ifndef MSPA_TIGHT_DMA16
-#define MSPA_TIGHT_DMA16 1
-#endif
-#ifndef MSPA_STAGE2_ROW_BARRIER
-#define MSPA_STAGE2_ROW_BARRIER 0      // 0 never, 1 after every row, 2 after the second row only, 3 after the second row for the compacted set only
-#endif
-#ifndef MSPA_SCALED_ROW_BARRIER
-#define MSPA_SCALED_ROW_BARRIER 1      // ScanNet-shape kernel: 100 -> 73 VGPRs (4 -> 6 waves per SIMD), 2.30 -> 2.11 ms per 1 000 pairs
-#endif
-#ifndef MSPA_SCALED_TILE_CULL
-#define MSPA_SCALED_TILE_CULL 1        // ScanNet-shape kernel: frustum test of a tile's colour box against frame 2 before projecting it
-#endif
-#ifndef MSPA_SCALED_FULL_WAIT
-#define MSPA_SCALED_FULL_WAIT 1        // ScanNet-shape kernel: one vmcnt(0) for a group's gathers instead of a counted wait per row (-1..4 %)
-#endif
-#ifndef MSPA_PRIO
-#define MSPA_PRIO 1                    // s_setprio: a tile's prologue above the row loops (correspondence and minimal sets; 0 = off)
-#endif
-#ifndef MSPA_COMPACT_LDS_PAD
-#define MSPA_COMPACT_LDS_PAD 0
-#endif
-#ifndef MSPA_TIGHT_WAVES_PER_EU
-#define MSPA_TIGHT_WAVES_PER_EU 0      // > 0: ask the register allocator for that many waves per SIMD
-#endif
-#if MSPA_TIGHT_WAVES_PER_EU > 0
-#define MSPA_TIGHT_ATTR __attribute__((amdgpu_waves_per_eu(MSPA_TIGHT_WAVES_PER_EU, MSPA_TIGHT_WAVES_PER_EU)))
-#else
-#define MSPA_TIGHT_ATTR
-#endif
-constexpr int kTightRows = MSPA_TIGHT_ROWS;            // tile height of the correspondence family (= MSPA_CORR_TILE_H)
-#ifndef MSPA_TIGHT_ROWS_DENSE
-#define MSPA_TIGHT_ROWS_DENSE 32
-#endif
+constexpr int kTightRows = 48;                         // tile height of the correspondence family (= MSPA_CORR_TILE_H)
 // The dense sets carry a 3 KB transpose stage per wave: with 48-row tiles that is 36 KB of LDS per workgroup (four per CU),
 // with 32-row tiles 28 KB (five): measured 1.22 -> 1.17 ms per 1 000 pairs (dense without colour words, tools/ab_k3.py)
-constexpr int kTightRowsDense = MSPA_TIGHT_ROWS_DENSE;
-#ifndef MSPA_TIGHT_RG_LIGHT
-#define MSPA_TIGHT_RG_LIGHT 4
-#endif
+constexpr int kTightRowsDense = 32;
 // rows whose depth-2 gathers are in flight together: the sets without a transpose stage (minimal, compact) may take more
-constexpr int tight_rg_of(uint32_t set) { return (set & (O_PIX | O_XYZ32 | O_RGBA | O_VIS_U8)) ? kRowGroup : MSPA_TIGHT_RG_LIGHT; }
-// Two A/B knobs of round 5, both measured at noise level and left off (tools/ab_scannet.py / ab_k3.py, one box, ms per 1 000
-// pairs, shipped -> knob): MSPA_WG_COMPOSE = 1 -- ScanNet's shape corr 1.717 -> 1.701, minimal 1.343 -> 1.336, compact 1.798 ->
-// 1.814; 640x480 corr 0.4494 -> 0.4514, compact 0.3489 -> 0.3497, minimal 0.2855 -> 0.2834: the workgroup barrier costs what
-// the ~65 saved issues per tile save.  MSPA_SCALED_CULL_BATCH = 16 -- corr 1.717 -> 1.716, minimal 1.343 -> 1.361, compact
-// 1.798 -> 1.793: a culled tile's twelve serial round trips are hidden by the other waves already.
-#ifndef MSPA_WG_COMPOSE
-#define MSPA_WG_COMPOSE 0              // 1: the pair's composed matrix once per WORKGROUP (wave 0 -> LDS -> the others), not per wave
-#endif
-#ifndef MSPA_SCALED_CULL_BATCH
-#define MSPA_SCALED_CULL_BATCH 4       // SCALED form, culled tile: rows whose samples are requested together for the valid-sample count
-#endif
+constexpr int tight_rg_of(uint32_t set) { return (set & (O_PIX | O_XYZ32 | O_RGBA | O_VIS_U8)) ? kRowGroup : 4; }
+// Two variants of round 5 were measured at noise level and removed (tools/ab_scannet.py / ab_k3.py, one box, ms per 1 000
+// pairs, shipped -> variant).  The pair's composed matrix once per WORKGROUP (wave 0 -> LDS -> the others behind a workgroup
+// barrier, 12 broadcast reads + 24 v_readfirstlane) instead of per wave (~100 VALU issues of a tile's ~400 of fixed work) --
+// ScanNet's shape corr 1.717 -> 1.701, minimal 1.343 -> 1.336, compact 1.798 -> 1.814; 640x480 corr 0.4494 -> 0.4514, compact
+// 0.3489 -> 0.3497, minimal 0.2855 -> 0.2834: the workgroup barrier cost what the ~65 saved issues per tile saved.  Sixteen
+// rows per round trip instead of four in a culled SCALED tile's valid-sample count (kScaledCullBatch) -- corr 1.717 -> 1.716,
+// minimal 1.343 -> 1.361, compact 1.798 -> 1.793: a culled tile's twelve serial round trips are hidden by the other waves
+// already.
+constexpr int kScaledCullBatch = 4;    // SCALED form, culled tile: rows whose samples are requested together for the valid-sample count
 // Tile height of the SCALED form (no LDS tile: height costs no occupancy; one lane per tile row holds its visibility word, so
 // 64 at most).  A tile's fixed work -- box scan, composition, culling test, ~400 VALU issues and their round trips -- is paid
 // per tile whatever it goes on to do, and at ScanNet's shape about half the tiles are culled: the minimal set runs 10 % faster
 // on 64-row tiles (1.298 vs 1.445 ms per 1 000 pairs), the correspondence set 7 % slower (1.821 vs 1.708: coarser culling
 // writes more of its index table), tools/ab_scannet.py round 5.  The compacted set's tile is part of the API (48).
-#ifndef MSPA_SCALED_ROWS
-#define MSPA_SCALED_ROWS 48
-#endif
-#ifndef MSPA_SCALED_ROWS_NOPIX
-#define MSPA_SCALED_ROWS_NOPIX 64
-#endif
-// Tiles per wave of the SCALED form (MSPA_SCALED_TPW_*, A/B knob, 1 = off): a wave walks this many vertically adjacent tiles --
-// launch, the pair's matrices, the column's depth-grid offsets and the other per-stripe constants are paid once for them, the
-// culling stays per tile.  Measured at ScanNet's shape (tools/ab_scannet.py, round 5, ms per 1 000 pairs at 1 / 2 / 3 / 4 tiles):
-// corr 1.745 / 2.102 / 2.125 / 2.256, minimal 1.349 / 2.021 / 2.055 / 1.996 -- bit-identical and 20-50 % SLOWER: what is live
-// across the tile loop costs the row loop its registers (minimal: 42 VGPRs spilled to scratch in it).  Not for the compacted
-// set at all: with its spills the SGPR quad of the inline-asm `idxen` store came back wrong (memory fault; static_assert below).
-#ifndef MSPA_SCALED_TPW_CORR
-#define MSPA_SCALED_TPW_CORR 1
-#endif
-#ifndef MSPA_SCALED_TPW_COMPACT
-#define MSPA_SCALED_TPW_COMPACT 1
-#endif
-#ifndef MSPA_SCALED_TPW_NOPIX
-#define MSPA_SCALED_TPW_NOPIX 1
-#endif
-constexpr int tight_tpw_of(uint32_t set, bool scaled) {
-    return !scaled ? 1 : (set & O_CPIX) ? MSPA_SCALED_TPW_COMPACT : (set & O_PIX) ? MSPA_SCALED_TPW_CORR : MSPA_SCALED_TPW_NOPIX;
-}
+constexpr int kScaledRows = 48;
+constexpr int kScaledRowsNoPix = 64;
+// A wave of the SCALED form takes ONE tile.  Walking several vertically adjacent tiles per wave -- launch, the pair's matrices,
+// the column's depth-grid offsets and the other per-stripe constants paid once for them, the culling still per tile -- was
+// measured at ScanNet's shape (tools/ab_scannet.py, round 5, ms per 1 000 pairs at 1 / 2 / 3 / 4 tiles) and rejected:
+// corr 1.745 / 2.102 / 2.125 / 2.256, minimal 1.349 / 2.021 / 2.055 / 1.996 -- bit-identical and 20-50 % SLOWER: what was live
+// across the tile loop cost the row loop its registers (minimal: 42 VGPRs spilled to scratch in it).  For the compacted set
+// it never worked at all: with its spills the SGPR quad of the inline-asm `idxen` store came back wrong (memory fault).
 constexpr int tight_rows_of(uint32_t set, bool scaled = false) {
     return (set & (O_XYZ32 | O_RGBA | O_VIS_U8)) ? kTightRowsDense
-           : (scaled && !(set & O_CPIX)) ? ((set & O_PIX) ? MSPA_SCALED_ROWS : MSPA_SCALED_ROWS_NOPIX) : kTightRows;
+           : (scaled && !(set & O_CPIX)) ? ((set & O_PIX) ? kScaledRows : kScaledRowsNoPix) : kTightRows;
 }
 // waves (= tiles) per workgroup, per output set (tools/ab_k3.py, one box, ms per 1 000 pairs at 1 / 2 / 4 / 8 waves): the sets
 // without an index table like small workgroups -- a workgroup's LDS is released only when its slowest tile is done --
 // minimal 0.325 / 0.309 / 0.319 / 0.351, compact 0.388 / 0.377 / 0.388 / 0.424; corr 0.525 / 0.505 / 0.503 / 0.558; the dense
 // point set without colour a large one, dense_xyz 1.303 / 1.200 / 1.149 / 1.132 (with colour words 4 stay better than 8:
-// 1.572 vs 1.587).  MSPA_TIGHT_BLOCK_WAVES > 0 forces one size for all (A/B builds).
+// 1.572 vs 1.587).
 // The SCALED form (no LDS depth tile: a workgroup's size costs no occupancy) runs best at four for every set
 // (tools/ab_scannet.py at ScanNet's shape, ms per 1 000 pairs at 1 / 2 / 4 / 8 waves: minimal 2.76 / 1.94 / 1.55-1.63 / 1.63,
 // compact 3.03 / 2.18 / 1.93 / 2.01, corr 2.55 / - / 1.72-1.80 / 1.79).
 constexpr int tight_bw_of(uint32_t set, bool scaled = false) {
-    return MSPA_TIGHT_BLOCK_WAVES > 0 ? MSPA_TIGHT_BLOCK_WAVES
-           : scaled ? 4
+    return scaled ? 4
            : (set & O_RGBA) ? 4
            : (set & (O_XYZ32 | O_VIS_U8)) ? 8
            : (set & O_PIX) ? 4 : 2;
 }
 // waves per SIMD the register allocator must leave room for (second argument of __launch_bounds__): the sets without an
 // index table run best at six (80 VGPRs); round 4's guard-band bookkeeping had pushed `minimal` to 82 = five waves, +5 %
-// (the SCALED correspondence set sat at 97 VGPRs = four waves: held at five)
-#ifndef MSPA_CORR_MINWAVES
-#define MSPA_CORR_MINWAVES 1           // A/B knob: waves per SIMD the correspondence-table instantiation is held to (register budget)
-#endif
-#ifndef MSPA_COMPACT_FRACT
-#define MSPA_COMPACT_FRACT 0
-#endif
-#ifndef MSPA_COMPACT_MINWAVES
-#define MSPA_COMPACT_MINWAVES MSPA_NOPIX_MINWAVES
-#endif
-#ifndef MSPA_NOPIX_MINWAVES
-#define MSPA_NOPIX_MINWAVES 6
-#endif
-#ifndef MSPA_SCALED_NOPIX_MINWAVES
-#define MSPA_SCALED_NOPIX_MINWAVES 6
-#endif
-#ifndef MSPA_SCALED_CORR_MINWAVES
-#define MSPA_SCALED_CORR_MINWAVES 5
-#endif
+// (the SCALED correspondence set sat at 97 VGPRs = four waves: held at five; the whole-tile correspondence set is not held)
 constexpr int tight_minwaves_of(uint32_t set, bool scaled) {
     return (set & (O_XYZ32 | O_RGBA | O_VIS_U8)) ? 1
-           : (set & O_PIX) ? (scaled ? MSPA_SCALED_CORR_MINWAVES : MSPA_CORR_MINWAVES)
-           : (scaled ? MSPA_SCALED_NOPIX_MINWAVES : (set & O_CPIX) ? MSPA_COMPACT_MINWAVES : MSPA_NOPIX_MINWAVES);
+           : (set & O_PIX) ? (scaled ? 5 : 1)
+           : 6;
 }
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
@@ -913,7 +835,7 @@ __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m, uint32_t base)
 //   * the bitset: W % 16 == 0 makes a tile row's 64 bits four ALIGNED 16-bit pieces of the row-major bitset whatever the
 //     row -- four 2-byte stores per tile (lane = row) instead of one 8-byte store, no atomics, no wobble.
 template <uint32_t SET, bool STREAM, int ROWS, int RG, bool SCALED = false>
-__global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of(SET, SCALED)) MSPA_TIGHT_ATTR void pair_fast_tight_kernel(const uint16_t *__restrict__ depth,
+__global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of(SET, SCALED)) void pair_fast_tight_kernel(const uint16_t *__restrict__ depth,
                                                                    const uint8_t *__restrict__ rgb,
                                                                    const double *__restrict__ mats,
                                                                    const int32_t *__restrict__ pairs, PairArgs a) {
@@ -921,7 +843,7 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
     constexpr int kTightBW = tight_bw_of(SET, SCALED);
     constexpr bool WANT_XYZ = (SET & O_XYZ32) != 0;
     constexpr bool COMPACT = (SET & O_CPIX) != 0;
-    constexpr bool FRACT_GUARD = (!COMPACT || (MSPA_COMPACT_FRACT && !SCALED)) && !(SCALED && (SET & O_PIX));   // stage 2's tie / bound test by v_fract (see there)
+    constexpr bool FRACT_GUARD = !COMPACT && !(SCALED && (SET & O_PIX));   // stage 2's tie / bound test by v_fract (see there)
     constexpr double kUV = FRACT_GUARD ? 2.0 : 1.0;                           // ... on doubled image coordinates
     static_assert(RG == 4 || !(SET & (O_PIX | O_XYZ32 | O_RGBA | O_VIS_U8)), "the transpose stages move 4-row blocks");
     static_assert(ROWS % RG == 0, "whole row groups");
@@ -933,7 +855,7 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
     // A new wave gets its requests and its per-tile work out ahead of the row loops of the others (s_setprio; back to 0 in front
     // of the row loop): corr -1.5 %, minimal -0.5 % (ScanNet's shape: -2.7 %), compact +2 % -- so not for the compacted set
     // (tools/ab_k3.py, ab_scannet.py, one box; raising stage 2 above the rest as well changed nothing).
-    constexpr bool PROLOGUE_PRIO = MSPA_PRIO && !(SET & (O_CPIX | O_XYZ32 | O_RGBA | O_VIS_U8));
+    constexpr bool PROLOGUE_PRIO = !(SET & (O_CPIX | O_XYZ32 | O_RGBA | O_VIS_U8));
     if (PROLOGUE_PRIO) __builtin_amdgcn_s_setprio(2);
     const int f1 = pairs[2 * pair + 0];
     const int f2 = pairs[2 * pair + 1];
@@ -951,14 +873,17 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
 
     // wave tile -> (row band, column stripe); both wave-uniform
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int TPW = tight_tpw_of(SET, SCALED);
-    static_assert(TPW == 1 || !(SET & O_CPIX), "tiles per wave > 1 is not available for the compacted set (see tight_tpw_of)");
-    const uint32_t wtile = tgroup * kTightBW + wave;                 // this wave's tile group: TPW vertically adjacent tiles
+    // One tile per wave.  The walk over TPW vertically adjacent tiles (measured and rejected, see above tight_rows_of) keeps its loop
+    // form with TPW = 1: written as straight-line code the same arithmetic comes out of the compiler with another register
+    // allocation in every instantiation, and the measurements above belong to this code.
+    constexpr int TPW = 1;
+    static_assert(TPW == 1, "the host sizes the grid for one tile per wave; more never worked for the compacted set");
+    const uint32_t wtile = tgroup * kTightBW + wave;                 // this wave's tile
     const uint32_t sband = a.n_stripes == 1 ? wtile : __umulhi(wtile, a.stripe_magic);
     const uint32_t stripe = wtile - sband * (uint32_t)a.n_stripes;
     const bool tile_ok = wtile < (uint32_t)a.n_wave_tiles;
     const uint32_t col = stripe * 64u + (uint32_t)c.lane;
-    uint32_t row0 = sband * (uint32_t)(TPW * ROWS);                  // of the group's first tile; advanced per tile below
+    uint32_t row0 = sband * (uint32_t)(TPW * ROWS);
     uint32_t tile = sband * (uint32_t)TPW * (uint32_t)a.n_stripes + stripe;   // tile index of the API (band-major)
 
     // The tile's depth-1 samples (48 rows x 128 B) go HBM -> LDS by LDS-DMA, two rows per wave
@@ -972,14 +897,11 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
     // predecessor).  The wave's LDS operations execute in order; the next group reads ITS rows before its stage overwrites them.
     constexpr bool PX_IN_TILE = !SCALED && (SET & O_PIX) && !(SET & (O_XYZ32 | O_RGBA));
     constexpr int kPadPx = PX_IN_TILE ? 256 : 0;                        // uint16 units: 512 bytes
-    // (MSPA_COMPACT_LDS_PAD: A/B knob -- bytes of LDS added per wave of the compacted set to cap its waves per SIMD)
-    constexpr int kOccPad = (COMPACT && !SCALED) ? MSPA_COMPACT_LDS_PAD / 2 : 0;
-    __shared__ __attribute__((aligned(16))) uint16_t lds_w[kTightBW][SCALED ? 16 : kPadPx + ROWS * 64 + kOccPad];   // SCALED: counter slots only
+    __shared__ __attribute__((aligned(16))) uint16_t lds_w[kTightBW][SCALED ? 16 : kPadPx + ROWS * 64];   // SCALED: counter slots only
     uint16_t *const lds_d1w = &lds_w[wave][kPadPx];                     // this wave's 48 x 64 depth-1 samples
     if (tile_ok && !SCALED) {
         typedef __attribute__((address_space(1))) const void gvoid_t;
         typedef __attribute__((address_space(3))) void lvoid_t;
-#if MSPA_TIGHT_DMA16
         // gfx950's 16-byte LDS-DMA: eight lanes fetch a row's 128 bytes, one wave instruction lands eight rows (1 KB,
         // contiguous in LDS: lane L writes bytes 16 L .. 16 L + 15 past the base) -- 6 requests per tile instead of 24
         static_assert(ROWS % 8 == 0, "eight rows per 16-byte LDS-DMA request");
@@ -989,14 +911,6 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
         for (int k = 0; k < ROWS / 8; ++k)
             __builtin_amdgcn_global_load_lds((gvoid_t *)(src + (int64_t)(8 * k) * a.W),
                                              (lvoid_t *)&lds_d1w[k * 512], 16, 0, STREAM ? 2 : 0);  // aux 2 = nt
-#else
-        const uint16_t *src = c.depth1 + (int64_t)(row0 + (uint32_t)(c.lane >> 5)) * a.W + stripe * 64u +
-                              (uint32_t)(c.lane & 31) * 2u;
-#pragma unroll
-        for (int k = 0; k < ROWS / 2; ++k)
-            __builtin_amdgcn_global_load_lds((gvoid_t *)(src + (int64_t)(2 * k) * a.W),
-                                             (lvoid_t *)&lds_d1w[k * 128], 4, 0, STREAM ? 2 : 0);   // aux 2 = nt
-#endif
     }
 
     const double *__restrict__ U = m1 + MSPA_MAT_UNPROJ * 16;
@@ -1036,44 +950,17 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
             M[2][k] = uniform(raw[2][k]);
         }
     };
-    // MSPA_WG_COMPOSE: the tiles of a workgroup belong to one pair, so its waves would all form the same twelve numbers (~100
-    // VALU issues of a tile's ~400 of fixed work).  Wave 0 forms them, parks them in LDS, the others pick them up behind a
-    // workgroup barrier (12 broadcast reads + 24 v_readfirstlane).  `all_here`: every wave of the workgroup reaches this point
-    // (block-uniform) -- otherwise each wave composes for itself as before.
-    constexpr bool WG_COMPOSE = MSPA_WG_COMPOSE && kTightBW > 1 && !WANT_XYZ;
-    __shared__ __attribute__((aligned(16))) double lds_mat[WG_COMPOSE ? 12 : 1];
-    auto obtain_matrix = [&](bool all_here) {
-        if (!WG_COMPOSE || !all_here) {
-            compose();
-            return;
-        }
-        if (wave == 0) {
-            compose();
-            if (c.lane == 0) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) lds_mat[4 * r + k] = M[r][k];
-            }
-        }
-        __syncthreads();
-        if (wave != 0) {
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) M[r][k] = uniform(lds_mat[4 * r + k]);
-        }
-    };
+    // (a lambda of its own: with `compose` called at the two places directly the compiler inlines it differently and every
+    // instantiation's code changes)
+    auto obtain_matrix = [&]() { compose(); };
     // The whole-tile form composes here, behind its LDS-DMA requests.  The SCALED form has no such requests in flight yet: it
     // composes further down, behind the loads of its depth box and of its first row group.
-    if (!SCALED) obtain_matrix(true);
+    if (!SCALED) obtain_matrix();
 
     // transpose stage: the group's pixel indices, then (dense set) its rgba words, then its 4 x 64 x 3 point coordinates
     __shared__ __attribute__((aligned(16))) uint32_t lds_pxs[kTightBW][(PX_IN_TILE || !(SET & (O_PIX | O_XYZ32 | O_RGBA))) ? 4 : RG * 64 * (WANT_XYZ ? 3 : 1)];
     static_assert(ROWS <= 64, "one lane per tile row holds that row's visibility word");
-#ifndef MSPA_EXPERIMENT_ROWS   // timing-only builds with another tile height (tools/build_variant.sh): the compacted set is then wrong
     static_assert(!COMPACT || (ROWS * 64 == MSPA_CORR_TILE_CAP && ROWS == MSPA_CORR_TILE_H), "tile segment of the compacted set");
-#endif
     int n_valid = 0, n_vis = 0;
 #pragma unroll 1
     for (int sub = 0; tile_ok && sub < TPW; ++sub) {
@@ -1082,7 +969,6 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
             tile += (uint32_t)a.n_stripes;
             if (row0 >= (uint32_t)a.H) break;
         }
-        const int n_vis_before = n_vis;
         const uint32_t Wb = (uint32_t)a.W;
         // buffer resources: SGPR base + byte count; raw addressing = base + voffset (VGPR) + soffset (SGPR)
         const int kRsrcFlags = 0x00020000;
@@ -1149,7 +1035,7 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
             }
 #pragma unroll
             for (int j = 0; j < RG; ++j) d16_first[j] = load_d1_row(j);
-            if (sub == 0) obtain_matrix((tgroup * (uint32_t)kTightBW + (uint32_t)(kTightBW - 1)) < (uint32_t)a.n_wave_tiles);
+            obtain_matrix();
         }
         // dense payload: byte mask (lane L: 4 pixels of row L >> 4), colour in / rgba out, points (16-byte pieces of the
         // group's 4 x 768 bytes: piece 64 k + L lies in row (16 (64 k + L)) / 768)
@@ -1336,9 +1222,9 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
                         n_valid += __popcll(ballot64((w & 0xFFFFu) != 0u)) + __popcll(ballot64(w > 0xFFFFu));
                     }
                 } else {                                   // the tile's own samples (the box only bounded their range)
-                    // MSPA_SCALED_CULL_BATCH rows per round trip: a culled tile does nothing else, so its registers are free
+                    // kScaledCullBatch rows per round trip: a culled tile does nothing else, so its registers are free
                     // for the requests (4 per trip made a 48-row tile twelve serial round trips)
-                    constexpr int CB = MSPA_SCALED_CULL_BATCH;
+                    constexpr int CB = kScaledCullBatch;
 #pragma unroll 1
                     for (int r0 = 0; r0 < n_rows; r0 += CB) {
                         uint32_t d[CB];
@@ -1480,14 +1366,11 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
                             rkc[j] = ballot64(!(__builtin_fmax(__builtin_fabs(wu), __builtin_fabs(wv)) < 0.25 - kGuardPx));
                         }
                         if (CAREFUL) rkc[j] |= ballot64(!(qz[j] > zmin));        // lanes behind the plane are not in ivm
-                        // Scheduling barrier between rows (A/B knob, off): left to itself the scheduler interleaves the four rows'
-                        // rounding / guard code and keeps all their temporaries live.  Until round 4's second half the compacted set
-                        // took one barrier, after the second row (73 VGPRs; 0.381 vs 0.387 ms with none); with the shorter stage 2
-                        // the interleaved form is the better one for every set (compact 0.353 vs 0.391 ms with that barrier,
+                        // No scheduling barrier between rows: left to itself the scheduler interleaves the four rows' rounding /
+                        // guard code and keeps all their temporaries live.  Until round 4's second half the compacted set took one
+                        // barrier, after the second row (73 VGPRs; 0.381 vs 0.387 ms with none); with the shorter stage 2 the
+                        // interleaved form was the better one for every set (compact 0.353 vs 0.391 ms with that barrier,
                         // tools/ab_k3.py, one box; a barrier after every row: corr 0.66, minimal 0.40 ms).
-                        if (MSPA_STAGE2_ROW_BARRIER == 1 || (MSPA_STAGE2_ROW_BARRIER == 2 && j == 1) ||
-                            (MSPA_STAGE2_ROW_BARRIER == 3 && COMPACT && j == 1))
-                            __builtin_amdgcn_sched_barrier(0);
                     }
                     // ---- stage 3: depth test, outputs -------------------------------------------------------
                     unsigned long long rbm[RG];
@@ -1585,9 +1468,6 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
 
         // ---- cold loop: rows with guarded lanes are re-evaluated with the exact chain ---------------
         bool redo = false;                                  // compacted set: a guarded lane changed its visibility (wave-uniform)
-#ifdef MSPA_EXPERIMENT_NOCOLD   // timing only (wrong results on rows with guarded lanes)
-        risky_rows = 0;
-#endif
         if (risky_rows) {
             __builtin_amdgcn_s_waitcnt(0);                 // the fast path's stores are in L2, LDS writes landed
             // compacted set: lane r <- entries of the tile's rows above r (exclusive prefix of the rows' popcounts), so that
@@ -1662,7 +1542,7 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
                     base += (uint32_t)__popcll(w);
                 }
             }
-            if (c.lane == 0) a.tile_counts[pair * (int64_t)a.n_tiles + (int64_t)tile] = n_vis - n_vis_before;
+            if (c.lane == 0) a.tile_counts[pair * (int64_t)a.n_tiles + (int64_t)tile] = n_vis;
         }
         // the tile's visibility words: lane r stores the word of row row0 + r (8 bytes; rows are W/8 bytes apart)
         if (SCALED && (Wb & 63u)) {
@@ -1845,14 +1725,13 @@ __global__ __launch_bounds__(kThreads) void pair_fast_scaled_kernel(const uint16
         const double *__restrict__ bnd2 = m2 + MSPA_MAT_BOUNDS * 16;
         constexpr double wh_max = (double)(W_ > H_ ? W_ : H_);
         double zmin = 0.0, gz = kGuardZmmFloor, tnear = 0.0;
-        if (last || !MSPA_SCALED_TILE_CULL) {             // no pre-pass for the last stripe: the bound over the full sample range
+        if (last) {                                       // no pre-pass for the last stripe: the bound over the full sample range
             const Guard gd = guard_from_bounds(bnd1, bnd2, (double)(W_ - 1), (double)(row0 + (uint32_t)(kRows - 1)), 65535.0, wh_max);
             zmin = uniform(gd.zmin);
             gz = uniform(gd.gz);
             tnear = uniform(2.0 * wh_max * gd.zmin);
         }
-#if MSPA_SCALED_TILE_CULL
-        if (!last) {
+        if (!last) {                                      // frustum test of the tile's colour box against frame 2 before projecting it
             typedef unsigned short us4 __attribute__((ext_vector_type(4)));
             const uint32_t cA = stripe * 64u, cB = cA + 63u + (uint32_t)kOff[1];       // kOff[1] is the largest wobble
             static_assert(kOff[1] >= kOff[2] && kOff[1] >= kOff[3] && (S - 2) * 64 + 63 + kOff[1] < W_, "colour box of a tile");
@@ -1909,7 +1788,6 @@ __global__ __launch_bounds__(kThreads) void pair_fast_scaled_kernel(const uint16
             }
             culled = __builtin_amdgcn_readfirstlane((int)culled) != 0;                  // wave-uniform, and known to be
         }
-#endif
         // The tile body once per kind of stripe (compile-time LAST): a run-time flag inside the row loop would keep both
         // variants' masks and corrections live at once (52 spilled SGPRs).
         auto run_tile = [&](auto last_c, auto careful_c) {
@@ -2032,24 +1910,18 @@ __global__ __launch_bounds__(kThreads) void pair_fast_scaled_kernel(const uint16
                         const double ru = __builtin_rint(u[e]), rv = __builtin_rint(v[e]);
                         const int xi = med3_0((int)ru, hi_x);
                         const int yi = med3_0((int)rv, hi_y);
-#if !defined(MSPA_EXPERIMENT_GATHER)
                         dv16[e] = __builtin_amdgcn_raw_buffer_load_b16(rs_d2, (int)(__umul24((uint32_t)yi, (uint32_t)(DW_ * 2)) + ((uint32_t)xi << 1)), 0, 0);
-#elif MSPA_EXPERIMENT_GATHER == 1   // timing only, as in the tight kernel
-                        dv16[e] = __builtin_amdgcn_raw_buffer_load_b16(rs_d2, (int)(__umul24((uint32_t)__builtin_amdgcn_readfirstlane(yi), (uint32_t)(DW_ * 2)) + ((uint32_t)xi << 1)), 0, 0);
-#else
-                        dv16[e] = (uint32_t)xi + 1000u;
-#endif
                         pix[e] = (int)((uint32_t)xi | ((uint32_t)yi << 16));
                         const double wu = __builtin_fabs(u[e] - ru) - 0.25;
                         const double wv = __builtin_fabs(v[e] - rv) - 0.25;
                         rkc[e] = ballot64(!(__builtin_fmax(__builtin_fabs(wu), __builtin_fabs(wv)) < 0.25 - kGuardPx));
                         if (CAREFUL) rkc[e] |= ballot64(!(qz[e] > zmin));
-                        if (MSPA_SCALED_ROW_BARRIER) __builtin_amdgcn_sched_barrier(0);   // see the tight kernel: registers vs interleaving
+                        // a scheduling barrier after every row (the tight kernel runs without: registers vs interleaving):
+                        // 100 -> 73 VGPRs (4 -> 6 waves per SIMD), 2.30 -> 2.11 ms per 1 000 pairs
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                     unsigned long long rbm[NCH];
-#if MSPA_SCALED_FULL_WAIT
-                    __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): ONE wait for the group's gathers instead of one per row
-#endif
+                    __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): ONE wait for the group's gathers instead of a counted one per row (-1..4 %)
     #pragma unroll
                     for (int e = 0; e < NCH; ++e) {
                         const bool inview = __builtin_amdgcn_inverse_ballot_w64(ivm[e]);
@@ -2289,9 +2161,8 @@ static int pair_reproject_impl(const uint16_t *depth, const uint8_t *rgb, const 
                                       : a.n_stripes * ((H + tile_rows - 1) / tile_rows);
         a.stripe_magic = (uint32_t)((1ull << 32) / (uint64_t)a.n_stripes) + 1u;
         const int bw = rect ? tight_bw_of(set, true) : tight24 ? tight_bw_of(set) : (kThreads / kWave);
-        const int tpw = rect ? tight_tpw_of(set, true) : 1;                       // tiles a wave walks (vertically adjacent)
-        a.n_wave_tiles = (tight24 || rect) ? a.n_stripes * (((H + tile_rows - 1) / tile_rows + tpw - 1) / tpw) : a.n_tiles;
-        a.strips = (a.n_wave_tiles + bw - 1) / bw;
+        a.n_wave_tiles = a.n_tiles;
+        a.strips = (a.n_tiles + bw - 1) / bw;
     } else {
         a.n_stripes = a.n_tiles = a.n_wave_tiles = 0;
         a.stripe_magic = 0;
@@ -2425,9 +2296,6 @@ extern "C" int mspa_pair_correspondences(const uint16_t *depth, const double *fr
                                          int32_t *out_counts, void *workspace, int64_t workspace_bytes, uint32_t flags,
                                          mspa_stream_t stream) {
     if (n_pairs == 0) return MSPA_OK;
-#ifdef MSPA_EXPERIMENT_ROWS
-    return fail(MSPA_EUNSUPPORTED, "mspa_pair_correspondences: timing-only build with another tile height");
-#endif
     if (!out_vis_bits || !out_cpix_i16 || !out_tile_counts)
         return fail(MSPA_EINVAL, "mspa_pair_correspondences: vis_bits, cpix and tile_counts are all required");
     if (((uintptr_t)out_cpix_i16 & 15u) || ((uintptr_t)out_vis_bits & 7u))

@@ -28,15 +28,9 @@ struct VertexArgs {
     double dscale;                 // depth_value_scale (IH:76, IH:368): metres per depth unit, 0.001 for ScanNet
 };
 
-#ifndef MSPA_VTHREADS
-#define MSPA_VTHREADS 256
-#endif
-constexpr int kVThreads = MSPA_VTHREADS;
+constexpr int kVThreads = 256;
 static_assert(kVThreads % 64 == 0 && kVThreads <= 256, "the compacted kernel packs the thread index into eight bits");
-#ifndef MSPA_VIMG
-#define MSPA_VIMG 8
-#endif
-constexpr int kImgPerBlock = MSPA_VIMG;
+constexpr int kImgPerBlock = 8;
 
 template <bool HOMOG>
 __global__ __launch_bounds__(kVThreads) void vertex_visibility_kernel(const double *__restrict__ xyz,
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(kVThreads) void vertex_visibility_kernel(const doub
 // the reference chain for all its lanes.  The composed matrix is scaled by 1000: u and v are unchanged and the third
 // coordinate is the camera depth in millimetres, directly comparable with the raw depth sample.
 // ---------------------------------------------------------------------------------------------------------
-constexpr double kVGuardPx = 1e-6;              // K1's own pixel guard (K3's is tunable: mspa_common.h MSPA_GUARD_PX)
+constexpr double kVGuardPx = 1e-6;              // K1's own pixel guard (K3's: mspa_common.h kGuardPx)
 
 // Per-image guard coefficients (za, zb, ga, gb) from slot MSPA_CAM_BOUNDS of the image record (host-side:
 // mspa_camera_bounds_host; round 4's first form computed the 36 multiply-adds of magnitudes in the kernel, one thread per
@@ -140,10 +134,7 @@ __device__ __forceinline__ void image_guard_coefficients(const double *__restric
     out4[2] = 2.0 * b[1];
     out4[3] = __builtin_fma(2.0, b[3], kGuardZmmFloor);
 }
-#ifndef MSPA_VBATCH
-#define MSPA_VBATCH 8
-#endif
-constexpr int kVBatch = MSPA_VBATCH;             // images whose depth gathers are in flight together
+constexpr int kVBatch = 8;                       // images whose depth gathers are in flight together
 
 template <bool IDENT>
 __global__ __launch_bounds__(kVThreads) void vertex_visibility_fast_kernel(const double *__restrict__ xyz,
@@ -299,26 +290,11 @@ __global__ __launch_bounds__(kVThreads) void vertex_visibility_fast_kernel(const
 // unconditionally and re-evaluated.  Same integers as the other two kernels (tests/test_gpu_parity.py: goldens, adversarial
 // cameras, ScanNet's two grids, non-pinhole K).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef MSPA_VCOMPACT
-#define MSPA_VCOMPACT 1
-#endif
-#ifndef MSPA_V_NT
-#define MSPA_V_NT 0
-#endif
-#ifndef MSPA_VCOMPACT_ENTRIES
-#define MSPA_VCOMPACT_ENTRIES 1
-#endif
 constexpr double kVBandPx = kVGuardPx;       // phase A: candidate band around the image, on the homogeneous coordinates
 constexpr double kVTiePx = 2.0 * kVGuardPx;  // phase B: tie / bound guard on the divided coordinates
 
-#ifndef MSPA_VCOMPACT_WAVES
-#define MSPA_VCOMPACT_WAVES 8
-#endif
 template <bool IDENT>
-__global__ __launch_bounds__(kVThreads)
-#if MSPA_VCOMPACT_WAVES
-__attribute__((amdgpu_waves_per_eu(MSPA_VCOMPACT_WAVES, MSPA_VCOMPACT_WAVES)))
-#endif
+__global__ __launch_bounds__(kVThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void vertex_visibility_compact_kernel(const double *__restrict__ xyz,
                                                                               const double *__restrict__ cam_mats,
                                                                               const uint16_t *__restrict__ depth,
@@ -382,19 +358,13 @@ void vertex_visibility_compact_kernel(const double *__restrict__ xyz,
     const int64_t i = (int64_t)vblock * kVThreads + tid;
     const bool live = i < a.n_points;
     const int64_t ic = live ? i : a.n_points - 1;
-    // MSPA_V_NT (off): the vertex array is streamed -- every block reads its 256 vertices once -- so non-temporal loads
-    // should keep its 3 MB per image group from displacing the eight depth frames the XCD's blocks gather from.  Measured
-    // (tools/ab_k1.py, round 3): 0.103 vs 0.092 ms on the shuffled cloud, 0.092 vs 0.077 in Morton order -- slower; so is
+    // Plain loads.  The vertex array is streamed -- every block reads its 256 vertices once -- so non-temporal loads should
+    // have kept its 3 MB per image group from displacing the eight depth frames the XCD's blocks gather from.  Measured
+    // (tools/ab_k1.py, round 3): 0.103 vs 0.092 ms on the shuffled cloud, 0.092 vs 0.077 in Morton order -- slower; so were
     // 16 images per block (0.112 / 0.079).  The 200 MB working set lives in the 256 MB Infinity Cache either way.
-#if MSPA_V_NT
-    const double x = __builtin_nontemporal_load(&xyz[ic * a.point_stride]);
-    const double y = __builtin_nontemporal_load(&xyz[ic * a.point_stride + a.comp_stride]);
-    const double z = __builtin_nontemporal_load(&xyz[ic * a.point_stride + 2 * a.comp_stride]);
-#else
     const double x = xyz[ic * a.point_stride];
     const double y = xyz[ic * a.point_stride + a.comp_stride];
     const double z = xyz[ic * a.point_stride + 2 * a.comp_stride];
-#endif
     lds_xyz[tid][0] = x;
     lds_xyz[tid][1] = y;
     lds_xyz[tid][2] = z;
@@ -468,7 +438,7 @@ void vertex_visibility_compact_kernel(const double *__restrict__ xyz,
     const uint32_t dw2 = (uint32_t)a.dw * 2u, dpix2 = (uint32_t)(dpix * 2);
     const __amdgpu_buffer_rsrc_t rs =
         __builtin_amdgcn_make_buffer_rsrc((void *)(depth + (int64_t)img0 * dpix), 0, (int)((int64_t)nimg * dpix * 2), 0x00020000);
-    constexpr int kEnt = MSPA_VCOMPACT_ENTRIES;                       // list entries per thread and trip: their gathers fly together
+    constexpr int kEnt = 1;                                           // list entries per thread and trip: their gathers fly together
     for (uint32_t e0 = 0; e0 < n; e0 += kVThreads * kEnt) {           // block-uniform trip count
         bool active[kEnt], risky[kEnt];
         uint32_t vv[kEnt], qq[kEnt], d[kEnt];
@@ -519,11 +489,7 @@ void vertex_visibility_compact_kernel(const double *__restrict__ xyz,
             const double sd = izs[k] - (double)d[k];
             bool vis = sd < 0.0;
             const bool rk = active[k] & (risky[k] | !(__builtin_fabs(sd) > gzs[k]));
-#ifdef MSPA_EXPERIMENT_NOCOLD   // timing only (wrong results for guarded lanes)
-            if (false) {
-#else
             if (__builtin_amdgcn_ballot_w64(rk) != 0ull) {            // rare: the reference chain (IH:57-69, 337-386)
-#endif
                 if (rk) {
                     const int img = img0 + (int)qq[k];
                     const double *__restrict__ Einv = cam_mats + (int64_t)img * (MSPA_CAM_MATS * 16);
@@ -674,7 +640,7 @@ extern "C" int mspa_vertex_visibility_ex(const double *xyz, int64_t n_points, in
     a.dscale = depth_value_scale;
     // float64 outputs are DEFINED as the reference's operation order; everything else (bitset, byte mask, counts) takes the
     // composed + guarded kernel, which reproduces the same integers
-    const bool compact = MSPA_VCOMPACT && (int64_t)kImgPerBlock * dh * dw * 2 < 0x7fffffffLL && kImgPerBlock * 12 <= kVThreads;
+    const bool compact = (int64_t)kImgPerBlock * dh * dw * 2 < 0x7fffffffLL && kImgPerBlock * 12 <= kVThreads;
     // ... and so do a general homogeneous coordinate and a depth scale other than the millimetre the composed kernels fold in
     if (homogeneous)
         hipLaunchKernelGGL(vertex_visibility_kernel<true>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);

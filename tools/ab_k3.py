@@ -2,6 +2,7 @@
 """A/B timing of K3 builds inside ONE process on one GPU box: every tools/ab/libmspa_*.so plus the in-tree library is
 loaded through its own ctypes handle, the bench's inputs (vc workload) are built once, and the output sets named on the
 command line are timed interleaved, several rounds, HIP events around `--steps` back-to-back launches.
+The libraries under tools/ab/ are earlier revisions built by tools/build_rev_variant.sh.
 
     python tools/ab_k3.py [--sets corr,compact,minimal,dense_xyz] [--steps 30] [--rounds 3] [--workload vc]
 Prints one line per library: median kernel ms per set (and the spread over the rounds).
