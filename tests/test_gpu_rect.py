@@ -2,8 +2,8 @@
 shape -- 1296x968 colour over 640x480 depth -- gets the FUSED compacted correspondence output (no dense table:
 ``mspa_pair_correspondences_workspace_bytes(..., 968, 1296, FAST) == 0``), and every shape with W % 16 == 0, H % 4 == 0,
 dw % 4 == 0 the correspondence / minimal / compacted sets.  Against the NumPy oracle (``np.nonzero(oracle vis)`` order for the
-compacted set), against the exact kernel on adversarial poses incl. identity pairs (cold loop, in-place rewrite, rebuild), and
-against the wobbling-stripe kernel the correspondence set takes by default at ScanNet's shape.
+compacted set), against the exact kernel on adversarial poses incl. identity pairs (cold loop, in-place rewrite, rebuild), and, at
+ScanNet's shape, with the retired flag MSPA_PAIR_WORD_STRIPES (the kernel it selected was removed): accepted, changes nothing.
 
 Shapes: a ragged right stripe (16 live columns) and a ragged bottom band (4 / 8 rows); rows that are not whole bitset words
 (W = 144, 1296: the 2-byte bitset stores) and rows that are (W = 128 over a 64-wide depth grid: the 8-byte store); equal
@@ -115,8 +115,8 @@ def test_rect_kernel_equals_exact_on_adversarial_poses(name):
 @pytest.mark.gpu
 def test_rect_kernel_at_scannet_shape():
     """ScanNet's own shape: the fused compacted set needs no workspace and equals np.nonzero(oracle vis) order; the
-    rectangular-tile kernel's correspondence / minimal sets equal the oracle's AND the wobbling-stripe
-    kernel's; 30 adversarial pairs against the exact kernel."""
+    rectangular-tile kernel's correspondence / minimal sets equal the oracle's, and a launch with the retired
+    MSPA_PAIR_WORD_STRIPES bit runs the same kernel and gives the same arrays; 30 adversarial pairs against the exact kernel."""
     hw, dhw = (968, 1296), (480, 640)
     lib = _lib.load()
     assert lib.mspa_pair_correspondences_workspace_bytes(1000, 480, 640, 968, 1296, _lib.PAIR_FAST) == 0
@@ -138,11 +138,11 @@ def test_rect_kernel_at_scannet_shape():
         assert np.array_equal(i.cpu().numpy(), nz) and np.array_equal(xi.cpu().numpy(), ref["xi"][nz])
         assert np.array_equal(yi.cpu().numpy(), ref["yi"][nz])
     for sname in ("corr", "minimal"):
-        wob, kw = launch(depth, mats, None, pairs, hw, SETS[sname], _lib.PAIR_FAST | _lib.PAIR_WORD_STRIPES)
+        ign, ki = launch(depth, mats, None, pairs, hw, SETS[sname], _lib.PAIR_FAST | _lib.PAIR_WORD_STRIPES)
         rect, kr = launch(depth, mats, None, pairs, hw, SETS[sname], _lib.PAIR_FAST)
-        assert kw == _lib.KERNEL_PAIR_FAST_SCALED and kr == _lib.KERNEL_PAIR_FAST_RECT
+        assert ki == _lib.KERNEL_PAIR_FAST_RECT and kr == _lib.KERNEL_PAIR_FAST_RECT
         for k in SETS[sname]:
-            assert np.array_equal(wob[k], rect[k]), k
+            assert np.array_equal(ign[k], rect[k]), k
         for n, ref in enumerate(refs):
             check_integers(rect, n, ref, hw)
     # adversarial poses against the exact kernel

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""ScanNet's own shape (1296x968 colour over 640x480 depth), one process, interleaved rounds: the wobbling-stripe kernel
-(correspondence / minimal sets, MSPA_PAIR_WORD_STRIPES), the rectangular-tile kernel on the same sets (the default) and the fused compacted
-set (rectangular tiles), ms per 1 000 pairs -- the rectangular-tile legs once per library (tools/ab/libmspa_*.so + in-tree).
+"""ScanNet's own shape (1296x968 colour over 640x480 depth), one process, interleaved rounds: the rectangular-tile kernel's
+correspondence / minimal sets and its fused compacted set, ms per 1 000 pairs -- once per library (tools/ab/libmspa_*.so +
+in-tree).  (Rounds 2-3's word-stripe kernel, which the recorded runs in profiles/ compare against, was removed.)
     python tools/ab_scannet.py [--pairs 200] [--steps 20] [--rounds 3]"""
 import argparse
 import os
@@ -74,9 +74,6 @@ def main():
         legs["corr:rect" + tag] = (h, "corr", F)
         legs["minimal:rect" + tag] = (h, "minimal", F)
         legs["compact:rect" + tag] = (h, "compact", F)
-    h0 = handles[list(handles)[-1]]
-    legs["corr:wobble"] = (h0, "corr", F | _lib.PAIR_WORD_STRIPES)
-    legs["minimal:wobble"] = (h0, "minimal", F | _lib.PAIR_WORD_STRIPES)
     if a.legs:
         legs = {k: v for k, v in legs.items() if any(t in k for t in a.legs.split(","))}
     for k in list(legs):                     # an older library may not take a set at this shape (rc != 0): drop the leg
