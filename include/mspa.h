@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 200            /* 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 210            /* 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -593,6 +593,36 @@ int64_t mspa_png_encode_capacity(int32_t h, int32_t w);
 int64_t mspa_png_encode_workspace_bytes(int64_t n, int32_t h, int32_t w);
 int mspa_png_encode_device(const int16_t *depth_dev, int64_t n, int32_t h, int32_t w, uint8_t *out_dev, int64_t out_pitch,
                            int64_t *nbytes_dev, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Image resizing ON THE DEVICE (csrc/resize.hip, arithmetic in csrc/resize_core.h): n 8-bit RGB images of one shape resampled
+ * to one target shape, bit-identical to Pillow's `Image.resize((W, H), resample)` for resample = BILINEAR (filter 2) and
+ * BICUBIC (filter 3, Pillow's default): float64 weights per axis turned into 22-bit fixed point, a horizontal pass rounded to
+ * 8 bits, then a vertical pass; a pass whose size does not change is skipped.  A g++ build of resize_core.h is the reference.
+ *
+ * mspa_resize_coeffs_host  the tables of one axis of `in` samples resampled to `out` (host pointers only): bounds = [out, 2]
+ *   int32 (first tap, tap count), coeffs = [out, *ksize] int32 (zero past the tap count), *ksize = taps per row.  With bounds
+ *   and coeffs both null only *ksize is written (a sizing call); coeffs alone may be null.  1 <= in, out <= 65535.  A table
+ *   with a row whose sum of |coefficient| would let the 32-bit accumulator wrap returns MSPA_EUNSUPPORTED (none does for a
+ *   factor within 1/8 .. 8).
+ * mspa_resize_workspace_bytes  bytes of scratch a resize of n images of h x w to H x W needs (0 when at most one pass runs);
+ *   -1 for a bad argument.
+ * mspa_resize_rgb_device  src_dev + k * src_image_pitch + y * src_row_pitch = row y of image k ([w, 3] uint8; pitches in
+ *   bytes, any alignment) -> dst_dev = [n_images, H, W, 3] uint8, contiguous.  The four tables are DEVICE copies of what
+ *   mspa_resize_coeffs_host gives for (w, W, filter) and (h, H, filter); the tables of a pass that does not run may be null.
+ *   The kernels clamp every table entry to the data they hold, so a damaged table gives wrong pixels, never a wild access.
+ *   workspace: caller-owned, 16-byte aligned, >= mspa_resize_workspace_bytes (may be null when that is 0); contents
+ *   undefined afterwards.  n_images = 0 returns MSPA_OK and enqueues nothing; sizes outside 1..65535, more than 65535 images,
+ *   a null pointer, a pitch smaller than a row or a bad filter return MSPA_EINVAL.  A per-axis factor below 1/8 or above 8
+ *   returns MSPA_EUNSUPPORTED (there Pillow's pass order is not the one restated here); inside that range nothing is
+ *   declined.  Only enqueues on `stream`.
+ */
+int mspa_resize_coeffs_host(int32_t in, int32_t out, int32_t filter, int32_t *bounds, int32_t *coeffs, int32_t *ksize);
+int64_t mspa_resize_workspace_bytes(int64_t n_images, int32_t h, int32_t w, int32_t H, int32_t W);
+int mspa_resize_rgb_device(const uint8_t *src_dev, int64_t n_images, int32_t h, int32_t w, int64_t src_row_pitch,
+                           int64_t src_image_pitch, uint8_t *dst_dev, int32_t H, int32_t W, int32_t filter,
+                           const int32_t *bounds_x_dev, const int32_t *coeffs_x_dev, const int32_t *bounds_y_dev,
+                           const int32_t *coeffs_y_dev, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * K4 -- per-pair camera relations: the distance / yaw / pitch columns of CFR.process_scene's pair

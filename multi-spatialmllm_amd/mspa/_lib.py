@@ -17,6 +17,7 @@ PAIR_STREAM = 2
 PAIR_WORD_STRIPES = 0x200      # retired: accepted and ignored (the word-stripe kernel it selected was removed)
 CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
 JPEG_DESC_BYTES = 4224
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
 
@@ -107,6 +108,10 @@ _SIGNATURES = {
     "mspa_png_encode_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "mspa_png_encode_device": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                        c_void_p]),
+    "mspa_resize_coeffs_host": (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, POINTER(c_int32)]),
+    "mspa_resize_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "mspa_resize_rgb_device": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mspa_draw_spans_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "mspa_blend_masks_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "mspa_check_visibility": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,

@@ -81,7 +81,11 @@ def draw_filled_circle(image, center: Tuple[int, int], radius: int, color) -> No
 
 class PillowAnnotator:
     """Draw marks on ``src`` and save to ``dst`` (JPEG).  Colours arrive in upstream's channel order (BGR) and are
-    flipped for Pillow's RGB canvas, so the saved picture shows what OpenCV would have shown."""
+    flipped for Pillow's RGB canvas, so the saved picture shows what OpenCV would have shown.  ``output_size`` = (H, W): the
+    painted picture is resized (``Image.resize``, bicubic) before it is saved, e.g. to the training shape (968, 1296)."""
+
+    def __init__(self, output_size: Optional[Tuple[int, int]] = None):
+        self.output_size = (int(output_size[0]), int(output_size[1])) if output_size else None
 
     def annotate(self, src: str, dst: str, marks: Sequence[Mark]):
         from PIL import Image, ImageDraw
@@ -98,6 +102,8 @@ class PillowAnnotator:
             if m.label:
                 rgb = (m.color[2], m.color[1], m.color[0])
                 draw.text((m.x + m.label_offset[0], m.y + m.label_offset[1] - 22), m.label, fill=rgb, font=self._font())
+        if self.output_size:
+            im = im.resize((self.output_size[1], self.output_size[0]))
         im.save(dst, quality=95)
 
     def copy(self, src: str, dst: str):
@@ -219,11 +225,14 @@ class DeviceAnnotator:
     source of a pending job, first flush the queue, and a destination leaves the frame cache.  Paths are compared as given.
     ``flush()`` finishes every pending job (errors raise); ``pending(dst)`` says whether ``dst`` is queued.  A context manager
     flushes on exit.  Device memory: one batch's distinct frames, their per-job copies in chunks of ``ENCODE_CHUNK``, and
-    ``cache_frames`` frames of their own (copied out of the decode batch, so a cached frame never keeps a batch alive)."""
+    ``cache_frames`` frames of their own (copied out of the decode batch, so a cached frame never keeps a batch alive).
+    ``output_size`` = (H, W): painted frames are resized (``engine.resize_rgb_device``, bicubic, bit-identical to Pillow's
+    ``Image.resize``) before the encode, as ``PillowAnnotator(output_size)`` does; copies stay copies."""
 
     ENCODE_CHUNK = 128                      # images per encode call: bounds the device output buffer and workspace
 
-    def __init__(self, batch_size: int = 1024, cache_frames: int = 256, device="cuda", n_threads: Optional[int] = None):
+    def __init__(self, batch_size: int = 1024, cache_frames: int = 256, device="cuda", n_threads: Optional[int] = None,
+                 output_size: Optional[Tuple[int, int]] = None):
         from collections import OrderedDict
         from . import hostinfo
         self.batch_size = max(1, int(batch_size))
@@ -234,7 +243,8 @@ class DeviceAnnotator:
         self._reads = {}                    # src -> number of pending jobs that read it
         self._frames = OrderedDict()        # src -> [H, W, 3] uint8 device tensor (LRU)
         self._labels = LabelMasks()
-        self._host = PillowAnnotator()
+        self.output_size = (int(output_size[0]), int(output_size[1])) if output_size else None
+        self._host = PillowAnnotator(self.output_size)
 
     def __enter__(self):
         return self
@@ -349,6 +359,8 @@ class DeviceAnnotator:
                 if labels:
                     engine.blend_masks_device(canvas, torch.from_numpy(np.array(labels, dtype=np.int64)).to(dev),
                                               torch.from_numpy(np.concatenate(masks)).to(dev))
+                if self.output_size:
+                    canvas = engine.resize_rgb_device(canvas, self.output_size)
                 out, nbytes = engine.jpeg_encode_device(canvas, quality=95, subsampling="4:2:0")
                 nb = nbytes.cpu().numpy()
                 host = out[:, :int(nb.max())].cpu().numpy()

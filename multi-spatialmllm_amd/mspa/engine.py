@@ -399,6 +399,102 @@ def blend_masks_device(images: torch.Tensor, labels: torch.Tensor, masks: torch.
                                                    n, H, W, _stream_ptr()))
 
 
+RESIZE_FILTERS = {"bilinear": _lib.RESIZE_BILINEAR, "bicubic": _lib.RESIZE_BICUBIC}
+_RESIZE_TABLES: Dict[tuple, tuple] = {}
+
+
+def _resize_filter(resample) -> int:
+    if isinstance(resample, str):
+        _require(resample.lower() in RESIZE_FILTERS, f"resample: one of {sorted(RESIZE_FILTERS)}")
+        return RESIZE_FILTERS[resample.lower()]
+    _require(int(resample) in RESIZE_FILTERS.values(), "resample: 2 (bilinear) or 3 (bicubic), Pillow's numbers")
+    return int(resample)
+
+
+def resize_coeffs_host(n_in: int, n_out: int, resample="bicubic") -> Tuple[np.ndarray, np.ndarray]:
+    """(bounds [n_out, 2] int32, coeffs [n_out, ksize] int32): Pillow's fixed-point resampling table of one axis
+    (mspa_resize_coeffs_host)."""
+    lib = _lib.load()
+    f = _resize_filter(resample)
+    ksize = ctypes.c_int32(0)
+    _lib.check(lib.mspa_resize_coeffs_host(int(n_in), int(n_out), f, None, None, ctypes.byref(ksize)))
+    bounds = np.zeros((int(n_out), 2), dtype=np.int32)
+    coeffs = np.zeros((int(n_out), ksize.value), dtype=np.int32)
+    _lib.check(lib.mspa_resize_coeffs_host(int(n_in), int(n_out), f, bounds.ctypes.data, coeffs.ctypes.data, ctypes.byref(ksize)))
+    return bounds, coeffs
+
+
+def _resize_tables(n_in: int, n_out: int, f: int, device) -> tuple:
+    """The device copy of one axis's tables, built once per (in, out, filter, device)."""
+    device = torch.device(device)
+    key = (n_in, n_out, f, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        bounds, coeffs = resize_coeffs_host(n_in, n_out, f)
+        if len(_RESIZE_TABLES) >= 64:                   # a tree of many shapes: forget the oldest
+            _RESIZE_TABLES.pop(next(iter(_RESIZE_TABLES)))
+        hit = _RESIZE_TABLES[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(coeffs).to(device))
+    return hit
+
+
+def resize_rgb_pillow(frames: np.ndarray, hw: Tuple[int, int], resample="bicubic") -> np.ndarray:
+    """The definition: Pillow's ``Image.resize`` of each [h, w, 3] uint8 frame of ``frames`` to ``hw`` = (H, W), on the host."""
+    from PIL import Image
+    f = _resize_filter(resample)
+    H, W = int(hw[0]), int(hw[1])
+    out = np.empty((len(frames), H, W, 3), dtype=np.uint8)
+    for k, img in enumerate(frames):
+        out[k] = np.asarray(Image.fromarray(np.ascontiguousarray(img)).resize((W, H), f))
+    return out
+
+
+def resize_rgb_device(frames: torch.Tensor, hw: Tuple[int, int], resample="bicubic", out: Optional[torch.Tensor] = None,
+                      fallback: bool = True) -> torch.Tensor:
+    """[n, h, w, 3] uint8 RGB on the device -> [n, H, W, 3] uint8 with ``hw`` = (H, W): bit for bit Pillow's
+    ``Image.fromarray(frames[k]).resize((W, H), resample)`` for ``resample`` "bicubic" (Pillow's default) or "bilinear"
+    (mspa_resize_rgb_device).  ``frames`` may be a strided view as long as a pixel's three bytes and a row's pixels are adjacent
+    (rows and images may be padded).  A per-axis factor outside 1/8 .. 8 is declined by the kernels: with ``fallback`` Pillow
+    resizes those frames on the host (download, resize, upload), without it ``MspaError`` (code MSPA_EUNSUPPORTED) is raised.
+    Only enqueues on the current stream otherwise."""
+    _require_gpu()
+    _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3,
+             "frames: an [n, h, w, 3] uint8 device tensor")
+    n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    H, W = int(hw[0]), int(hw[1])
+    _require(1 <= h <= 65535 and 1 <= w <= 65535 and 1 <= H <= 65535 and 1 <= W <= 65535, "1 <= h, w, H, W <= 65535")
+    _require(n <= 65535, "at most 65 535 images in one call")
+    f = _resize_filter(resample)
+    st = frames.stride()
+    if n and not (st[3] == 1 and st[2] == 3 and st[1] >= 3 * w and (n == 1 or st[0] >= (h - 1) * st[1] + 3 * w)):
+        frames = frames.contiguous()
+        st = frames.stride()
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
+    _require(out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, H, W, 3),
+             "out: a contiguous [n, H, W, 3] uint8 device tensor")
+    if n == 0:
+        return out
+    lib = _lib.load()
+    bx = kx = by = ky = None
+    try:
+        if w != W:
+            bx, kx = _resize_tables(w, W, f, frames.device)
+        if h != H:
+            by, ky = _resize_tables(h, H, f, frames.device)
+        ws_bytes = int(lib.mspa_resize_workspace_bytes(n, h, w, H, W))
+        work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=frames.device).view(torch.uint8) if ws_bytes else None
+        image_pitch = int(st[0]) if n > 1 else h * int(st[1])      # a single image's stride(0) means nothing
+        _lib.check(lib.mspa_resize_rgb_device(frames.data_ptr(), n, h, w, int(st[1]), image_pitch,
+                                              _ptr(out), H, W, f, _ptr(bx), _ptr(kx), _ptr(by), _ptr(ky),
+                                              work.data_ptr() if work is not None else None, int(work.numel()) if work is not None else 0,
+                                              _stream_ptr()))
+    except _lib.MspaError as e:
+        if e.code != _lib.MSPA_EUNSUPPORTED or not fallback:
+            raise
+        out.copy_(torch.from_numpy(resize_rgb_pillow(frames.cpu().numpy(), (H, W), f)).to(out.device))
+    return out
+
+
 def _require_pinhole(mats: torch.Tensor):
     """MSPA_PAIR_FAST reads the camera-2 depth off the third image row: K's third row must be 0 0 1 0 in EVERY frame record
     (include/mspa.h).  The records live on the device, so the check is one read-back of all frames' rows the first time a
