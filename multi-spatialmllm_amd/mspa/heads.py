@@ -164,19 +164,17 @@ def camera_movement_dataset(rows: Sequence, frame_pose, image_hw_of, question_ty
     With a communicator (``ctx``: one process per GPU) the TEXT is built in parallel: every rank makes the draws of all rows
     (``camera_movement_draw``: the generator ends where a single process leaves it, on every rank), formats a contiguous
     slice of the rows -- its own K4 launch, its own image-size lookups, ``transform`` (e.g. the eval form) applied -- and
-    the finished JSON lines go to rank 0 through ONE ``shard.gather_bytes``.  Rank 0 gets the records as ``JsonLine``s in
+    the finished JSON lines go to rank 0 through ONE ``shard.gather_json_lines``.  Rank 0 gets the records as ``JsonLine``s in
     row order, the other ranks an empty list.  Without one the records are returned as dicts, as before.
     """
-    import torch
-    from . import engine
+    from . import shard
     n = len(rows)
     if n == 0:
         return []
-    rank, world = (ctx.rank, ctx.world) if ctx is not None else (0, 1)
     draws = None
     if ctx is not None:                                        # all rows, every rank: ~4 generator calls per row
         draws = [camera_movement_draw(r, question_type, templates, rng) for r in rows]
-    lo, hi = (0, n) if ctx is None else _partition(n, world, rank)
+    lo, hi = (0, n) if ctx is None else shard.partition(n, ctx.world, ctx.rank)
     failure: Optional[BaseException] = None
     mine: List[dict] = []
     try:
@@ -189,12 +187,9 @@ def camera_movement_dataset(rows: Sequence, frame_pose, image_hw_of, question_ty
         failure = e
     if ctx is None:
         return mine
-    from . import shard
     shard.raise_together(ctx, failure, "camera_movement_dataset")
-    parts = shard.gather_bytes("".join(json.dumps(rec) + "\n" for rec in mine).encode(), ctx, dst=0)
-    if rank != 0:
-        return []
-    return [JsonLine(line) for p in parts for line in bytes(p).split(b"\n")[:-1]]
+    lines = shard.gather_json_lines(enumerate(mine, lo), n, ctx)
+    return lines if ctx.rank == 0 else []
 
 
 def _camera_movement_slice(rows, lo, hi, frame_pose, image_hw_of, question_type, templates, rng, device, draws) -> List[dict]:
@@ -225,12 +220,6 @@ def _camera_movement_slice(rows, lo, hi, frame_pose, image_hw_of, question_type,
     return [camera_movement_record(rows[k], k, question_type, out[k - lo, 3:6], out[m + k - lo, 3:6],
                                    image_hw_of(rows[k]["scene_id"], rows[k]["image_id1"]), templates, rng,
                                    draw=None if draws is None else draws[k]) for k in range(lo, hi)]
-
-
-def _partition(n_items: int, world: int, rank: int) -> Tuple[int, int]:
-    base, rem = divmod(n_items, world)
-    start = rank * base + min(rank, rem)
-    return start, start + base + (1 if rank < rem else 0)
 
 
 # --------------------------------------------------------------------------------------------
@@ -342,50 +331,59 @@ def visual_correspondence_records(scene, rows: Sequence[dict], image_hw, start_i
     return records
 
 
-@quietly
-def visual_correspondence_dataset(rows: Sequence, get_scene, get_bits=None, templates: T.TemplateSet = T.VISUAL_CORRESPONDENCE,
-                                  rng=_random, max_points_per_pair: int = 1, on_warn=None, ctx=None,
-                                  transform=None) -> List[Optional[dict]]:
-    """The record loop of VC_C.build_train_dataset (VC_C:424-429) for rows that may span many scenes.
+# --------------------------------------------------------------------------------------------
+# the row loop of the two correspondence heads
+# --------------------------------------------------------------------------------------------
+STRIDE = 1024       # rows between two checkpoints of the generator: a rewind replays the draws of at most that many rows
+NONE = 1 << 62      # "no row of mine" in the dot head's all_reduce(MIN): above every row << 32 | x << 16 | y
 
-    Pass 1 (per scene, GPU): size of the common visible set of every row (K2 on the scene's bitsets).
-    Pass 2 (host, global row order): every draw of VC_C.build_training_sample -- they depend on those sizes only.
-    Pass 3 (per scene, GPU): the drawn positions -> vertices (K6a) -> both projections + visibility re-check (K6b).
-    Returns one entry per row in row order, None where upstream returns None (no common vertex / unknown scene).
-    Upstream draws no template for a vertex that fails the re-check (VC_C:327-338; only possible when the visibility index
-    is stale): such a row is found after pass 3, the generator is rewound to it (checkpoints every 1024 rows) and the
-    passes resume with that slot marked -- as in ``visual_correspondence_dot_dataset``.
 
-    ``get_scene(scene_id)`` -> resident ``SceneOnDevice`` (or None if the scene is unknown) and ``get_bits(scene_id, scene)``
-    -> [F, n_words] bitsets in ``scene.ids`` order (default: K1 on the resident scene); or pass a ready backend
-    (``GpuCorrespondenceBackend``-like object) as ``get_scene``.
+def _in_drawn_order(row, swap: bool) -> Tuple[str, str]:
+    """(first image, second image) of a row after its swap coin."""
+    return (row["image_id2"], row["image_id1"]) if swap else (row["image_id1"], row["image_id2"])
+
+
+def _rank0_only(on_warn, ctx):
+    """The warning file is rank 0's: ``on_warn`` there (and without a communicator), a no-op on the other ranks."""
+    if on_warn is None or (ctx is not None and ctx.rank != 0):
+        return lambda message: None
+    return on_warn
+
+
+def _correspondence_rows(what: str, rows: Sequence, backend, rng, warn, ctx, transform, share_image_size: bool,
+                         draw, positions, first_invalid, emit) -> List:
+    """The record loop both correspondence heads run over rows that may span many scenes; ``what`` names the head in errors.
+
+    Pass 1 (per scene, GPU): ``backend.common_counts`` -- the size of the common visible set of every row (K2).
+    Pass 2 (host, global row order): every draw of upstream's build_training_sample, ``draw(k, size, image_hw, mark)``.
+    ``size`` is None for a row whose scene the backend does not know; ``mark`` is what an earlier round learnt about the row
+    (below), None at first.  The draws depend on the sizes and on ``mark`` only.
+    Pass 3 (per scene, GPU): ``backend.project`` for ``positions(d)`` of every drawn row -- vertices (K6a), both projections
+    and the visibility re-check (K6b).  A row's results are a list, one ``(vertex, uv1, uv2, ok1, ok2)`` per position.
+    Then ``first_invalid(start, draws, proj, marks)`` names the first row whose draws rest on an assumption the projections
+    refute, as ``(row, mark)`` or None, and ``emit(k, d, results, size, image_hw)`` (results None for a row of another rank)
+    writes the warnings and returns the record, or None, of every row in front of it.  The generator is then taken back to
+    the start of that row (replayed from a checkpoint kept every ``STRIDE`` rows), the row gets its mark and the passes resume
+    there.  Where the refuted assumption is a failed re-check (a stale visibility index: upstream warns and draws no further
+    for that vertex) the warning lines are written here.  Such rows are rare, so this is one round in practice.
 
     With a communicator (``ctx``: one process per GPU) the SCENES are dealt over the ranks (longest-first by their number of
     rows): a rank reads, uploads and runs passes 1 and 3 only for its own scenes; the sizes of pass 1 are summed over the ranks
-    (one all_reduce of an int64 [rows, 2] table: every row has exactly one owner), pass 2 -- all draws, microseconds per row --
-    runs identically on every rank (so the generator ends where a single process leaves it), each rank builds the records of its
-    scenes' rows (``transform`` applied) and ONE ``shard.gather_bytes`` brings the JSON lines to rank 0, which returns them in
-    row order as ``JsonLine``s (None where upstream returns None); the other ranks return a list of Nones.  A stale visibility
-    index (a drawn vertex fails the re-check: the rewind below) is a single-process affair and raises here.
+    (one all_reduce of an int64 [rows, 2] table, [rows, 4] with the image sizes when the draws need them: every row has
+    exactly one owner); pass 2 -- microseconds per row -- runs identically on every rank, so the generator ends where a single
+    process leaves it; each rank builds the records of its scenes' rows (``transform`` applied) and ONE
+    ``shard.gather_json_lines`` brings them to rank 0, which returns them in row order as ``JsonLine``s (None where upstream
+    returns None); the other ranks return a list of Nones.  A rank-local failure reaches every rank before the next
+    collective (``shard.raise_together`` after pass 1 and after the rounds).  A failed re-check is a single-process affair:
+    the rank that owns the row raises.
     """
-    backend = get_scene if hasattr(get_scene, "project") else GpuCorrespondenceBackend(get_scene, get_bits)
-    warn = on_warn or (lambda message: None)
+    from . import shard
     by_scene: Dict[str, List[int]] = {}
     for k, r in enumerate(rows):
         by_scene.setdefault(r["scene_id"], []).append(k)
     n = len(rows)
-    rank, world = (ctx.rank, ctx.world) if ctx is not None else (0, 1)
-    if ctx is not None:
-        from . import shard
-        names = list(by_scene)
-        bins = shard.lpt_assign([float(len(by_scene[s])) for s in names], world)
-        mine = {names[i] for i in bins[rank]}
-        if rank != 0:
-            warn = lambda message: None                                    # the warning file is rank 0's
-    else:
-        mine = set(by_scene)
-    n_common = [0] * n
-    known = [False] * n
+    mine = shard.lpt_mine({s: len(ks) for s, ks in by_scene.items()}, ctx)
+    size: List[Optional[int]] = [None] * n
     hw: Dict[str, Tuple[int, int]] = {}
     failure: Optional[BaseException] = None
     try:
@@ -397,100 +395,78 @@ def visual_correspondence_dataset(rows: Sequence, get_scene, get_bits=None, temp
                 continue
             hw[scene_id] = backend.image_hw(scene_id)
             for k, c in zip(ks, counts):
-                known[k], n_common[k] = True, c
+                size[k] = c
     except Exception as e:                                                 # a rank-local failure (a missing frame, a backend
         if ctx is None:                                                    # error) must reach EVERY rank before the collective
             raise
         failure = e
     if ctx is not None:
-        from . import shard
-        shard.raise_together(ctx, failure, "visual_correspondence_dataset (pass 1)")
-    if ctx is not None and n:
         import torch
         import torch.distributed as dist
-        table = torch.tensor([[int(kn), int(c)] for kn, c in zip(known, n_common)], dtype=torch.int64, device=ctx.collective_device)
-        dist.all_reduce(table, op=dist.ReduceOp.SUM, group=ctx.group)
-        table = table.cpu().numpy()
-        known, n_common = [bool(v) for v in table[:, 0]], [int(v) for v in table[:, 1]]
+        shard.raise_together(ctx, failure, f"{what} (pass 1)")
+        if n:
+            table = [[int(c is not None), int(c or 0)] for c in size]
+            if share_image_size:                                           # (H, W) of the rows whose scene is known
+                table = [t + list(hw[rows[k]["scene_id"]] if t[0] else (0, 0)) for k, t in enumerate(table)]
+            table = torch.tensor(table, dtype=torch.int64, device=ctx.collective_device)
+            dist.all_reduce(table, op=dist.ReduceOp.SUM, group=ctx.group)
+            table = table.cpu().numpy()
+            size = [int(t[1]) if t[0] else None for t in table]
+            if share_image_size:
+                for k, t in enumerate(table):
+                    if t[0]:
+                        hw.setdefault(rows[k]["scene_id"], (int(t[2]), int(t[3])))
 
-    hidden: Dict[int, set] = {}                                            # row -> slots whose vertex failed the re-check
+    marks: Dict[int, object] = {}                                          # row -> what a refuted round learnt about it
     out: List[Optional[dict]] = [None] * n
-    STRIDE = 1024
-
-    def draw(k):
-        if not known[k]:
-            rng.random()                                                   # the swap coin comes before the scene check (VC_C:280)
-            return None
-        return visual_correspondence_draws([rows[k]], [n_common[k]], templates, rng, max_points_per_pair, [hidden.get(k)])[0]
-
+    image_hw = [hw.get(r["scene_id"]) for r in rows]
     try:
         start = 0
         while start < n:
             draws: Dict[int, Optional[dict]] = {}
             checkpoints: Dict[int, tuple] = {}
-            for k in range(start, n):                                          # pass 2
+            for k in range(start, n):                                      # pass 2
                 if (k - start) % STRIDE == 0:
                     checkpoints[k] = rng.getstate()
-                draws[k] = draw(k)
+                draws[k] = draw(k, size[k], image_hw[k], marks.get(k))
             proj: Dict[int, list] = {}
-            for scene_id, ks in by_scene.items():                              # pass 3
+            for scene_id, ks in by_scene.items():                          # pass 3
                 if scene_id not in mine:
                     continue
-                live = [k for k in ks if k >= start and draws[k] is not None]
-                if not live:
-                    continue
                 jobs, owner = [], []
-                for k in live:
-                    r, d = rows[k], draws[k]
-                    i1, i2 = (r["image_id2"], r["image_id1"]) if d["swap"] else (r["image_id1"], r["image_id2"])
-                    for j in d["positions"]:
-                        jobs.append((i1, i2, j))
-                        owner.append(k)
+                for k in ks:
+                    drawn = positions(draws[k]) if k >= start else ()
+                    if drawn:
+                        i1, i2 = _in_drawn_order(rows[k], draws[k]["swap"])
+                        jobs += [(i1, i2, j) for j in drawn]
+                        owner += [k] * len(drawn)
+                if not jobs:
+                    continue
                 for k, res in zip(owner, backend.project(scene_id, jobs)):
                     proj.setdefault(k, []).append(res)
-            redo = None
-            for k in range(start, n):                                          # records, until a row needs its draws corrected
-                r, d = rows[k], draws[k]
-                if d is None:
-                    if not known[k]:
-                        warn(f"[build_training_sample] Warning: Visibility info not found for scene {r['scene_id']}\n")
-                    else:
-                        warn(f"[build_training_sample] Warning: No common visible points for scene {r['scene_id']} "
-                             f"{r['image_id1']}, {r['image_id2']}\n")
-                    continue
-                image1, image2 = (r["image_id2"], r["image_id1"]) if d["swap"] else (r["image_id1"], r["image_id2"])
-                if r["scene_id"] not in mine:                                  # another rank's row: its record arrives as bytes;
-                    if all(p is None for p in d["picks"]):                     # its warning line is rank 0's to write (the picks
-                        warn(f"[build_training_sample] Warning: No conversation for scene {r['scene_id']} {image1}, {image2}\n")
-                    continue                                                   # come from the replicated draws: known here)
-                bad = {s for s, (_, _, _, ok1, ok2) in enumerate(proj[k]) if not (ok1 and ok2)}
-                if bad - hidden.get(k, set()):
-                    if ctx is not None:
-                        raise RuntimeError(f"visual_correspondence_dataset: vertex {proj[k][min(bad)][0]} of scene {r['scene_id']} failed the "
-                                           "visibility re-check (a visibility index that does not belong to these frames); the rewind that "
-                                           "reproduces upstream's draws for such rows runs in a single process only")
-                    for s in sorted(bad):
-                        vertex, _, _, ok1, ok2 = proj[k][s]
-                        if not ok1:
-                            warn(f"Warning: Point {vertex} is not visible in image {image1} in scene {r['scene_id']}.\n")
-                        if not ok2:
-                            warn(f"Warning: Point {vertex} is not visible in image {image2} in scene {r['scene_id']}.\n")
-                    redo = (k, bad)
-                    break
-                if all(p is None for p in d["picks"]):                         # VC_C:373-378
-                    warn(f"[build_training_sample] Warning: No conversation for scene {r['scene_id']} {image1}, {image2}\n")
-                    continue
-                uv1 = np.stack([res[1] for res in proj[k]])
-                uv2 = np.stack([res[2] for res in proj[k]])
-                out[k] = visual_correspondence_record(r, k, d, uv1, uv2, hw[r["scene_id"]], templates)
-            if redo is None:
+            first = first_invalid(start, draws, proj, marks)               # nothing is written before the ranks agree on it
+            for k in range(start, n if first is None else first[0]):
+                out[k] = emit(k, draws[k], proj.get(k), size[k], image_hw[k])
+            if first is None:
                 break
-            k, bad = redo                                                      # take the generator back to the start of row k
-            base = max(c for c in checkpoints if c <= k)
+            k, mark = first
+            r = rows[k]
+            failed = [(vertex, ok1, ok2) for vertex, _, _, ok1, ok2 in proj.get(k, ()) if not (ok1 and ok2)]
+            if failed and ctx is not None:
+                raise RuntimeError(f"{what}: vertex {failed[0][0]} of scene {r['scene_id']} failed the visibility re-check (a "
+                                   "visibility index that does not belong to these frames); the rewind that reproduces upstream's "
+                                   "draws for such rows runs in a single process only")
+            image1, image2 = _in_drawn_order(r, draws[k]["swap"])
+            for vertex, ok1, ok2 in failed:
+                if not ok1:
+                    warn(f"Warning: Point {vertex} is not visible in image {image1} in scene {r['scene_id']}.\n")
+                if not ok2:
+                    warn(f"Warning: Point {vertex} is not visible in image {image2} in scene {r['scene_id']}.\n")
+            base = max(c for c in checkpoints if c <= k)                   # take the generator back to the start of row k
             rng.setstate(checkpoints[base])
             for j in range(base, k):
-                draw(j)
-            hidden[k] = set(bad)
+                draw(j, size[j], image_hw[j], marks.get(j))
+            marks[k] = mark
             start = k
         if transform is not None:
             out = [None if rec is None else transform(rec) for rec in out]
@@ -500,17 +476,67 @@ def visual_correspondence_dataset(rows: Sequence, get_scene, get_bits=None, temp
         failure = e
     if ctx is None:
         return out
-    from . import shard
-    shard.raise_together(ctx, failure, "visual_correspondence_dataset (passes 2-3)")
-    lines = "".join(f"{k}\t{json.dumps(rec)}\n" for k, rec in enumerate(out) if rec is not None).encode()
-    parts = shard.gather_bytes(lines, ctx, dst=0)
-    merged: List[Optional[dict]] = [None] * n
-    if rank == 0:
-        for p in parts:
-            for line in bytes(p).split(b"\n")[:-1]:
-                k, _, body = line.partition(b"\t")
-                merged[int(k)] = JsonLine(body)
-    return merged
+    shard.raise_together(ctx, failure, f"{what} (passes 2-3)")
+    return shard.gather_json_lines(((k, rec) for k, rec in enumerate(out) if rec is not None), n, ctx)
+
+
+@quietly
+def visual_correspondence_dataset(rows: Sequence, get_scene, get_bits=None, templates: T.TemplateSet = T.VISUAL_CORRESPONDENCE,
+                                  rng=_random, max_points_per_pair: int = 1, on_warn=None, ctx=None,
+                                  transform=None) -> List[Optional[dict]]:
+    """The record loop of VC_C.build_train_dataset (VC_C:424-429) for rows that may span many scenes: the passes, the rewind and
+    the sharded form (``ctx``, ``transform``) are ``_correspondence_rows``'s.
+    Returns one entry per row in row order, None where upstream returns None (no common vertex / unknown scene).
+    Upstream draws no template for a vertex that fails the re-check (VC_C:327-338; only possible when the visibility index
+    is stale): such a row is found after pass 3 and redrawn with that slot marked.
+
+    ``get_scene(scene_id)`` -> resident ``SceneOnDevice`` (or None if the scene is unknown) and ``get_bits(scene_id, scene)``
+    -> [F, n_words] bitsets in ``scene.ids`` order (default: K1 on the resident scene); or pass a ready backend
+    (``GpuCorrespondenceBackend``-like object) as ``get_scene``.
+
+    With a communicator the ranks exchange nothing about a failed re-check: the stale-index error of the owner reaches the
+    other ranks through the failure vote.
+    """
+    backend = get_scene if hasattr(get_scene, "project") else GpuCorrespondenceBackend(get_scene, get_bits)
+    warn = _rank0_only(on_warn, ctx)
+
+    def draw(k, size, image_hw, hidden):                                   # hidden: slots whose vertex failed the re-check
+        if size is None:
+            rng.random()                                                   # the swap coin comes before the scene check (VC_C:280)
+            return None
+        return visual_correspondence_draws([rows[k]], [size], templates, rng, max_points_per_pair, [hidden])[0]
+
+    def positions(d):
+        return () if d is None else d["positions"]
+
+    def first_invalid(start, draws, proj, hidden):
+        for k in range(start, len(rows)):
+            bad = {s for s, (_, _, _, ok1, ok2) in enumerate(proj.get(k, ())) if not (ok1 and ok2)}
+            if bad - hidden.get(k, set()):
+                return k, bad
+        return None
+
+    def emit(k, d, results, size, image_hw):
+        r = rows[k]
+        if d is None:
+            if size is None:
+                warn(f"[build_training_sample] Warning: Visibility info not found for scene {r['scene_id']}\n")
+            else:
+                warn(f"[build_training_sample] Warning: No common visible points for scene {r['scene_id']} "
+                     f"{r['image_id1']}, {r['image_id2']}\n")
+            return None
+        if results is None:                                                # another rank's row: its record arrives as bytes
+            return None
+        if all(p is None for p in d["picks"]):                             # VC_C:373-378
+            image1, image2 = _in_drawn_order(r, d["swap"])
+            warn(f"[build_training_sample] Warning: No conversation for scene {r['scene_id']} {image1}, {image2}\n")
+            return None
+        uv1 = np.stack([res[1] for res in results])
+        uv2 = np.stack([res[2] for res in results])
+        return visual_correspondence_record(r, k, d, uv1, uv2, image_hw, templates)
+
+    return _correspondence_rows("visual_correspondence_dataset", rows, backend, rng, warn, ctx, transform, False,
+                                draw, positions, first_invalid, emit)
 
 
 def _vc_dot_row_draws(n_common: int, known: bool, image_hw, templates: T.TemplateSet, rng, correct_point=None):
@@ -594,206 +620,96 @@ class GpuCorrespondenceBackend:
 def visual_correspondence_dot_dataset(rows: Sequence, backend, templates: T.TemplateSet = None, rng=_random, on_warn=None,
                                       on_mark=None, ctx=None, transform=None) -> List[Optional[dict]]:
     """Record loop of the multiple-choice correspondence head (visual_correspondence_qa_engine_dot_2_multichoice.py
-    :279-433, VC_D) for rows that may span scenes.  ``backend``: ``GpuCorrespondenceBackend`` (or anything with its
-    three methods).
+    :279-433, VC_D) for rows that may span scenes: the passes, the rewind and the sharded form (``ctx``, ``transform``) are
+    ``_correspondence_rows``'s.  ``backend``: ``GpuCorrespondenceBackend`` (or anything with its three methods).
 
-    Pass 1 (per scene): sizes of the common visible sets.  Pass 2 (host, global row order): every draw.  Pass 3 (per
-    scene): drawn positions -> vertices -> projections.  Upstream rejects a random distractor that coincides with the
-    correct pixel (VC_D:366) -- a draw that depends on the projection.  The draws are made assuming no such coincidence
-    and checked afterwards; at the first row where one did occur the generator is taken back to that row (replayed from
-    a checkpoint kept every 1024 rows), the row is redrawn with the rejection applied, and the passes resume behind it.
+    Upstream rejects a random distractor that coincides with the correct pixel (VC_D:366) -- a draw that depends on the
+    projection.  The draws are made assuming no such coincidence and checked afterwards; at the first row where one did occur
+    the row is redrawn with the rejection applied.
     ``on_mark(row_index, scene_id, first_image, second_image, vertex, p1_pixel, colour1, labelled_points, colours)``.
 
-    With a communicator (``ctx``: one process per GPU) the SCENES are dealt over the ranks (longest-first by rows), as in
-    ``visual_correspondence_dataset``: passes 1 and 3, the records and -- the expensive part of this head -- the two annotated
-    JPEGs per record (``on_mark``) only for a rank's own scenes; the sizes of pass 1 summed over the ranks; all draws on every
-    rank.  A coincidence is expected a handful of times in the 500 K-row train set, so it is handled, not refused: the ranks
-    agree on the FIRST row where one occurred (one all_reduce(MIN) of row << 32 | x << 16 | y), every rank rewinds to it with the
-    owner's pixel, and records and images are only produced for rows in front of it -- the files of a sharded run are those of
-    one process.  The finished JSON lines (``transform`` applied) travel to rank 0 in one ``shard.gather_bytes``; the other
-    ranks get Nones.  Only a stale visibility index (a drawn vertex that fails the depth test) stays a one-process affair."""
+    With a communicator the expensive part of this head -- the two annotated JPEGs per record (``on_mark``) -- is made only for
+    a rank's own scenes.  A coincidence is expected a handful of times in the 500 K-row train set, so it is handled, not
+    refused: the ranks agree on the FIRST row where one occurred (one all_reduce(MIN) of row << 32 | x << 16 | y per round),
+    every rank rewinds to it with the owner's pixel, and records and images are only produced for rows in front of it -- the
+    files of a sharded run are those of one process.  Only a stale visibility index (a drawn vertex that fails the depth test)
+    stays a one-process affair."""
     templates = templates or T.VISUAL_CORRESPONDENCE_DOT
-    warn = on_warn or (lambda message: None)
-    by_scene: Dict[str, List[int]] = {}
-    for k, r in enumerate(rows):
-        by_scene.setdefault(r["scene_id"], []).append(k)
-    n = len(rows)
-    rank, world = (ctx.rank, ctx.world) if ctx is not None else (0, 1)
-    if ctx is not None:
-        from . import shard
-        names = list(by_scene)
-        bins = shard.lpt_assign([float(len(by_scene[s_])) for s_ in names], world)
-        mine = {names[i] for i in bins[rank]}
-        if rank != 0:
-            warn = lambda message: None                                    # noqa: E731 -- the warning file is rank 0's
-    else:
-        mine = set(by_scene)
-    n_common = [0] * n
-    known = [False] * n
-    hw: Dict[str, Tuple[int, int]] = {}
-    failure: Optional[BaseException] = None
-    try:
-        for scene_id, ks in by_scene.items():                              # pass 1
-            if scene_id not in mine:
+    warn = _rank0_only(on_warn, ctx)
+
+    def draw(k, size, image_hw, forced):                                   # forced: the correct pixel where the rejection applies
+        return _vc_dot_row_draws(size or 0, size is not None, image_hw, templates, rng, forced)
+
+    def positions(d):
+        return () if d["dead"] else (d["pos"],)
+
+    def first_invalid(start, draws, proj, forced):
+        local = NONE                                                       # the first row (of mine) that refutes its draws
+        for k in range(start, len(rows)):
+            if k not in proj:
                 continue
-            counts = backend.common_counts(scene_id, [(rows[k]["image_id1"], rows[k]["image_id2"]) for k in ks])
-            if counts is None:
-                continue
-            hw[scene_id] = backend.image_hw(scene_id)
-            for k, c in zip(ks, counts):
-                known[k], n_common[k] = True, c
-    except Exception as e:
-        if ctx is None:
-            raise
-        failure = e
-    if ctx is not None:
-        import torch
-        import torch.distributed as dist
-        shard.raise_together(ctx, failure, "visual_correspondence_dot_dataset (pass 1)")
-        if n:
-            # known, size, and the image size the distractors are drawn inside (H, W): every row has exactly one owner
-            table = torch.tensor([[int(kn), int(c), hw.get(rows[k]["scene_id"], (0, 0))[0] if kn else 0,
-                                   hw.get(rows[k]["scene_id"], (0, 0))[1] if kn else 0]
-                                  for k, (kn, c) in enumerate(zip(known, n_common))], dtype=torch.int64, device=ctx.collective_device)
-            dist.all_reduce(table, op=dist.ReduceOp.SUM, group=ctx.group)
-            table = table.cpu().numpy()
-            known, n_common = [bool(v) for v in table[:, 0]], [int(v) for v in table[:, 1]]
-            for k in range(n):
-                if known[k]:
-                    hw.setdefault(rows[k]["scene_id"], (int(table[k, 2]), int(table[k, 3])))
-
-    out: List[Optional[dict]] = [None] * n
-    start = 0
-    forced: Dict[int, Tuple[int, int]] = {}                                # row -> correct pixel where the rejection applies
-    STRIDE = 1024
-    NONE = (1 << 62)
-
-    def draw(k):
-        return _vc_dot_row_draws(n_common[k], known[k], hw.get(rows[k]["scene_id"], (0, 0)), templates, rng, forced.get(k))
-
-    try:
-        while start < n:
-            draws: Dict[int, dict] = {}
-            checkpoints: Dict[int, tuple] = {}
-            for k in range(start, n):                                      # pass 2
-                if (k - start) % STRIDE == 0:
-                    checkpoints[k] = rng.getstate()
-                draws[k] = draw(k)
-            proj: Dict[int, tuple] = {}
-            for scene_id, ks in by_scene.items():                          # pass 3
-                if scene_id not in mine:
-                    continue
-                live = [k for k in ks if k >= start and not draws[k]["dead"]]
-                if not live:
-                    continue
-                jobs = []
-                for k in live:
-                    r, d = rows[k], draws[k]
-                    i1, i2 = (r["image_id2"], r["image_id1"]) if d["swap"] else (r["image_id1"], r["image_id2"])
-                    jobs.append((i1, i2, d["pos"]))
-                for k, res in zip(live, backend.project(scene_id, jobs)):
-                    proj[k] = res
-            # the first row (of mine) where the assumption behind the draws fails; nothing is written before the ranks agree
-            local = NONE
-            for k in range(start, n):
-                if k not in proj:
-                    continue
-                vertex, uv1, uv2, ok1, ok2 = proj[k]
-                if not (ok1 and ok2):
-                    local = (k << 32) | (0xFFFF << 16) | 0xFFFF
-                    break
-                correct = (int(uv2[0]), int(uv2[1]))
-                if k not in forced and correct in draws[k]["wrong"]:
-                    local = (k << 32) | ((correct[0] & 0xFFFF) << 16) | (correct[1] & 0xFFFF)
-                    break
-            first = local
-            if ctx is not None:
-                import torch
-                import torch.distributed as dist
-                t = torch.tensor([local], dtype=torch.int64, device=ctx.collective_device)
-                dist.all_reduce(t, op=dist.ReduceOp.MIN, group=ctx.group)
-                first = int(t.item())
-            stop = n if first == NONE else first >> 32
-            clash = None
-            if first != NONE:
-                cx, cy = (first >> 16) & 0xFFFF, first & 0xFFFF
-                clash = (stop, "invisible" if (cx, cy) == (0xFFFF, 0xFFFF) else (cx, cy))
-            for k in range(start, min(n, stop + (1 if clash and clash[1] == "invisible" else 0))):     # records in front of it
-                r, d = rows[k], draws[k]
-                image1, image2 = (r["image_id2"], r["image_id1"]) if d["swap"] else (r["image_id1"], r["image_id2"])
-                if d["dead"]:
-                    if d.get("invisible"):
-                        pass                                               # warned when the failure was found
-                    elif not known[k]:
-                        warn(f"[build_training_sample] Warning: Visibility info not found for scene {r['scene_id']}\n")
-                    else:
-                        warn(f"[build_training_sample] Warning: No common visible points for scene {r['scene_id']} {image1}, {image2}\n")
-                    continue
-                if k not in proj:                                          # another rank's row: its record arrives as bytes
-                    continue
-                vertex, uv1, uv2, ok1, ok2 = proj[k]
-                if not (ok1 and ok2):
-                    # the index and the depth test disagree (a stale visibility file): upstream warns and returns before any
-                    # further draw (VC_D:339-351) -- rewind to this row and redraw it that way
-                    if ctx is not None:
-                        raise RuntimeError(f"visual_correspondence_dot_dataset: vertex {vertex} of scene {r['scene_id']} failed the "
-                                           "visibility re-check (a visibility index that does not belong to these frames); the rewind "
-                                           "that reproduces upstream's draws for such rows runs in a single process only")
-                    if not ok1:
-                        warn(f"Warning: Point {vertex} is not visible in image {image1} in scene {r['scene_id']}.\n")
-                    if not ok2:
-                        warn(f"Warning: Point {vertex} is not visible in image {image2} in scene {r['scene_id']}.\n")
-                    break
-                correct = (int(uv2[0]), int(uv2[1]))
-                H, W = hw[r["scene_id"]]
-                points = [correct] + d["wrong"]
-                labeled = dict(zip(d["labels"], [points[j] for j in d["order"]]))
-                correct_label = [lab for lab, p in labeled.items() if p == correct][0]
-                ti, qi, ai = d["picks"]
-                p1_pixel = (int(uv1[0]), int(uv1[1]))
-                if on_mark is not None:
-                    on_mark(k, r["scene_id"], image1, image2, vertex, p1_pixel, d["color1"], labeled,
-                            {lab: d["colors"][j] for j, lab in enumerate(d["labels"])})
-                out[k] = {
-                    "id": f"{k}_p{vertex}",
-                    "image": [os.path.join(r["scene_id"], f"{k}_point{vertex}_{image1}_{image2}_img1.jpg"),
-                              os.path.join(r["scene_id"], f"{k}_point{vertex}_{image1}_{image2}_img2.jpg")],
-                    "conversations": [{"from": "human", "value": f"{templates.task_description[ti]}\n{templates.questions['default'][qi]}"},
-                                      {"from": "gpt", "value": templates.answers["default"][ai].format(correct_label=correct_label)}],
-                    "height_list": [H] * 2,
-                    "width_list": [W] * 2,
-                    "question_type": "visual_correspondence_multiple_choice",
-                    "gt_value": correct_label,
-                    "p1_list": [p1_pixel[0], p1_pixel[1]],
-                    "p2_list": [correct] + d["wrong"],
-                }
-            if clash is None:
+            _, _, uv2, ok1, ok2 = proj[k][0]
+            if not (ok1 and ok2):
+                local = (k << 32) | (0xFFFF << 16) | 0xFFFF
                 break
-            k, correct = clash                                             # take the generator back to the start of row k
-            base = max(c for c in checkpoints if c <= k)
-            rng.setstate(checkpoints[base])
-            for j in range(base, k):
-                draw(j)
-            forced[k] = correct
-            start = k
-        if transform is not None:
-            out = [None if rec is None else transform(rec) for rec in out]
-    except Exception as e:
-        if ctx is None:
-            raise
-        failure = e
-    if ctx is None:
-        return out
-    shard.raise_together(ctx, failure, "visual_correspondence_dot_dataset (passes 2-3)")
-    lines = "".join(f"{k}\t{json.dumps(rec)}\n" for k, rec in enumerate(out) if rec is not None).encode()
-    parts = shard.gather_bytes(lines, ctx, dst=0)
-    merged: List[Optional[dict]] = [None] * n
-    if rank == 0:
-        for p in parts:
-            for line in bytes(p).split(b"\n")[:-1]:
-                k, _, body = line.partition(b"\t")
-                merged[int(k)] = JsonLine(body)
-    return merged
+            correct = (int(uv2[0]), int(uv2[1]))
+            if k not in forced and correct in draws[k]["wrong"]:
+                local = (k << 32) | ((correct[0] & 0xFFFF) << 16) | (correct[1] & 0xFFFF)
+                break
+        first = local
+        if ctx is not None:
+            import torch
+            import torch.distributed as dist
+            t = torch.tensor([local], dtype=torch.int64, device=ctx.collective_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN, group=ctx.group)
+            first = int(t.item())
+        if first == NONE:
+            return None
+        cx, cy = (first >> 16) & 0xFFFF, first & 0xFFFF
+        # the index and the depth test disagree (a stale visibility file): upstream warns and returns before any further draw
+        # (VC_D:339-351) -- the row is redrawn that way
+        return first >> 32, "invisible" if (cx, cy) == (0xFFFF, 0xFFFF) else (cx, cy)
+
+    def emit(k, d, results, size, image_hw):
+        r = rows[k]
+        image1, image2 = _in_drawn_order(r, d["swap"])
+        if d["dead"]:
+            if d.get("invisible"):
+                pass                                                       # warned when the failure was found
+            elif size is None:
+                warn(f"[build_training_sample] Warning: Visibility info not found for scene {r['scene_id']}\n")
+            else:
+                warn(f"[build_training_sample] Warning: No common visible points for scene {r['scene_id']} {image1}, {image2}\n")
+            return None
+        if results is None:                                                # another rank's row: its record arrives as bytes
+            return None
+        vertex, uv1, uv2, _, _ = results[0]
+        correct = (int(uv2[0]), int(uv2[1]))
+        H, W = image_hw
+        points = [correct] + d["wrong"]
+        labeled = dict(zip(d["labels"], [points[j] for j in d["order"]]))
+        correct_label = [lab for lab, p in labeled.items() if p == correct][0]
+        ti, qi, ai = d["picks"]
+        p1_pixel = (int(uv1[0]), int(uv1[1]))
+        if on_mark is not None:
+            on_mark(k, r["scene_id"], image1, image2, vertex, p1_pixel, d["color1"], labeled,
+                    {lab: d["colors"][j] for j, lab in enumerate(d["labels"])})
+        return {
+            "id": f"{k}_p{vertex}",
+            "image": [os.path.join(r["scene_id"], f"{k}_point{vertex}_{image1}_{image2}_img1.jpg"),
+                      os.path.join(r["scene_id"], f"{k}_point{vertex}_{image1}_{image2}_img2.jpg")],
+            "conversations": [{"from": "human", "value": f"{templates.task_description[ti]}\n{templates.questions['default'][qi]}"},
+                              {"from": "gpt", "value": templates.answers["default"][ai].format(correct_label=correct_label)}],
+            "height_list": [H] * 2,
+            "width_list": [W] * 2,
+            "question_type": "visual_correspondence_multiple_choice",
+            "gt_value": correct_label,
+            "p1_list": [p1_pixel[0], p1_pixel[1]],
+            "p2_list": [correct] + d["wrong"],
+        }
+
+    return _correspondence_rows("visual_correspondence_dot_dataset", rows, backend, rng, warn, ctx, transform, True,
+                                draw, positions, first_invalid, emit)
 
 
 # --------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import dataclasses
 import datetime
+import json
 import os
 from typing import List, Sequence, Tuple
 
@@ -94,6 +95,15 @@ def lpt_assign(costs: Sequence[float], world: int, rank0_share: float = 1.0) -> 
     for b in bins:
         b.sort()
     return bins
+
+
+def lpt_mine(costs: dict, ctx: "DistContext | None") -> set:
+    """The named groups (name -> cost, e.g. a scene and its number of rows) that fall to this rank when all of them are dealt
+    longest-first (``lpt_assign``: every rank computes the same deal); with no communicator all of them."""
+    names = list(costs)
+    if ctx is None:
+        return set(names)
+    return {names[i] for i in lpt_assign([float(costs[s]) for s in names], ctx.world)[ctx.rank]}
 
 
 def scene_cost(n_frames: int, n_points: int) -> float:
@@ -180,6 +190,21 @@ def gather_bytes(payload, ctx: DistContext, dst: int = 0):
     if ctx.rank != dst:
         return None
     return [parts[r][:c].cpu().numpy() for r, c in enumerate(counts)]
+
+
+def gather_json_lines(indexed, n: int, ctx: DistContext, dst: int = 0) -> list:
+    """``(index, record)`` pairs of every rank -> on rank ``dst`` a list of ``n`` entries with every record at its index as a
+    ``heads.JsonLine`` (the owner's ``json.dumps``, not parsed again) and None where no rank had one; ``n`` Nones on the other
+    ranks.  ONE ``gather_bytes`` of ``"{index}\t{json}\n"`` lines: json.dumps escapes tabs and newlines, so both split cleanly."""
+    parts = gather_bytes("".join(f"{k}\t{json.dumps(rec)}\n" for k, rec in indexed).encode(), ctx, dst=dst)
+    placed = [None] * n
+    if ctx.rank == dst:
+        from .heads import JsonLine
+        for p in parts:
+            for line in bytes(p).split(b"\n")[:-1]:
+                k, _, body = line.partition(b"\t")
+                placed[int(k)] = JsonLine(body)
+    return placed
 
 
 def raise_together(ctx: "DistContext | None", failure: "BaseException | None", what: str = "a sharded step"):

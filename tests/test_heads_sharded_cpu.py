@@ -1,7 +1,8 @@
 """The sharded form of the multiple-choice correspondence builder (heads.visual_correspondence_dot_dataset with a communicator)
 against the one-process form, on two gloo ranks with a synthetic numeric backend: same records, same marks, same generator
 state at the end -- including a row whose random distractor lands on the correct pixel (the ranks agree on the first such row
-and rewind together; VC_D:366)."""
+and rewind together; VC_D:366).  The coordinate builder (heads.visual_correspondence_dataset) the same way: same JSON bytes,
+warning lines and generator state; a vertex that fails the re-check is rewound by one process and refused by two."""
 import json
 import os
 import random
@@ -24,9 +25,9 @@ N_ROWS = 60
 class Backend:
     """Deterministic numbers in place of K2 / K6: sizes and projections are functions of (scene, images, position)."""
 
-    def __init__(self, clash_row=None, clash_pixel=None, rows=None):
+    def __init__(self, clash_row=None, clash_pixel=None, rows=None, stale_row=None):
         self.calls = []
-        self.clash_row, self.clash_pixel, self.rows = clash_row, clash_pixel, rows
+        self.clash_row, self.clash_pixel, self.rows, self.stale_row = clash_row, clash_pixel, rows, stale_row
 
     def image_hw(self, scene_id):
         return (H, W)
@@ -40,14 +41,18 @@ class Backend:
     def project(self, scene_id, jobs):
         self.calls.append(("project", scene_id))
         out = []
+        stale = None if self.stale_row is None else self.rows[self.stale_row]
         for a, b, pos in jobs:
+            ok2 = True
+            if stale is not None and stale["scene_id"] == scene_id and {a, b} == {stale["image_id1"], stale["image_id2"]}:
+                ok2, stale = False, None                       # a stale index: ONE vertex of that row fails the re-check
             h = hash_int(scene_id, a, b, pos)
             uv2 = (float(h % (W - 20)), float((h // 1000) % (H - 20)))
             if self.clash_row is not None:
                 r = self.rows[self.clash_row]
                 if r["scene_id"] == scene_id and {a, b} == {r["image_id1"], r["image_id2"]}:
                     uv2 = (float(self.clash_pixel[0]), float(self.clash_pixel[1]))
-            out.append((pos * 3 + 1, (float((h // 7) % W), float((h // 11) % H)), uv2, True, True))
+            out.append((pos * 3 + 1, (float((h // 7) % W), float((h // 11) % H)), uv2, True, ok2))
         return out
 
 
@@ -129,6 +134,79 @@ def test_dot_dataset_two_ranks_equals_one_process_with_and_without_a_rewind():
         assert sorted(res[0][1] + res[1][1]) == sorted(want_marks) and res[0][1] and res[1][1]      # every image drawn once, by its owner
         assert res[0][2] == want_state == res[1][2]                # the generator ends where one process leaves it, on every rank
         assert not (set(res[0][3]) & set(res[1][3])) and len(set(res[0][3]) | set(res[1][3])) == 5   # scenes are dealt, not shared
+
+
+# ---- the coordinate head: no collective for a failed re-check, so two ranks refuse what one process rewinds --------------
+def _coor_run(rows, max_points_per_pair, stale_row, ctx=None):
+    warned = []
+    rng = random.Random(9)
+    be = Backend(rows=rows, stale_row=stale_row)
+    try:
+        out = heads.visual_correspondence_dataset(rows, be, rng=rng, max_points_per_pair=max_points_per_pair,
+                                                  on_warn=warned.append, ctx=ctx)
+    except RuntimeError as e:
+        return {"raised": str(e)}
+    if ctx is not None:
+        assert all(r is None or isinstance(r, heads.JsonLine) for r in out)
+        out = [None if r is None else bytes(r) for r in out]
+    return {"out": out, "warned": warned, "state": rng.getstate(), "scenes": sorted({s for _, s in be.calls})}
+
+
+def _coor_cases(rows):
+    """(max_points_per_pair, stale_row): one and several points per pair, then a row (one with a record) whose first vertex
+    fails the re-check."""
+    out = _coor_run(rows, 2, None)["out"]
+    live = [k for k, r in enumerate(out) if r is not None]
+    return [(1, None), (3, None), (2, live[len(live) // 2])]
+
+
+def _coor_rank_main(rank, world, port, q):
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      MSPA_DIST_BACKEND="gloo")
+    ctx = shard.context_from_env(torch.device("cpu"))
+    rows = _rows()
+    q.put((rank, [_coor_run(rows, mpp, stale_row, ctx) for mpp, stale_row in _coor_cases(rows)]))
+    ctx.barrier()
+    ctx.close()
+
+
+def test_coordinate_dataset_two_ranks_equals_one_process_and_refuses_a_stale_index():
+    import torch.multiprocessing as mp
+    rows = _rows()
+    assert len({r["scene_id"] for r in rows}) >= 3
+    cases = _coor_cases(rows)
+    mpc = mp.get_context("spawn")
+    q = mpc.Queue()
+    port = _free_port()
+    procs = [mpc.Process(target=_coor_rank_main, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=120) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for n, (mpp, stale_row) in enumerate(cases):
+        want = _coor_run(rows, mpp, stale_row)
+        got0, got1 = res[0][n], res[1][n]
+        text = "".join(want["warned"])
+        assert sum(r is not None for r in want["out"]) >= 20
+        assert "Visibility info not found" in text and "No common visible points" in text
+        if stale_row is None:
+            assert all(len(r["p1_list"]) == mpp for r in want["out"] if r is not None)
+            assert got0["out"] == [None if r is None else json.dumps(r).encode() for r in want["out"]]   # rank 0: the same bytes
+            assert all(r is None for r in got1["out"]) and len(got1["out"]) == len(rows)
+            assert got0["state"] == want["state"] == got1["state"]     # the generator ends where one process leaves it
+            assert got0["warned"] == want["warned"] and got1["warned"] == []           # the warning file is rank 0's
+            assert got0["scenes"] and got1["scenes"] and not (set(got0["scenes"]) & set(got1["scenes"]))
+            assert len(set(got0["scenes"]) | set(got1["scenes"])) == 5                 # scenes are dealt, not shared
+        else:
+            # one process: the row keeps its other point, the failed one is warned about and draws no template
+            assert len(want["out"][stale_row]["p1_list"]) == mpp - 1 and text.count("is not visible in image") == 1
+            assert want["state"] != _coor_run(rows, mpp, None)["state"]
+            # two ranks: the owner raises the stale-index error, the other rank learns of it in the failure vote
+            said = sorted((g["raised"] for g in (got0, got1)), key=lambda text: "another rank failed" in text)
+            assert "failed the visibility re-check" in said[0] and "single process only" in said[0]
+            assert "failed the visibility re-check" not in said[1] and "another rank failed" in said[1]
 
 
 # ---- the chained build of the depth-comparison engines (draws depend on the numerics) ------------------------------------
