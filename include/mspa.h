@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 210            /* 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 220            /* 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -688,11 +688,38 @@ int mspa_track_pair_distances(const double *world, int32_t T, int32_t P, const i
 /*
  * K7 -- the accumulation inside rigid_body_segmentation (OM_C:49-92): cumulative_loss[i, j] = sum over
  * frames t >= 1 of |d_t(i,j) - d_{t-1}(i,j)| where that change exceeds smoothing_factor, d_t the Euclidean
- * distance between track points i and j at frame t.  The linkage / fcluster step stays with SciPy on the
- * host.   tracks_xyz [T, P, 3] f64 -> out_loss [P, P] f64 (symmetric, zero diagonal)
+ * distance between track points i and j at frame t.  The linkage / fcluster step that consumes it is
+ * mspa_track_linkage below.   tracks_xyz [T, P, 3] f64 -> out_loss [P, P] f64 (symmetric, zero diagonal)
+ * The batch form runs n_blocks equal-shape track blocks in one launch: tracks_xyz [n_blocks, T, P, 3] ->
+ * out_loss [n_blocks, P, P], each block's matrix the one the single form writes.  n_blocks <= 65 535.
  */
 int mspa_track_rigidity_loss(const double *tracks_xyz, int32_t T, int32_t P, double smoothing_factor,
                              double *out_loss, mspa_stream_t stream);
+int mspa_track_rigidity_loss_batch(const double *tracks_xyz, int32_t n_blocks, int32_t T, int32_t P,
+                                   double smoothing_factor, double *out_loss, mspa_stream_t stream);
+
+/*
+ * K7b -- the second half of rigid_body_segmentation (OM_C:80-92) for a batch of K7 matrices: SciPy's
+ * linkage(squareform(loss, checks=False), method='average') (the nearest-neighbour chain, its tie rules, its
+ * stable sort by height and its union-find relabelling) and fcluster(Z, threshold, criterion='distance'),
+ * one workgroup per block.  Only the strict upper triangle of a block is read, as squareform does.
+ *   loss [n_blocks, P, P] f64 (left untouched)  ->  out_Z [n_blocks, P-1, 4] f64, bit for bit SciPy's;
+ *   out_labels [n_blocks, P] i32, value for value fcluster's;  out_status [n_blocks] i32:
+ *   MSPA_LINKAGE_OK, MSPA_LINKAGE_NONFINITE (a NaN / inf in the block: SciPy raises ValueError there) or
+ *   MSPA_LINKAGE_ITERATION_CAP (the chain loop reached 4 P scans: a bug indicator, never a normal outcome).
+ *   A block whose status is not 0 has zeros in out_Z and out_labels; the other blocks are unaffected.
+ * 2 <= P <= MSPA_LINKAGE_MAX_POINTS; P < 2 or n_blocks == 0 returns MSPA_OK with nothing written.
+ * workspace: caller-owned, 16-byte aligned, >= mspa_track_linkage_workspace_bytes(n_blocks, P) bytes (the
+ * working copy of every matrix; -1 for a bad argument); contents undefined afterwards.
+ */
+#define MSPA_LINKAGE_MAX_POINTS 2048
+#define MSPA_LINKAGE_OK 0
+#define MSPA_LINKAGE_NONFINITE 1
+#define MSPA_LINKAGE_ITERATION_CAP 2
+int64_t mspa_track_linkage_workspace_bytes(int64_t n_blocks, int32_t P);
+int mspa_track_linkage(const double *loss, int64_t n_blocks, int32_t P, double threshold, double *out_Z,
+                       int32_t *out_labels, int32_t *out_status, void *workspace, int64_t workspace_bytes,
+                       mspa_stream_t stream);
 
 /*
  * K8 -- per (object, image) extent of the object's visible vertices: what compute_coverage

@@ -138,11 +138,13 @@ __global__ __launch_bounds__(256) void track_pair_distances_kernel(const double 
 // K7: accumulated pairwise-distance change of the tracks (rigid_body_segmentation, OM_C:49-92): for every
 // point pair (i, j): sum over t >= 1 of |d_t - d_{t-1}| where it exceeds the smoothing threshold, d_t the
 // Euclidean distance of the two points at frame t (scipy pdist: sqrt((dx*dx + dy*dy) + dz*dz)).  One lane
-// per pair walks the frames in order, so the float64 sum has the reference's order.
+// per pair walks the frames in order, so the float64 sum has the reference's order.  blockIdx.y = the track block of a batch.
 __global__ __launch_bounds__(256) void rigidity_loss_kernel(const double *__restrict__ tracks, int T, int P,
                                                             double smoothing, double *__restrict__ loss) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= (int64_t)P * P) return;
+    tracks += (int64_t)blockIdx.y * T * P * 3;
+    loss += (int64_t)blockIdx.y * P * P;
     const int i = (int)(k / P), j = (int)(k % P);
     double acc = 0.0;
     if (i != j) {
@@ -180,16 +182,22 @@ extern "C" int mspa_track_pair_distances(const double *world, int32_t T, int32_t
     return check_hip(hipGetLastError(), "track_pair_distances_kernel launch");
 }
 
-extern "C" int mspa_track_rigidity_loss(const double *tracks_xyz, int32_t T, int32_t P, double smoothing_factor,
-                                        double *out_loss, mspa_stream_t stream) {
-    if (T < 0 || P < 0) return fail(MSPA_EINVAL, "mspa_track_rigidity_loss: bad size");
-    if (P == 0) return MSPA_OK;
+extern "C" int mspa_track_rigidity_loss_batch(const double *tracks_xyz, int32_t n_blocks, int32_t T, int32_t P,
+                                              double smoothing_factor, double *out_loss, mspa_stream_t stream) {
+    if (n_blocks < 0 || T < 0 || P < 0) return fail(MSPA_EINVAL, "mspa_track_rigidity_loss: bad size");
+    if (n_blocks == 0 || P == 0) return MSPA_OK;
     if (!tracks_xyz || !out_loss) return fail(MSPA_EINVAL, "mspa_track_rigidity_loss: null pointer");
     const int64_t blocks = ((int64_t)P * P + 255) / 256;
     if (blocks > 0x7fffffffLL) return fail(MSPA_EINVAL, "mspa_track_rigidity_loss: too many points");
-    hipLaunchKernelGGL(rigidity_loss_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, tracks_xyz, T, P,
-                       smoothing_factor, out_loss);
+    if (n_blocks > 65535) return fail(MSPA_EINVAL, "mspa_track_rigidity_loss: more than 65 535 track blocks in one launch");
+    hipLaunchKernelGGL(rigidity_loss_kernel, dim3((uint32_t)blocks, (uint32_t)n_blocks), dim3(256), 0, (hipStream_t)stream,
+                       tracks_xyz, T, P, smoothing_factor, out_loss);
     return check_hip(hipGetLastError(), "rigidity_loss_kernel launch");
+}
+
+extern "C" int mspa_track_rigidity_loss(const double *tracks_xyz, int32_t T, int32_t P, double smoothing_factor,
+                                        double *out_loss, mspa_stream_t stream) {
+    return mspa_track_rigidity_loss_batch(tracks_xyz, 1, T, P, smoothing_factor, out_loss, stream);
 }
 
 

@@ -8,6 +8,7 @@ the kernels is bit-identical to what the reference would multiply with.
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Dict, Iterable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -975,6 +976,74 @@ def track_rigidity_loss(tracks_xyz: torch.Tensor, smoothing_factor: float = 0.01
     out = torch.empty((P, P), dtype=torch.float64, device=tracks_xyz.device)
     _lib.check(lib.mspa_track_rigidity_loss(_ptr(tracks_xyz), T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
     return out
+
+
+def track_rigidity_loss_batch(tracks_xyz: torch.Tensor, smoothing_factor: float = 0.01) -> torch.Tensor:
+    """Enqueue K7 for equal-shape track blocks in one launch: [B,T,P,3] f64 -> [B,P,P] f64, each the single form's matrix."""
+    _require_gpu()
+    lib = _lib.load()
+    _require(tracks_xyz.dtype == torch.float64 and tracks_xyz.dim() == 4 and tracks_xyz.shape[3] == 3 and tracks_xyz.is_contiguous(), "tracks_xyz: contiguous float64 [B, T, P, 3]")
+    B, T, P, _ = tracks_xyz.shape
+    out = torch.empty((B, P, P), dtype=torch.float64, device=tracks_xyz.device)
+    _lib.check(lib.mspa_track_rigidity_loss_batch(_ptr(tracks_xyz), B, T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
+    return out
+
+
+def linkage_backend() -> str:
+    """Where the object-movement callers run linkage + fcluster: "scipy" (default: on the host, on the downloaded K7 matrix) or
+    "device" (``MSPA_LINKAGE=device``: K7b, identical to SciPy).  Read at every call."""
+    value = os.environ.get("MSPA_LINKAGE", "scipy").strip().lower() or "scipy"
+    if value not in ("scipy", "device"):
+        raise ValueError(f"MSPA_LINKAGE={value!r}: expected 'scipy' or 'device'")
+    return value
+
+
+LINKAGE_NONFINITE_TEXT = "The condensed distance matrix must contain only finite values."      # SciPy's, for status 1
+
+
+def track_linkage(loss: torch.Tensor, threshold: float = 0.1):
+    """Enqueue K7b: SciPy's ``linkage(squareform(loss, checks=False), 'average')`` and ``fcluster(Z, threshold, 'distance')`` of
+    K7 matrices, one workgroup per matrix.  loss [P,P] or [B,P,P] f64 (left untouched) -> (Z [.., P-1, 4] f64 bit for bit SciPy's,
+    labels [.., P] i32, status [..] i32: 0 ok, 1 a non-finite entry (SciPy raises there), 2 iteration cap).  Enqueue only: the
+    status is a device tensor like the rest.  P < 2 has no merge: Z is empty, a single point gets label 1."""
+    _require_gpu()
+    lib = _lib.load()
+    _require(loss.dtype == torch.float64 and loss.dim() in (2, 3) and loss.shape[-1] == loss.shape[-2] and loss.is_contiguous(), "loss: contiguous float64 [P, P] or [B, P, P]")
+    single = loss.dim() == 2
+    B, P = (1 if single else loss.shape[0]), loss.shape[-1]
+    dev = loss.device
+    if P < 2:
+        Z = torch.zeros((B, 0, 4), dtype=torch.float64, device=dev)
+        labels = torch.ones((B, P), dtype=torch.int32, device=dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+    else:
+        Z = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+        labels = torch.empty((B, P), dtype=torch.int32, device=dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        need = lib.mspa_track_linkage_workspace_bytes(B, P)
+        if need < 0:
+            raise _lib.MspaError(_lib.MSPA_EINVAL, f"track_linkage: {P} points, at most {_lib.LINKAGE_MAX_POINTS} are supported")
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.mspa_track_linkage(_ptr(loss), B, P, float(threshold), _ptr(Z), _ptr(labels), _ptr(status), _ptr(ws), need,
+                                          _stream_ptr()))
+    return (Z[0], labels[0], status[0]) if single else (Z, labels, status)
+
+
+def track_rigid_groups(tracks_xyz: torch.Tensor, threshold: float = 0.1, smoothing_factor: float = 0.01):
+    """rigid_body_segmentation (OM_C:49-92) with both halves on the device: K7, then K7b, and only the labels (4 P bytes) and
+    the status come back.  [T,P,3] f64 tracks -> the reference's list of index lists (``np.where(labels == i)`` for i = 1..max).
+    Raises what SciPy raises: ValueError for a non-finite distance and for fewer than two points."""
+    _require(tracks_xyz.dim() == 3, "tracks_xyz.dim() == 3")
+    if tracks_xyz.shape[1] < 2:
+        raise ValueError("The number of observations cannot be determined on an empty distance matrix.")
+    _, labels, status = track_linkage(track_rigidity_loss(tracks_xyz, smoothing_factor), threshold)
+    host = torch.cat([labels, status.reshape(1)]).cpu().numpy()
+    labels, status = host[:-1], int(host[-1])
+    if status == _lib.LINKAGE_NONFINITE:
+        raise ValueError(LINKAGE_NONFINITE_TEXT)
+    if status != _lib.LINKAGE_OK:
+        raise RuntimeError(f"track_linkage: status {status} (iteration cap reached: a bug in the kernel's tie rules)")
+    return [np.where(labels == i)[0].tolist() for i in range(1, int(labels.max()) + 1)]
 
 
 def object_extents(vis_bits: torch.Tensor, xyz: torch.Tensor, obj_offsets: torch.Tensor, obj_vertices: torch.Tensor):

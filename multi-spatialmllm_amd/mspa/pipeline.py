@@ -461,9 +461,13 @@ def run(scenes: Sequence, out_dir: str, ctx: Optional[shard.DistContext] = None,
             outputs: Dict[str, List[dict]] = {}
             xyz = np.ascontiguousarray(tr.tracks_XYZ, dtype=np.float64)
             dev_tracks = torch.from_numpy(xyz).to(device)
-            loss = E.track_rigidity_loss(dev_tracks).cpu().numpy()                                  # K7
-            labels = fcluster(linkage(squareform(loss, checks=False), method="average"), 0.1, criterion="distance")
-            groups = [g for g in (np.where(labels == i)[0].tolist() for i in range(1, max(labels) + 1)) if len(g) > 5]
+            if E.linkage_backend() == "device":
+                all_groups = E.track_rigid_groups(dev_tracks, 0.1)                                  # K7 + K7b
+            else:
+                loss = E.track_rigidity_loss(dev_tracks).cpu().numpy()                              # K7
+                labels = fcluster(linkage(squareform(loss, checks=False), method="average"), 0.1, criterion="distance")
+                all_groups = [np.where(labels == i)[0].tolist() for i in range(1, max(labels) + 1)]
+            groups = [g for g in all_groups if len(g) > 5]
             c2w = torch.from_numpy(np.linalg.inv(tr.extrinsics_w2c).reshape(-1, 16)).to(device)
             world_xyz = E.track_to_world(dev_tracks, c2w, tr.fx_fy_cx_cy, tr.image_hw, ("world",))["world"]       # K5a
             for qt in T.OBJECT_MOVEMENT_TYPES:

@@ -14,10 +14,13 @@ from mspa.hostinfo import quietly
 
 def rigid_body_segmentation(points, threshold=0.1, smoothing_factor=0.01):
     """Groups of track indices that move rigidly together (reference: :49-92): the T x P^2 distance-change
-    accumulation runs on the GPU (K7), average linkage + fcluster stay with SciPy."""
+    accumulation runs on the GPU (K7); average linkage + fcluster run in SciPy on the downloaded matrix, or with
+    ``MSPA_LINKAGE=device`` on the GPU as well (K7b, identical to SciPy), and only the labels come back."""
+    pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).cuda()
+    if engine.linkage_backend() == "device":
+        return engine.track_rigid_groups(pts, threshold, smoothing_factor)
     from scipy.cluster.hierarchy import fcluster, linkage
     from scipy.spatial.distance import squareform
-    pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64)).cuda()
     loss = engine.track_rigidity_loss(pts, smoothing_factor).cpu().numpy()
     links = linkage(squareform(loss), method="average")
     labels = fcluster(links, threshold, criterion="distance")
@@ -105,7 +108,7 @@ class TwoFrameVideoQAEngine:
     # -- scene level (reference: :405-575) ---------------------------------------------------------
     def generate_qa_training_single_scene(self, input_file, npoints_per_group=5, npairs_per_bin=1e8, img_output_dir="",
                                           augment=True, augment_ratio=1.0, _loaded=None):
-        """All records of one TAPVid-3D sample file: frames to ``img_output_dir/<scene>/``, rigid groups (K7 + SciPy),
+        """All records of one TAPVid-3D sample file: frames to ``img_output_dir/<scene>/``, rigid groups (K7 + SciPy, or K7 + K7b),
         frame-pair mining (K5c), records (K5a + K5b).  The JPEG payloads are written as stored -- upstream decodes
         and re-encodes them -- and the image size is read from the first payload's header."""
         scene_id = os.path.splitext(os.path.basename(input_file))[0]
