@@ -8,6 +8,8 @@ the kernels is bit-identical to what the reference would multiply with.
 from __future__ import annotations
 
 import ctypes
+import functools
+import types
 import os
 from typing import Dict, Iterable, Optional, Sequence, Tuple
 
@@ -17,6 +19,7 @@ import torch
 from . import _lib
 
 _AFFINE_ROW = np.array([0.0, 0.0, 0.0, 1.0])
+_DEPTH = (torch.int16, torch.uint16)        # uint16 depth values, stored as int16 (torch has few uint16 ops)
 
 
 def _require(condition: bool, what: str):
@@ -31,15 +34,93 @@ def _require_gpu():
                            "there is no CPU fallback -- the CPU restatement under oracle/ is test-only")
 
 
+def _check(name: str, t, dtypes, shape: tuple, contiguous: bool = True) -> torch.Tensor:
+    """THE check of a tensor argument before it becomes a raw pointer: a device tensor of dtype ``dtypes`` (one, or a tuple of them)
+    whose extents match ``shape`` entry by entry -- k: exactly k, None: any, (k,): at least k (slot buffers are larger than the call's
+    n) -- and contiguous, unless the wrapper hands the strides over.  Reads metadata only: no synchronisation.  Returns ``t``."""
+    if not isinstance(dtypes, tuple):
+        dtypes = (dtypes,)
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.dim() == len(shape) and (t.is_contiguous() or not contiguous):
+        if t.shape == shape:                                                # every entry exact and equal
+            return t
+        for got, e in zip(t.shape, shape):
+            if not (e is None or got == e or (isinstance(e, tuple) and got >= e[0])):
+                break
+        else:                                                               # no entry objected
+            return t
+    _require_gpu()                      # on a machine without one, that is the answer whatever the tensor looks like
+    extents = ", ".join("any" if e is None else f">= {e[0]}" if isinstance(e, tuple) else str(e) for e in shape)
+    got = type(t).__name__
+    if isinstance(t, torch.Tensor):
+        got = f"{str(t.dtype)[6:]} {list(t.shape)} on {t.device}" + ("" if t.is_contiguous() or not contiguous else f", strides {tuple(t.stride())}")
+    raise ValueError(f"mspa.engine: {name}: expected a {'contiguous ' if contiguous else ''}{' / '.join(str(d)[6:] for d in dtypes)} "
+                     f"device tensor [{extents}], got {got}")
+
+
 def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    if t is None:
-        return None
-    _require(t.is_cuda and t.is_contiguous(), "device-resident contiguous tensors only")
-    return t.data_ptr()
+    """The raw pointer (None -> NULL) of a tensor that ``_check`` has passed, or that this module allocated itself."""
+    return None if t is None else t.data_ptr()
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """Scratch of ``nbytes`` rounded up to 16, as uint8, on a 16-byte boundary (allocated as int64 pairs)."""
+    return torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=device).view(torch.uint8)
+
+
+def _check_bits(name: str, bits) -> Tuple[int, int]:
+    """A bitset table, int64 [rows, n_words] (K1's output and everything packed like it) -> (rows, n_words)."""
+    return tuple(_check(name, bits, torch.int64, (None, None)).shape)
+
+
+def _check_images(name: str, images) -> Tuple[int, int, int]:
+    """An image batch, uint8 [n, H, W, 3] -> (n, H, W)."""
+    return tuple(_check(name, images, torch.uint8, (None, None, None, 3)).shape[:3])
+
+
+def _check_streams(offsets, nbytes) -> int:
+    """The ``offsets`` / ``nbytes`` pair that cuts byte streams out of a flat ``src``: int64, one length -> that length."""
+    n = _check("offsets", offsets, torch.int64, (None,)).shape[0]
+    _check("nbytes", nbytes, torch.int64, (n,))
+    return n
+
+
+def _file_rows(n: int, pitch, out, nbytes, device):
+    """The (out [>= n, pitch] uint8, nbytes [>= n] int64) pair the encoders write files into; allocated (``pitch()`` wide) when not given."""
+    if out is None:
+        out = torch.empty((n, pitch()), dtype=torch.uint8, device=device)
+    if nbytes is None:
+        nbytes = torch.empty((n,), dtype=torch.int64, device=device)
+    return _check("out", out, torch.uint8, ((n,), None)), _check("nbytes", nbytes, torch.int64, ((n,),))
+
+
+def _check_pair_inputs(depth, mats, pairs) -> Tuple[int, int, int, int]:
+    """What both K3 wrappers read: depth [F, DH, DW], mats [F, FRAME_MATS, 16] float64, pairs [B, 2] int32 -> (F, DH, DW, B)."""
+    F, DH, DW = _check("depth", depth, _DEPTH, (None, None, None)).shape
+    _check("mats", mats, torch.float64, (F, _lib.FRAME_MATS, 16))
+    return F, DH, DW, _check("pairs", pairs, torch.int32, (None, 2)).shape[0]
+
+
+def _check_outputs(out: Dict[str, torch.Tensor], shapes: dict, required: tuple = ()) -> None:
+    """A caller's ``out`` dict against the table its allocator allocates from (names the table lacks are not read)."""
+    for name in required:
+        if out.get(name) is None:
+            raise ValueError(f"mspa.engine: out[{name!r}]: this output is not optional")
+    for name, t in out.items():                     # once per launch: one comparison per tensor, and _check words a mismatch
+        want = shapes.get(name)
+        if want is not None and t is not None and ((t.shape, t.dtype) != want or not t.is_cuda or not t.is_contiguous()):
+            _check(f"out[{name!r}]", t, want[1], want[0])
+
+
+def _alloc_wanted(want: Iterable[str], shapes: dict, device) -> Dict[str, torch.Tensor]:
+    """The outputs named in ``want``, allocated from ``shapes``; a name the table lacks is an error, not a tensor nothing writes."""
+    want = tuple(want)
+    unknown = [k for k in want if k not in shapes]
+    _require(not unknown, f"want: no output named {unknown}; choose from {tuple(shapes)}")
+    return {k: torch.empty(shape, dtype=dtype, device=device) for k, (shape, dtype) in shapes.items() if k in want}
 
 
 def check_affine(name: str, m: np.ndarray):
@@ -169,18 +250,13 @@ def inflate_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torc
     the per-frame zlib.decompress / cv2.imread of the reference, extract_posed_images.py:49-57, info_handler.py:149-155).
     Returns (out [n, pitch] uint8, status [n] int32): status 0 = inflated to exactly ``block_bytes`` with a matching
     Adler-32; anything else = decode that block on the host.  Only enqueues; read ``status`` after a synchronisation."""
-    _require_gpu()
-    n = int(offsets.shape[0])
-    _require(src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1, "src: a flat uint8 device tensor")
-    _require(offsets.is_cuda and offsets.dtype == torch.int64 and nbytes.is_cuda and nbytes.dtype == torch.int64
-             and nbytes.shape[0] == n, "offsets / nbytes: int64 device tensors of one length")
-    pitch = (int(block_bytes) + 255) // 256 * 256
+    _check("src", src, torch.uint8, (None,))
+    n = _check_streams(offsets, nbytes)
     if out is None:
-        out = torch.empty((n, pitch), dtype=torch.uint8, device=src.device)
-    _require(out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 2 and out.shape[0] >= n
-             and out.shape[1] >= block_bytes and out.shape[1] % 256 == 0, "out: [n, pitch] uint8 with a pitch that is a multiple of 256")
-    if status is None:
-        status = torch.empty((n,), dtype=torch.int32, device=src.device)
+        out = torch.empty((n, (int(block_bytes) + 255) // 256 * 256), dtype=torch.uint8, device=src.device)
+    _check("out", out, torch.uint8, ((n,), (block_bytes,)))
+    _require(out.shape[1] % 256 == 0, f"out: a pitch that is a multiple of 256, got {out.shape[1]}")
+    status = torch.empty((n,), dtype=torch.int32, device=src.device) if status is None else _check("status", status, torch.int32, ((n,),))
     work = torch.empty((max(n, 1),), dtype=torch.int32, device=src.device)
     _lib.check(_lib.load().mspa_inflate_blocks_device(_ptr(src), _ptr(offsets), _ptr(nbytes), int(src.numel()), n, int(block_bytes),
                                                       _ptr(out), int(out.shape[1]), _ptr(status), _ptr(work), _stream_ptr()))
@@ -192,17 +268,11 @@ def png_unfilter_device(raw: torch.Tensor, h: int, w: int, status: torch.Tensor,
     storage of the uint16 depth values, like every depth tensor here): the five PNG row filters undone on the device
     (mspa_png_unfilter_device).  Images with ``status[k] != 0`` are skipped; a filter byte > 4 sets status 3.  ``raw`` starts
     4-byte aligned and its pitch is a multiple of 4 (MspaError otherwise, as from the C ABI)."""
-    _require_gpu()
-    n = int(raw.shape[0])
-    _require(raw.is_cuda and raw.dtype == torch.uint8 and raw.dim() == 2 and raw.is_contiguous()
-             and raw.shape[1] >= h * (2 * w + 1), "raw: [n, pitch] uint8 with pitch >= h * (2 w + 1)")
-    if raw.data_ptr() % 4 or int(raw.shape[1]) % 4:
+    n = _check("raw", raw, torch.uint8, (None, (h * (2 * w + 1),))).shape[0]
+    if _ptr(raw) % 4 or int(raw.shape[1]) % 4:
         raise _lib.MspaError(_lib.MSPA_EINVAL, "png_unfilter_device: raw must start 4-byte aligned, with a pitch that is a multiple of 4")
-    _require(status.is_cuda and status.dtype == torch.int32 and status.shape[0] >= n, "status: int32 [n] on the device")
-    if out is None:
-        out = torch.empty((n, h, w), dtype=torch.int16, device=raw.device)
-    _require(out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and tuple(out.shape[-2:]) == (h, w)
-             and out.shape[0] >= n, "out: [n, h, w] int16 on the device")
+    _check("status", status, torch.int32, ((n,),))
+    out = torch.empty((n, h, w), dtype=torch.int16, device=raw.device) if out is None else _check("out", out, torch.int16, ((n,), h, w))
     _lib.check(_lib.load().mspa_png_unfilter_device(_ptr(raw), int(raw.shape[1]), n, int(h), int(w), _ptr(out), _ptr(status),
                                                     _stream_ptr()))
     return out
@@ -248,30 +318,20 @@ def jpeg_decode_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.T
     uint8) decoded into ``out[k]`` = [H, W, 3] uint8 RGB (mspa_jpeg_decode_device; replaces the per-frame cv2.imread /
     Pillow decode of the colour frames).  Returns (out, status): status 0 = bit-identical to libjpeg-turbo's decode;
     anything else = decode that frame on the host.  Only enqueues; read ``status`` after a synchronisation."""
-    _require_gpu()
-    n = int(offsets.shape[0])
     H, W = int(hw[0]), int(hw[1])
-    _require(H > 0 and W > 0, "hw: a positive (H, W)")
-    _require(src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 1 and src.numel() % 4 == 0,
-             "src: a flat uint8 device tensor, a multiple of 4 bytes long")
-    _require(offsets.is_cuda and offsets.dtype == torch.int64 and nbytes.is_cuda and nbytes.dtype == torch.int64
-             and nbytes.shape[0] == n, "offsets / nbytes: int64 device tensors of one length")
-    _require(descriptors.is_cuda and descriptors.dtype == torch.uint8 and descriptors.is_contiguous()
-             and tuple(descriptors.shape) == (n, _lib.JPEG_DESC_BYTES), "descriptors: [n, JPEG_DESC_BYTES] uint8 on the device")
-    if out is None:
-        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=src.device)
-    _require(out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape[1:]) == (H, W, 3)
-             and out.shape[0] >= n, "out: [n, H, W, 3] uint8 on the device")
-    if status is None:
-        status = torch.empty((n,), dtype=torch.int32, device=src.device)
-    _require(status.is_cuda and status.dtype == torch.int32 and status.shape[0] >= n, "status: int32 [n] on the device")
+    _require(H > 0 and W > 0, f"hw: a positive (H, W), got {(H, W)}")
+    _check("src", src, torch.uint8, (None,))
+    _require(src.numel() % 4 == 0, f"src: a multiple of 4 bytes long, got {src.numel()}")
+    n = _check_streams(offsets, nbytes)
+    _check("descriptors", descriptors, torch.uint8, (n, _lib.JPEG_DESC_BYTES))
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=src.device) if out is None else _check("out", out, torch.uint8, ((n,), H, W, 3))
+    status = torch.empty((n,), dtype=torch.int32, device=src.device) if status is None else _check("status", status, torch.int32, ((n,),))
     if n == 0:
         return out, status
     lib = _lib.load()
-    ws_bytes = int(lib.mspa_jpeg_workspace_bytes(n, H, W))
-    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=src.device).view(torch.uint8)   # 16-byte aligned
+    work = _workspace(int(lib.mspa_jpeg_workspace_bytes(n, H, W)), src.device)
     _lib.check(lib.mspa_jpeg_decode_device(_ptr(src), _ptr(offsets), _ptr(nbytes), int(src.numel()), _ptr(descriptors), n, H, W,
-                                           _ptr(out), _ptr(status), work.data_ptr(), int(work.numel()), _stream_ptr()))
+                                           _ptr(out), _ptr(status), _ptr(work), int(work.numel()), _stream_ptr()))
     return out, status
 
 
@@ -310,29 +370,18 @@ def jpeg_encode_device(rgb: torch.Tensor, quality: int = 95, subsampling="4:2:0"
     subsampling=subsampling)`` writes (mspa_jpeg_encode_device).  The default ``out`` has the worst-case pitch
     (``jpeg_encode_capacity``); with a narrower one, a file longer than the pitch is cut off there and its ``nbytes`` says how
     long it is.  Only enqueues; read ``nbytes`` after a synchronisation."""
-    _require_gpu()
-    _require(rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.dim() == 4 and rgb.shape[3] == 3,
-             "rgb: a contiguous [n, H, W, 3] uint8 device tensor")
-    n, H, W = int(rgb.shape[0]), int(rgb.shape[1]), int(rgb.shape[2])
-    _require(1 <= H <= 65535 and 1 <= W <= 65535, "rgb: 1 <= H, W <= 65535")
-    _require(isinstance(quality, (int, np.integer)) and 1 <= int(quality) <= 100, "quality: an integer in 1..100")
-    _require(n <= 65535, "at most 65 535 images in one call")
+    n, H, W = _check_images("rgb", rgb)
+    _require(1 <= H <= 65535 and 1 <= W <= 65535, f"rgb: 1 <= H, W <= 65535, got {(H, W)}")
+    _require(isinstance(quality, (int, np.integer)) and 1 <= int(quality) <= 100, f"quality: an integer in 1..100, got {quality!r}")
+    _require(n <= 65535, f"rgb: at most 65 535 images in one call, got {n}")
     ss = _subsampling(subsampling)
-    if out is None:
-        out = torch.empty((n, jpeg_encode_capacity((H, W), ss)), dtype=torch.uint8, device=rgb.device)
-    _require(out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] >= n and out.is_contiguous(),
-             "out: a contiguous [n, pitch] uint8 device tensor")
-    if nbytes is None:
-        nbytes = torch.empty((n,), dtype=torch.int64, device=rgb.device)
-    _require(nbytes.is_cuda and nbytes.dtype == torch.int64 and nbytes.is_contiguous() and nbytes.shape[0] >= n,
-             "nbytes: int64 [n] on the device")
+    out, nbytes = _file_rows(n, lambda: jpeg_encode_capacity((H, W), ss), out, nbytes, rgb.device)
     if n == 0:
         return out, nbytes
     lib = _lib.load()
-    ws_bytes = int(lib.mspa_jpeg_encode_workspace_bytes(n, H, W, ss))
-    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=rgb.device).view(torch.uint8)   # 16-byte aligned
+    work = _workspace(int(lib.mspa_jpeg_encode_workspace_bytes(n, H, W, ss)), rgb.device)
     _lib.check(lib.mspa_jpeg_encode_device(_ptr(rgb), n, H, W, int(quality), ss, _ptr(out), int(out.shape[1]),
-                                           _ptr(nbytes), work.data_ptr(), int(work.numel()), _stream_ptr()))
+                                           _ptr(nbytes), _ptr(work), int(work.numel()), _stream_ptr()))
     return out, nbytes
 
 
@@ -349,26 +398,15 @@ def png_encode_device(depth: torch.Tensor, out: Optional[torch.Tensor] = None, n
     the input and whose filtered scanlines are Pillow's (mspa_png_encode_device).  The default ``out`` has the pitch
     ``png_encode_capacity`` rounded up to 4.  Runs on the current torch stream and only enqueues; read ``nbytes`` after a
     synchronisation."""
-    _require_gpu()
-    _require(depth.is_cuda and depth.dtype in (torch.int16, torch.uint16) and depth.is_contiguous() and depth.dim() == 3,
-             "depth: a contiguous [n, H, W] int16 (or uint16) device tensor")
-    n, H, W = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
-    _require(1 <= H <= 8192 and 1 <= W <= 8192, "depth: 1 <= H, W <= 8192")
-    _require(n <= 65535, "at most 65 535 frames in one call")
-    if out is None:
-        out = torch.empty((n, (png_encode_capacity((H, W)) + 3) // 4 * 4), dtype=torch.uint8, device=depth.device)
-    _require(out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] >= n and out.is_contiguous(),
-             "out: a contiguous [n, pitch] uint8 device tensor")
-    if nbytes is None:
-        nbytes = torch.empty((n,), dtype=torch.int64, device=depth.device)
-    _require(nbytes.is_cuda and nbytes.dtype == torch.int64 and nbytes.is_contiguous() and nbytes.shape[0] >= n,
-             "nbytes: int64 [n] on the device")
+    n, H, W = _check("depth", depth, _DEPTH, (None, None, None)).shape
+    _require(1 <= H <= 8192 and 1 <= W <= 8192, f"depth: 1 <= H, W <= 8192, got {(H, W)}")
+    _require(n <= 65535, f"depth: at most 65 535 frames in one call, got {n}")
+    out, nbytes = _file_rows(n, lambda: (png_encode_capacity((H, W)) + 3) // 4 * 4, out, nbytes, depth.device)
     if n == 0:
         return out, nbytes
     lib = _lib.load()
-    ws_bytes = int(lib.mspa_png_encode_workspace_bytes(n, H, W))
-    work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=depth.device).view(torch.uint8)   # 16-byte aligned
-    _lib.check(lib.mspa_png_encode_device(_ptr(depth), n, H, W, _ptr(out), int(out.shape[1]), _ptr(nbytes), work.data_ptr(),
+    work = _workspace(int(lib.mspa_png_encode_workspace_bytes(n, H, W)), depth.device)
+    _lib.check(lib.mspa_png_encode_device(_ptr(depth), n, H, W, _ptr(out), int(out.shape[1]), _ptr(nbytes), _ptr(work),
                                           int(work.numel()), _stream_ptr()))
     return out, nbytes
 
@@ -376,12 +414,8 @@ def png_encode_device(depth: torch.Tensor, out: Optional[torch.Tensor] = None, n
 def draw_spans_device(images: torch.Tensor, spans: torch.Tensor) -> None:
     """Paint int32 span records [S, 5] = (image, y, x0, x1, 0xRRGGBB) into ``images`` ([n, H, W, 3] uint8, in place;
     mspa_draw_spans_device).  Records grouped by (image, y), call order kept inside a group (``annotate.pack_spans``)."""
-    _require_gpu()
-    _require(images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3,
-             "images: a contiguous [n, H, W, 3] uint8 device tensor")
-    _require(spans.is_cuda and spans.dtype == torch.int32 and spans.is_contiguous() and spans.dim() == 2 and spans.shape[1] == 5,
-             "spans: a contiguous [S, 5] int32 device tensor")
-    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    n, H, W = _check_images("images", images)
+    _check("spans", spans, torch.int32, (None, 5))
     _lib.check(_lib.load().mspa_draw_spans_device(_ptr(spans), int(spans.shape[0]), _ptr(images), n, H, W, _stream_ptr()))
 
 
@@ -389,13 +423,9 @@ def blend_masks_device(images: torch.Tensor, labels: torch.Tensor, masks: torch.
     """Blend 8-bit label masks into ``images`` ([n, H, W, 3] uint8, in place) with Pillow's arithmetic
     (mspa_blend_masks_device): int64 records [L, 8] = (image, x, y, mask w, mask h, 0xRRGGBB, offset into ``masks``, 0), grouped
     by image with call order kept inside a group (``annotate.DeviceAnnotator`` packs them)."""
-    _require_gpu()
-    _require(images.is_cuda and images.dtype == torch.uint8 and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3,
-             "images: a contiguous [n, H, W, 3] uint8 device tensor")
-    _require(labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.dim() == 2 and labels.shape[1] == 8,
-             "labels: a contiguous [L, 8] int64 device tensor")
-    _require(masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous() and masks.dim() == 1, "masks: a flat uint8 device tensor")
-    n, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+    n, H, W = _check_images("images", images)
+    _check("labels", labels, torch.int64, (None, 8))
+    _check("masks", masks, torch.uint8, (None,))
     _lib.check(_lib.load().mspa_blend_masks_device(_ptr(labels), int(labels.shape[0]), _ptr(masks), int(masks.numel()), _ptr(images),
                                                    n, H, W, _stream_ptr()))
 
@@ -457,22 +487,16 @@ def resize_rgb_device(frames: torch.Tensor, hw: Tuple[int, int], resample="bicub
     (rows and images may be padded).  A per-axis factor outside 1/8 .. 8 is declined by the kernels: with ``fallback`` Pillow
     resizes those frames on the host (download, resize, upload), without it ``MspaError`` (code MSPA_EUNSUPPORTED) is raised.
     Only enqueues on the current stream otherwise."""
-    _require_gpu()
-    _require(frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3,
-             "frames: an [n, h, w, 3] uint8 device tensor")
-    n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    n, h, w = _check("frames", frames, torch.uint8, (None, None, None, 3), contiguous=False).shape[:3]
     H, W = int(hw[0]), int(hw[1])
-    _require(1 <= h <= 65535 and 1 <= w <= 65535 and 1 <= H <= 65535 and 1 <= W <= 65535, "1 <= h, w, H, W <= 65535")
-    _require(n <= 65535, "at most 65 535 images in one call")
+    _require(1 <= h <= 65535 and 1 <= w <= 65535 and 1 <= H <= 65535 and 1 <= W <= 65535, f"1 <= h, w, H, W <= 65535, got {(h, w, H, W)}")
+    _require(n <= 65535, f"frames: at most 65 535 images in one call, got {n}")
     f = _resize_filter(resample)
     st = frames.stride()
     if n and not (st[3] == 1 and st[2] == 3 and st[1] >= 3 * w and (n == 1 or st[0] >= (h - 1) * st[1] + 3 * w)):
         frames = frames.contiguous()
         st = frames.stride()
-    if out is None:
-        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
-    _require(out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, H, W, 3),
-             "out: a contiguous [n, H, W, 3] uint8 device tensor")
+    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device) if out is None else _check("out", out, torch.uint8, (n, H, W, 3))
     if n == 0:
         return out
     lib = _lib.load()
@@ -483,12 +507,11 @@ def resize_rgb_device(frames: torch.Tensor, hw: Tuple[int, int], resample="bicub
         if h != H:
             by, ky = _resize_tables(h, H, f, frames.device)
         ws_bytes = int(lib.mspa_resize_workspace_bytes(n, h, w, H, W))
-        work = torch.empty(((ws_bytes + 15) // 16 * 2,), dtype=torch.int64, device=frames.device).view(torch.uint8) if ws_bytes else None
+        work = _workspace(ws_bytes, frames.device) if ws_bytes else None
         image_pitch = int(st[0]) if n > 1 else h * int(st[1])      # a single image's stride(0) means nothing
         _lib.check(lib.mspa_resize_rgb_device(frames.data_ptr(), n, h, w, int(st[1]), image_pitch,
                                               _ptr(out), H, W, f, _ptr(bx), _ptr(kx), _ptr(by), _ptr(ky),
-                                              work.data_ptr() if work is not None else None, int(work.numel()) if work is not None else 0,
-                                              _stream_ptr()))
+                                              _ptr(work), int(work.numel()) if work is not None else 0, _stream_ptr()))
     except _lib.MspaError as e:
         if e.code != _lib.MSPA_EUNSUPPORTED or not fallback:
             raise
@@ -521,10 +544,12 @@ PAIR_OUTPUTS = ("vis_bits", "vis_u8", "valid_u8", "pix_i16", "xyz_f32", "rgba", 
                 "depth_f64", "counts")
 
 
-def alloc_pair_outputs(n_pairs: int, image_hw: Tuple[int, int], outputs: Iterable[str], device="cuda"):
-    H, W = image_hw
+@functools.lru_cache(maxsize=16)
+def _pair_output_shapes(n_pairs: int, H: int, W: int) -> dict:
+    """name -> (shape, dtype) of mspa_pair_reproject's outputs: allocated by ``alloc_pair_outputs``, checked by ``pair_reproject``
+    (which asks per launch: the last few tables are kept; read-only)."""
     P = H * W
-    shapes = {
+    return types.MappingProxyType({
         "vis_bits": ((n_pairs, (P + 63) // 64), torch.int64),
         "vis_u8": ((n_pairs, P), torch.uint8),
         "valid_u8": ((n_pairs, P), torch.uint8),
@@ -535,7 +560,11 @@ def alloc_pair_outputs(n_pairs: int, image_hw: Tuple[int, int], outputs: Iterabl
         "uv_f64": ((n_pairs, P, 2), torch.float64),
         "depth_f64": ((n_pairs, P), torch.float64),
         "counts": ((n_pairs, 2), torch.int32),
-    }
+    })
+
+
+def alloc_pair_outputs(n_pairs: int, image_hw: Tuple[int, int], outputs: Iterable[str], device="cuda"):
+    shapes = _pair_output_shapes(n_pairs, *image_hw)
     out = {}
     for name in outputs:
         if name not in shapes:
@@ -547,26 +576,19 @@ def alloc_pair_outputs(n_pairs: int, image_hw: Tuple[int, int], outputs: Iterabl
 
 def pair_reproject(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.Tensor, image_hw: Tuple[int, int],
                    out: Dict[str, torch.Tensor], rgb: Optional[torch.Tensor] = None, flags: int = 0):
-    """Enqueue K3 on the current stream.  depth [F,DH,DW] int16(bits of uint16), mats [F,7,16] f64,
+    """Enqueue K3 on the current stream.  depth [F,DH,DW] int16(bits of uint16), mats [F,8,16] f64,
     pairs [B,2] int32, rgb [F,H,W,3] uint8 (only for out['rgba']).  ``out`` comes from
     alloc_pair_outputs and is filled in place."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3, "depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3")
-    _require(mats.dtype == torch.float64 and mats.shape[1:] == (_lib.FRAME_MATS, 16), "mats.dtype == torch.float64 and mats.shape[1:] == (_lib.FRAME_MATS, 16)")
-    _require(pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, "pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2")
-    F, DH, DW = depth.shape
-    _require(mats.shape[0] == F, "mats.shape[0] == F")
+    F, DH, DW, n = _check_pair_inputs(depth, mats, pairs)
     if flags & _lib.PAIR_FAST:
         _require_pinhole(mats)
     H, W = image_hw
     if rgb is not None:
-        _require(rgb.dtype == torch.uint8 and tuple(rgb.shape) == (F, H, W, 3), "rgb.dtype == torch.uint8 and tuple(rgb.shape) == (F, H, W, 3)")
-    g = lambda k: _ptr(out.get(k))
-    _lib.check(lib.mspa_pair_reproject(
-        _ptr(depth), _ptr(rgb), _ptr(mats), F, _ptr(pairs), pairs.shape[0], DH, DW, H, W,
-        g("vis_bits"), g("vis_u8"), g("valid_u8"), g("pix_i16"), g("xyz_f32"), g("rgba"),
-        g("xyz_f64"), g("uv_f64"), g("depth_f64"), g("counts"), flags, _stream_ptr()))
+        _check("rgb", rgb, torch.uint8, (F, H, W, 3))
+    _check_outputs(out, _pair_output_shapes(n, H, W))
+    _lib.check(_lib.load().mspa_pair_reproject(
+        _ptr(depth), _ptr(rgb), _ptr(mats), F, _ptr(pairs), n, DH, DW, H, W,
+        *map(_ptr, map(out.get, PAIR_OUTPUTS)), flags, _stream_ptr()))          # PAIR_OUTPUTS is in the C ABI's order
     return out
 
 
@@ -576,16 +598,20 @@ def corr_tiles(image_hw: Tuple[int, int]) -> Tuple[int, int]:
     return (W + _lib.CORR_TILE_W - 1) // _lib.CORR_TILE_W, (H + _lib.CORR_TILE_H - 1) // _lib.CORR_TILE_H
 
 
+@functools.lru_cache(maxsize=16)
+def _pair_correspondence_shapes(n_pairs: int, H: int, W: int) -> dict:
+    """name -> (shape, dtype) of mspa_pair_correspondences' outputs (include/mspa.h), as ``_pair_output_shapes``."""
+    ns, nb = corr_tiles((H, W))
+    return types.MappingProxyType({"vis_bits": ((n_pairs, (H * W + 63) // 64), torch.int64),
+            "cpix": ((n_pairs, ns * nb, _lib.CORR_TILE_CAP, 2), torch.int16),
+            "tile_counts": ((n_pairs, ns * nb), torch.int32),
+            "counts": ((n_pairs, 2), torch.int32)})
+
+
 def alloc_pair_correspondences(n_pairs: int, image_hw: Tuple[int, int], device="cuda", counts: bool = True):
     """Caller-owned outputs of ``pair_correspondences`` (include/mspa.h, mspa_pair_correspondences)."""
-    H, W = image_hw
-    ns, nb = corr_tiles(image_hw)
-    out = {"vis_bits": torch.empty((n_pairs, (H * W + 63) // 64), dtype=torch.int64, device=device),
-           "cpix": torch.empty((n_pairs, ns * nb, _lib.CORR_TILE_CAP, 2), dtype=torch.int16, device=device),
-           "tile_counts": torch.empty((n_pairs, ns * nb), dtype=torch.int32, device=device)}
-    if counts:
-        out["counts"] = torch.empty((n_pairs, 2), dtype=torch.int32, device=device)
-    return out
+    return {name: torch.empty(shape, dtype=dtype, device=device)
+            for name, (shape, dtype) in _pair_correspondence_shapes(n_pairs, *image_hw).items() if counts or name != "counts"}
 
 
 def pair_correspondences(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.Tensor, image_hw: Tuple[int, int],
@@ -593,31 +619,22 @@ def pair_correspondences(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.T
                          workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Enqueue K3 with the compacted correspondence output: the visibility bitset plus, per 64 x 48 tile of frame 1, the
     frame-2 pixel (xi, yi) of its VISIBLE pixels in (row, column) order.  One fused kernel on whole-tile shapes with
-    MSPA_PAIR_FAST (640x480); other shapes / the reference-order mode go through a dense table in ``workspace`` (allocated
-    here when not given).  ``out`` from ``alloc_pair_correspondences``."""
-    _require_gpu()
+    MSPA_PAIR_FAST (640x480); other shapes / the reference-order mode go through a dense table in ``workspace`` (int32 or
+    uint8, allocated here when not given or too small).  ``out`` from ``alloc_pair_correspondences``."""
     lib = _lib.load()
-    _require(depth.dtype in (torch.int16, torch.uint16) and depth.dim() == 3, "depth: [F, DH, DW] int16 / uint16")
-    _require(mats.dtype == torch.float64 and mats.shape[1:] == (_lib.FRAME_MATS, 16), "mats: float64 [F, 8, 16]")
-    _require(pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2, "pairs: int32 [B, 2]")
-    F, DH, DW = depth.shape
-    _require(mats.shape[0] == F, "mats.shape[0] == F")
+    F, DH, DW, n = _check_pair_inputs(depth, mats, pairs)
     if flags & _lib.PAIR_FAST:
         _require_pinhole(mats)
     H, W = image_hw
-    n = pairs.shape[0]
     if out is None:
         out = alloc_pair_correspondences(n, image_hw, depth.device)
-    ns, nb = corr_tiles(image_hw)
-    _require(tuple(out["cpix"].shape) == (n, ns * nb, _lib.CORR_TILE_CAP, 2) and out["cpix"].dtype == torch.int16,
-             "out['cpix']: int16 [n_pairs, n_tiles, 3072, 2]")
-    _require(tuple(out["tile_counts"].shape) == (n, ns * nb) and out["tile_counts"].dtype == torch.int32,
-             "out['tile_counts']: int32 [n_pairs, n_tiles]")
-    _require(tuple(out["vis_bits"].shape) == (n, (H * W + 63) // 64) and out["vis_bits"].dtype == torch.int64,
-             "out['vis_bits']: int64 [n_pairs, ceil(P / 64)]")
+    else:
+        _check_outputs(out, _pair_correspondence_shapes(n, H, W), required=("vis_bits", "cpix", "tile_counts"))
+    if workspace is not None:
+        _check("workspace", workspace, (torch.int32, torch.uint8), (None,))
     need = int(lib.mspa_pair_correspondences_workspace_bytes(n, DH, DW, H, W, flags))
-    _require(need >= 0, "image size within [2, 32767]")
-    if need == 0 and depth.data_ptr() & 3:
+    _require(need >= 0, "image_hw and the depth frames' size: within [2, 32767]")
+    if need == 0 and _ptr(depth) & 3:
         # a depth VIEW at an odd 2-byte offset: the fused kernel's 4-byte LDS-DMA cannot take it and the C entry point goes
         # through the dense table, which needs a workspace although the size query (it cannot see the pointer) said 0
         need = n * H * W * 4
@@ -652,6 +669,16 @@ def correspondences_rowmajor(out: Dict[str, torch.Tensor], image_hw: Tuple[int, 
     return yy * W + xx, e[:, 0], e[:, 1]
 
 
+def _check_cameras(xyz, cam_mats, depth, min_components: int = 3) -> Tuple[int, int, int]:
+    """What K1 and K6b project: xyz float64 [N, >= 3] handed over WITH its strides (any positive ones: rows, or a [3, N] SoA tensor's
+    ``.t()``), depth [I, DH, DW] and cam_mats [I, CAM_MATS, 16] float64 (``camera_matrices``) -> (I, DH, DW)."""
+    _check("xyz", xyz, torch.float64, (None, (min_components,)), contiguous=False)
+    _require(xyz.stride(0) > 0 and xyz.stride(1) > 0, f"xyz: positive strides, got {tuple(xyz.stride())}")
+    I, DH, DW = _check("depth", depth, _DEPTH, (None, None, None)).shape
+    _check("cam_mats", cam_mats, torch.float64, (I, _lib.CAM_MATS, 16))
+    return I, DH, DW
+
+
 def vertex_visibility(xyz: torch.Tensor, cam_mats: torch.Tensor, depth: torch.Tensor, image_hw: Tuple[int, int],
                       want: Iterable[str] = ("bits", "count"), homogeneous: bool = False,
                       depth_scale: float = 0.001) -> Dict[str, torch.Tensor]:
@@ -659,32 +686,15 @@ def vertex_visibility(xyz: torch.Tensor, cam_mats: torch.Tensor, depth: torch.Te
     given as xyz.t()); cam_mats [I,3,16]; depth [I,DH,DW].  Returns the requested outputs.
     ``homogeneous``: the rows are general homogeneous points (x, y, z, w) (``project_points`` takes any [N, 4], IH:46-72);
     ``depth_scale``: the handler's ``depth_value_scale`` (IH:76, IH:368)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.is_cuda, "xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.is_cuda")
+    I, DH, DW = _check_cameras(xyz, cam_mats, depth, 4 if homogeneous else 3)
     n = xyz.shape[0]
-    ps, cs = xyz.stride(0), xyz.stride(1)
-    _require(xyz.shape[1] >= (4 if homogeneous else 3) and ps > 0 and cs > 0, "xyz: [N, >= 3] rows ([N, >= 4] when homogeneous)")
-    I, DH, DW = depth.shape
-    _require(cam_mats.dtype == torch.float64 and tuple(cam_mats.shape) == (I, _lib.CAM_MATS, 16), "cam_mats: float64 [n_images, 3, 16] (engine.camera_matrices)")
     H, W = image_hw
-    dev = xyz.device
-    out: Dict[str, torch.Tensor] = {}
-    want = tuple(want)
-    if "bits" in want:
-        out["bits"] = torch.empty((I, (n + 63) // 64), dtype=torch.int64, device=dev)
-    if "mask" in want:
-        out["mask"] = torch.empty((I, n), dtype=torch.uint8, device=dev)
-    if "uv" in want:
-        out["uv"] = torch.empty((I, n, 2), dtype=torch.float64, device=dev)
-    if "depth" in want:
-        out["depth"] = torch.empty((I, n), dtype=torch.float64, device=dev)
-    if "count" in want:
-        out["count"] = torch.empty((I,), dtype=torch.int32, device=dev)
-    _require(depth.dtype in (torch.int16, torch.uint16), "depth.dtype in (torch.int16, torch.uint16)")
-    _lib.check(lib.mspa_vertex_visibility_ex(
-        xyz.data_ptr(), n, ps, cs, 1 if homogeneous else 0, _ptr(cam_mats), I, _ptr(depth), DH, DW, H, W, float(depth_scale),
-        _ptr(out.get("bits")), _ptr(out.get("mask")), _ptr(out.get("uv")), _ptr(out.get("depth")),
+    out = _alloc_wanted(want, {"bits": ((I, (n + 63) // 64), torch.int64), "mask": ((I, n), torch.uint8),
+                               "uv": ((I, n, 2), torch.float64), "depth": ((I, n), torch.float64),
+                               "count": ((I,), torch.int32)}, xyz.device)
+    _lib.check(_lib.load().mspa_vertex_visibility_ex(
+        xyz.data_ptr(), n, xyz.stride(0), xyz.stride(1), 1 if homogeneous else 0, _ptr(cam_mats), I, _ptr(depth), DH, DW, H, W,
+        float(depth_scale), _ptr(out.get("bits")), _ptr(out.get("mask")), _ptr(out.get("uv")), _ptr(out.get("depth")),
         _ptr(out.get("count")), _stream_ptr()))
     return out
 
@@ -696,16 +706,13 @@ def all_pairs(n: int, device="cuda") -> torch.Tensor:
 
 def pair_overlap(bits: torch.Tensor, pairs: torch.Tensor, want_counts: bool = False):
     """Enqueue K2 on K1's bitsets.  Returns overlap [n_pairs] f64 (+ inter, union int32)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous(), "bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous()")
-    _require(pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_contiguous(), "pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.is_conti")
-    n_pairs = pairs.shape[0]
+    F, n_words = _check_bits("bits", bits)
+    n_pairs = _check("pairs", pairs, torch.int32, (None, 2)).shape[0]
     overlap = torch.empty((n_pairs,), dtype=torch.float64, device=bits.device)
     inter = torch.empty((n_pairs,), dtype=torch.int32, device=bits.device) if want_counts else None
     uni = torch.empty((n_pairs,), dtype=torch.int32, device=bits.device) if want_counts else None
-    _lib.check(lib.mspa_pair_overlap(bits.data_ptr(), bits.shape[0], bits.shape[1], pairs.data_ptr(), n_pairs,
-                                     overlap.data_ptr(), _ptr(inter), _ptr(uni), _stream_ptr()))
+    _lib.check(_lib.load().mspa_pair_overlap(_ptr(bits), F, n_words, _ptr(pairs), n_pairs,
+                                             _ptr(overlap), _ptr(inter), _ptr(uni), _stream_ptr()))
     return (overlap, inter, uni) if want_counts else overlap
 
 
@@ -717,11 +724,7 @@ def _overlap_workspace(n_a: int, n_b: int, n_words: int, device) -> torch.Tensor
 def scene_overlap(bits: torch.Tensor, want_counts: bool = False):
     """Enqueue the tiled K2 over ALL pairs i < j of a scene's bitsets, in ``all_pairs`` order (CFR:176-178).
     Returns overlap [F(F-1)/2] f64 (+ inter, union int32) -- identical to ``pair_overlap(bits, all_pairs(F))``."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous() and bits.is_cuda,
-             "bits: contiguous device int64 [F, n_words]")
-    F, n_words = bits.shape
+    F, n_words = _check_bits("bits", bits)
     n_pairs = F * (F - 1) // 2
     dev = bits.device
     overlap = torch.empty((n_pairs,), dtype=torch.float64, device=dev)
@@ -729,49 +732,40 @@ def scene_overlap(bits: torch.Tensor, want_counts: bool = False):
     uni = torch.empty((n_pairs,), dtype=torch.int32, device=dev) if want_counts else None
     if n_pairs and n_words:
         ws = _overlap_workspace(F, F, n_words, dev)
-        _lib.check(lib.mspa_scene_overlap(bits.data_ptr(), F, n_words, ws.data_ptr(), ws.numel() * 4, overlap.data_ptr(),
-                                          _ptr(inter), _ptr(uni), _stream_ptr()))
+        _lib.check(_lib.load().mspa_scene_overlap(_ptr(bits), F, n_words, _ptr(ws), ws.numel() * 4, _ptr(overlap),
+                                                  _ptr(inter), _ptr(uni), _stream_ptr()))
     return (overlap, inter, uni) if want_counts else overlap
 
 
 def overlap_matrix(bits_a: torch.Tensor, bits_b: torch.Tensor) -> torch.Tensor:
     """Enqueue the tiled K2 on a rectangle: |a_i & b_j| for every row pair, [n_a, n_b] int32 (object visibility:
     objects x images, compute_object_visibility.py:72-152)."""
-    _require_gpu()
-    lib = _lib.load()
-    for t in (bits_a, bits_b):
-        _require(t.dtype == torch.int64 and t.dim() == 2 and t.is_contiguous() and t.is_cuda,
-                 "bits: contiguous device int64 [rows, n_words]")
-    _require(bits_a.shape[1] == bits_b.shape[1], "both bitset tables must have the same word count")
-    n_a, n_words = bits_a.shape
-    n_b = bits_b.shape[0]
+    n_a, n_words = _check_bits("bits_a", bits_a)
+    n_b = _check("bits_b", bits_b, torch.int64, (None, n_words)).shape[0]         # both tables: one word count
     out = torch.empty((n_a, n_b), dtype=torch.int32, device=bits_a.device)
     if n_a and n_b and n_words:
         ws = _overlap_workspace(n_a, n_b, n_words, bits_a.device)
-        _lib.check(lib.mspa_overlap_matrix(bits_a.data_ptr(), n_a, bits_b.data_ptr(), n_b, n_words, ws.data_ptr(),
-                                           ws.numel() * 4, out.data_ptr(), _stream_ptr()))
+        _lib.check(_lib.load().mspa_overlap_matrix(_ptr(bits_a), n_a, _ptr(bits_b), n_b, n_words, _ptr(ws),
+                                                   ws.numel() * 4, _ptr(out), _stream_ptr()))
     return out
 
 
 def bitset_csr(bits: torch.Tensor):
     """K9: rows of a bit matrix -> CSR of their set bits.  bits [R, n_words] int64 (device) -> (offsets [R+1] int64,
     indices [nnz] int32), both on the device; row r's set-bit positions, ascending, are indices[offsets[r]:offsets[r+1]]."""
-    _require_gpu()
     lib = _lib.load()
-    _require(bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous() and bits.is_cuda,
-             "bits: contiguous device int64 [rows, n_words]")
-    R, n_words = bits.shape
+    R, n_words = _check_bits("bits", bits)
     dev = bits.device
     if R == 0 or n_words == 0:
         return torch.zeros((R + 1,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev)
     counts = torch.empty((R * n_words,), dtype=torch.int32, device=dev)
-    _lib.check(lib.mspa_bits_popcount(bits.data_ptr(), R * n_words, counts.data_ptr(), _stream_ptr()))
+    _lib.check(lib.mspa_bits_popcount(_ptr(bits), R * n_words, _ptr(counts), _stream_ptr()))
     incl = torch.cumsum(counts, dim=0, dtype=torch.int64)              # torch as plumbing: one prefix sum
     word_offsets = (incl - counts).contiguous()
     total = int(incl[-1].item())
     indices = torch.empty((total,), dtype=torch.int32, device=dev)
     if total:
-        _lib.check(lib.mspa_bits_expand(bits.data_ptr(), R, n_words, word_offsets.data_ptr(), indices.data_ptr(), _stream_ptr()))
+        _lib.check(lib.mspa_bits_expand(_ptr(bits), R, n_words, _ptr(word_offsets), _ptr(indices), _stream_ptr()))
     offsets = torch.cat([word_offsets[::n_words], incl[-1:]])
     return offsets, indices
 
@@ -781,13 +775,10 @@ def format_lists_device(offsets: torch.Tensor, values: torch.Tensor, tokens: Opt
     make_visibility_info.py:38-73).  ``offsets`` [n + 1] int64, ``values`` [nnz] int32 (device).  ``tokens`` None: the items are
     integers; else item e is the text ``tokens[values[e]]`` (bytes, e.g. an already quoted image id).  Returns (text [bytes] uint8,
     text_offsets [n + 1] int32) on the device: arrow's string layout."""
-    _require_gpu()
     lib = _lib.load()
-    _require(offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= 1,
-             "offsets: contiguous device int64 [n_lists + 1]")
-    _require(values.dtype == torch.int32 and values.dim() == 1 and values.is_cuda and values.is_contiguous(), "values: contiguous device int32 [nnz]")
+    n = _check("offsets", offsets, torch.int64, ((1,),)).numel() - 1
+    nnz = _check("values", values, torch.int32, (None,)).numel()
     dev = offsets.device
-    n, nnz = offsets.numel() - 1, values.numel()
     tok = tok_off = None
     n_tokens = 0
     if tokens is not None:
@@ -817,14 +808,10 @@ def format_lists_device(offsets: torch.Tensor, values: torch.Tensor, tokens: Opt
 
 def bits_transpose(bits: torch.Tensor) -> torch.Tensor:
     """K9: [R, n_words] int64 bit matrix -> its transpose [n_words * 64, ceil(R / 64)] (padding bits zero)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous() and bits.is_cuda,
-             "bits: contiguous device int64 [rows, n_words]")
-    R, n_words = bits.shape
+    R, n_words = _check_bits("bits", bits)
     out = torch.empty((n_words * 64, (R + 63) // 64), dtype=torch.int64, device=bits.device)
     if R and n_words:
-        _lib.check(lib.mspa_bits_transpose(bits.data_ptr(), R, n_words, out.data_ptr(), _stream_ptr()))
+        _lib.check(_lib.load().mspa_bits_transpose(_ptr(bits), R, n_words, _ptr(out), _stream_ptr()))
     else:
         out.zero_()
     return out
@@ -850,13 +837,10 @@ def extract_yaw_pitch(E_aligned: torch.Tensor):
     """Device form of CFR:86-100 for frames that are already resident: E_aligned [F,16] f64 -> (yaw [F], pitch [F]) in
     degrees.  Within a few ulp of ``extract_yaw_pitch_host`` (device libm is not glibc); the pair-table writers keep the
     host path so that the parquet columns are the reference's bits."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(E_aligned.dtype == torch.float64 and E_aligned.dim() == 2 and E_aligned.shape[1] == 16, "E_aligned: float64 [F, 16]")
-    F = E_aligned.shape[0]
+    F = _check("E_aligned", E_aligned, torch.float64, (None, 16)).shape[0]
     yaw = torch.empty((F,), dtype=torch.float64, device=E_aligned.device)
     pitch = torch.empty((F,), dtype=torch.float64, device=E_aligned.device)
-    _lib.check(lib.mspa_extract_yaw_pitch(_ptr(E_aligned), F, _ptr(yaw), _ptr(pitch), _stream_ptr()))
+    _lib.check(_lib.load().mspa_extract_yaw_pitch(_ptr(E_aligned), F, _ptr(yaw), _ptr(pitch), _stream_ptr()))
     return yaw, pitch
 
 
@@ -864,38 +848,35 @@ def pair_pose(E_aligned: torch.Tensor, Einv_aligned: torch.Tensor, yaw: torch.Te
               pairs: torch.Tensor) -> torch.Tensor:
     """Enqueue K4.  E_aligned / Einv_aligned [F,16] f64, yaw / pitch [F] f64, pairs [n,2] i32 ->
     [n,6] f64: distance, dyaw, dpitch, translation of inv(E_i) @ E_j."""
-    _require_gpu()
-    lib = _lib.load()
-    F = E_aligned.shape[0]
-    for t in (E_aligned, Einv_aligned):
-        _require(t.dtype == torch.float64 and tuple(t.shape) == (F, 16), "t.dtype == torch.float64 and tuple(t.shape) == (F, 16)")
-    _require(yaw.dtype == torch.float64 and pitch.dtype == torch.float64 and pairs.dtype == torch.int32, "yaw.dtype == torch.float64 and pitch.dtype == torch.float64 and pairs.dtype == torch.int32")
-    out = torch.empty((pairs.shape[0], 6), dtype=torch.float64, device=E_aligned.device)
-    _lib.check(lib.mspa_pair_pose(_ptr(E_aligned), _ptr(Einv_aligned), _ptr(yaw), _ptr(pitch), F, _ptr(pairs),
-                                  pairs.shape[0], _ptr(out), _stream_ptr()))
+    F = _check("E_aligned", E_aligned, torch.float64, (None, 16)).shape[0]
+    _check("Einv_aligned", Einv_aligned, torch.float64, (F, 16))
+    _check("yaw", yaw, torch.float64, (F,))
+    _check("pitch", pitch, torch.float64, (F,))
+    n = _check("pairs", pairs, torch.int32, (None, 2)).shape[0]
+    out = torch.empty((n, 6), dtype=torch.float64, device=E_aligned.device)
+    _lib.check(_lib.load().mspa_pair_pose(_ptr(E_aligned), _ptr(Einv_aligned), _ptr(yaw), _ptr(pitch), F, _ptr(pairs),
+                                          n, _ptr(out), _stream_ptr()))
     return out
+
+
+def _check_tracks(name: str, tracks) -> Tuple[int, int]:
+    """Track points, float64 [T, P, 3] (camera space, or K5a's world positions) -> (T, P)."""
+    return tuple(_check(name, tracks, torch.float64, (None, None, 3)).shape[:2])
 
 
 def track_to_world(tracks_xyz: torch.Tensor, c2w: Optional[torch.Tensor], fx_fy_cx_cy: Sequence[float],
                    image_hw: Tuple[int, int], want=("world", "uvn", "ok")) -> Dict[str, torch.Tensor]:
     """Enqueue K5a.  tracks_xyz [T,P,3] f64, c2w [T,16] f64 (np.linalg.inv(extrinsics_w2c) on the host)."""
-    _require_gpu()
-    lib = _lib.load()
-    import ctypes
-    T, P, _ = tracks_xyz.shape
-    _require(tracks_xyz.dtype == torch.float64 and tracks_xyz.is_contiguous(), "tracks_xyz.dtype == torch.float64 and tracks_xyz.is_contiguous()")
-    dev = tracks_xyz.device
-    out = {}
-    if "world" in want:
-        out["world"] = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
-    if "uvn" in want:
-        out["uvn"] = torch.empty((T, P, 2), dtype=torch.float64, device=dev)
-    if "ok" in want:
-        out["ok"] = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    T, P = _check_tracks("tracks_xyz", tracks_xyz)
+    if c2w is not None:
+        _check("c2w", c2w, torch.float64, (T, 16))
+    _require(len(fx_fy_cx_cy) == 4, f"fx_fy_cx_cy: four numbers, got {len(fx_fy_cx_cy)}")
+    out = _alloc_wanted(want, {"world": ((T, P, 3), torch.float64), "uvn": ((T, P, 2), torch.float64),
+                               "ok": ((T, P), torch.uint8)}, tracks_xyz.device)
     intr = (ctypes.c_double * 4)(*[float(v) for v in fx_fy_cx_cy])
     H, W = image_hw
-    _lib.check(lib.mspa_track_to_world(_ptr(tracks_xyz), _ptr(c2w), T, P, intr, H, W, _ptr(out.get("world")),
-                                       _ptr(out.get("uvn")), _ptr(out.get("ok")), _stream_ptr()))
+    _lib.check(_lib.load().mspa_track_to_world(_ptr(tracks_xyz), _ptr(c2w), T, P, intr, H, W, _ptr(out.get("world")),
+                                               _ptr(out.get("uvn")), _ptr(out.get("ok")), _stream_ptr()))
     return out
 
 
@@ -903,89 +884,74 @@ def track_displacement(world: torch.Tensor, w2c: torch.Tensor, c2w: torch.Tensor
                        obj_threshold: float = 0.01, cam_threshold: float = 0.01):
     """Enqueue K5b.  Returns ([n,5] f64: distance, dx, dy, dz (camera-1 axes), binning distance;
     [n,2] u8: point_moving, cam_moving)."""
-    _require_gpu()
-    lib = _lib.load()
-    T, P, _ = world.shape
-    _require(triples.dtype == torch.int32 and triples.dim() == 2 and triples.shape[1] == 3, "triples.dtype == torch.int32 and triples.dim() == 2 and triples.shape[1] == 3")
-    n = triples.shape[0]
+    T, P = _check_tracks("world", world)
+    _check("w2c", w2c, torch.float64, (T, 16))
+    _check("c2w", c2w, torch.float64, (T, 16))
+    n = _check("triples", triples, torch.int32, (None, 3)).shape[0]
     out = torch.empty((n, 5), dtype=torch.float64, device=world.device)
     flags = torch.empty((n, 2), dtype=torch.uint8, device=world.device)
-    _lib.check(lib.mspa_track_displacement(_ptr(world), _ptr(w2c), _ptr(c2w), T, P, _ptr(triples), n,
-                                           obj_threshold, cam_threshold, _ptr(out), _ptr(flags), _stream_ptr()))
+    _lib.check(_lib.load().mspa_track_displacement(_ptr(world), _ptr(w2c), _ptr(c2w), T, P, _ptr(triples), n,
+                                                   obj_threshold, cam_threshold, _ptr(out), _ptr(flags), _stream_ptr()))
     return out, flags
 
 
 def check_visibility(uv: torch.Tensor, point_depth: Optional[torch.Tensor], depth_image: Optional[torch.Tensor],
                      image_hw: Tuple[int, int], want=("visible",), depth_scale: float = 0.001) -> Dict[str, torch.Tensor]:
     """The reference's three predicates on already-projected points (IH:337-386)."""
-    _require_gpu()
-    lib = _lib.load()
-    n = uv.shape[0]
-    _require(uv.dtype == torch.float64 and uv.dim() == 2 and uv.shape[1] == 2 and uv.is_contiguous(), "uv.dtype == torch.float64 and uv.dim() == 2 and uv.shape[1] == 2 and uv.is_contiguous()")
-    out = {k: torch.empty((n,), dtype=torch.uint8, device=uv.device) for k in want}
-    dh, dw = (depth_image.shape[-2], depth_image.shape[-1]) if depth_image is not None else (0, 0)
+    n = _check("uv", uv, torch.float64, (None, 2)).shape[0]
+    if point_depth is not None:
+        _check("point_depth", point_depth, torch.float64, (n,))
+    dh, dw = _check("depth_image", depth_image, _DEPTH, (None, None)).shape if depth_image is not None else (0, 0)
+    flags = ((n,), torch.uint8)
+    out = _alloc_wanted(want, {"in_bounds": flags, "by_depth": flags, "visible": flags}, uv.device)
     H, W = image_hw
-    _lib.check(lib.mspa_check_visibility_ex(_ptr(uv), _ptr(point_depth), n, _ptr(depth_image), dh, dw, H, W, float(depth_scale),
-                                            _ptr(out.get("in_bounds")), _ptr(out.get("by_depth")),
-                                            _ptr(out.get("visible")), _stream_ptr()))
+    _lib.check(_lib.load().mspa_check_visibility_ex(_ptr(uv), _ptr(point_depth), n, _ptr(depth_image), dh, dw, H, W, float(depth_scale),
+                                                    _ptr(out.get("in_bounds")), _ptr(out.get("by_depth")),
+                                                    _ptr(out.get("visible")), _stream_ptr()))
     return out
 
 
 def select_common_point(bits: torch.Tensor, selections: torch.Tensor) -> torch.Tensor:
     """Enqueue K6a.  bits [F, n_words] int64 (K1), selections [n, 3] int32 (image1, image2, j) ->
     [n] int32 vertex index: element j of np.intersect1d of the two visible lists (-1 if out of range)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous(), "bits.dtype == torch.int64 and bits.dim() == 2 and bits.is_contiguous()")
-    _require(selections.dtype == torch.int32 and selections.dim() == 2 and selections.shape[1] == 3, "selections.dtype == torch.int32 and selections.dim() == 2 and selections.shape[1] == 3")
-    out = torch.empty((selections.shape[0],), dtype=torch.int32, device=bits.device)
-    _lib.check(lib.mspa_select_common_point(_ptr(bits), bits.shape[0], bits.shape[1], _ptr(selections.contiguous()),
-                                            selections.shape[0], _ptr(out), _stream_ptr()))
+    F, n_words = _check_bits("bits", bits)
+    n = _check("selections", selections, torch.int32, (None, 3), contiguous=False).shape[0]
+    selections = selections.contiguous()        # a copy, if one is made, has to outlive the launch: a named tensor, not a temporary
+    out = torch.empty((n,), dtype=torch.int32, device=bits.device)
+    _lib.check(_lib.load().mspa_select_common_point(_ptr(bits), F, n_words, _ptr(selections), n, _ptr(out), _stream_ptr()))
     return out
 
 
 def project_samples(xyz: torch.Tensor, cam_mats: torch.Tensor, depth: torch.Tensor, image_hw: Tuple[int, int],
                     samples: torch.Tensor, depth_scale: float = 0.001):
     """Enqueue K6b.  samples [n, 2] int32 (vertex, image) -> (uv [n,2] f64, depth [n] f64, visible [n] u8)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] >= 3, "xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] >= 3")
-    _require(samples.dtype == torch.int32 and samples.dim() == 2 and samples.shape[1] == 2, "samples.dtype == torch.int32 and samples.dim() == 2 and samples.shape[1] == 2")
-    I, DH, DW = depth.shape
-    _require(xyz.is_cuda and xyz.stride(0) > 0 and xyz.stride(1) > 0, "xyz: device tensor with positive strides")
-    _require(depth.dtype in (torch.int16, torch.uint16), "depth.dtype in (torch.int16, torch.uint16)")
-    _require(cam_mats.dtype == torch.float64 and tuple(cam_mats.shape) == (I, _lib.CAM_MATS, 16), "cam_mats: float64 [n_images, 3, 16] (engine.camera_matrices)")
-    n = samples.shape[0]
+    I, DH, DW = _check_cameras(xyz, cam_mats, depth)
+    n = _check("samples", samples, torch.int32, (None, 2), contiguous=False).shape[0]
+    samples = samples.contiguous()              # named, as in select_common_point
     dev = xyz.device
     uv = torch.empty((n, 2), dtype=torch.float64, device=dev)
     d = torch.empty((n,), dtype=torch.float64, device=dev)
     vis = torch.empty((n,), dtype=torch.uint8, device=dev)
     H, W = image_hw
-    _lib.check(lib.mspa_project_samples_ex(xyz.data_ptr(), xyz.shape[0], xyz.stride(0), xyz.stride(1), _ptr(cam_mats), I,
-                                           _ptr(depth), DH, DW, H, W, float(depth_scale), _ptr(samples.contiguous()), n,
-                                           _ptr(uv), _ptr(d), _ptr(vis), _stream_ptr()))
+    _lib.check(_lib.load().mspa_project_samples_ex(xyz.data_ptr(), xyz.shape[0], xyz.stride(0), xyz.stride(1), _ptr(cam_mats), I,
+                                                   _ptr(depth), DH, DW, H, W, float(depth_scale), _ptr(samples), n,
+                                                   _ptr(uv), _ptr(d), _ptr(vis), _stream_ptr()))
     return uv, d, vis
 
 
 def track_rigidity_loss(tracks_xyz: torch.Tensor, smoothing_factor: float = 0.01) -> torch.Tensor:
     """Enqueue K7: [T,P,3] f64 tracks -> [P,P] f64 accumulated thresholded distance change (OM_C:66-78)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(tracks_xyz.dtype == torch.float64 and tracks_xyz.dim() == 3 and tracks_xyz.is_contiguous(), "tracks_xyz.dtype == torch.float64 and tracks_xyz.dim() == 3 and tracks_xyz.is_contiguous()")
-    T, P, _ = tracks_xyz.shape
+    T, P = _check_tracks("tracks_xyz", tracks_xyz)
     out = torch.empty((P, P), dtype=torch.float64, device=tracks_xyz.device)
-    _lib.check(lib.mspa_track_rigidity_loss(_ptr(tracks_xyz), T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
+    _lib.check(_lib.load().mspa_track_rigidity_loss(_ptr(tracks_xyz), T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
     return out
 
 
 def track_rigidity_loss_batch(tracks_xyz: torch.Tensor, smoothing_factor: float = 0.01) -> torch.Tensor:
     """Enqueue K7 for equal-shape track blocks in one launch: [B,T,P,3] f64 -> [B,P,P] f64, each the single form's matrix."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(tracks_xyz.dtype == torch.float64 and tracks_xyz.dim() == 4 and tracks_xyz.shape[3] == 3 and tracks_xyz.is_contiguous(), "tracks_xyz: contiguous float64 [B, T, P, 3]")
-    B, T, P, _ = tracks_xyz.shape
+    B, T, P, _ = _check("tracks_xyz", tracks_xyz, torch.float64, (None, None, None, 3)).shape
     out = torch.empty((B, P, P), dtype=torch.float64, device=tracks_xyz.device)
-    _lib.check(lib.mspa_track_rigidity_loss_batch(_ptr(tracks_xyz), B, T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
+    _lib.check(_lib.load().mspa_track_rigidity_loss_batch(_ptr(tracks_xyz), B, T, P, float(smoothing_factor), _ptr(out), _stream_ptr()))
     return out
 
 
@@ -1006,20 +972,19 @@ def track_linkage(loss: torch.Tensor, threshold: float = 0.1):
     K7 matrices, one workgroup per matrix.  loss [P,P] or [B,P,P] f64 (left untouched) -> (Z [.., P-1, 4] f64 bit for bit SciPy's,
     labels [.., P] i32, status [..] i32: 0 ok, 1 a non-finite entry (SciPy raises there), 2 iteration cap).  Enqueue only: the
     status is a device tensor like the rest.  P < 2 has no merge: Z is empty, a single point gets label 1."""
-    _require_gpu()
     lib = _lib.load()
-    _require(loss.dtype == torch.float64 and loss.dim() in (2, 3) and loss.shape[-1] == loss.shape[-2] and loss.is_contiguous(), "loss: contiguous float64 [P, P] or [B, P, P]")
-    single = loss.dim() == 2
+    single = isinstance(loss, torch.Tensor) and loss.dim() == 2
+    _check("loss", loss, torch.float64, (None, None) if single else (None, None, None))
+    _require(loss.shape[-1] == loss.shape[-2], f"loss: square matrices [P, P] or [B, P, P], got {list(loss.shape)}")
     B, P = (1 if single else loss.shape[0]), loss.shape[-1]
     dev = loss.device
+    status = torch.zeros((B,), dtype=torch.int32, device=dev)
     if P < 2:
         Z = torch.zeros((B, 0, 4), dtype=torch.float64, device=dev)
         labels = torch.ones((B, P), dtype=torch.int32, device=dev)
-        status = torch.zeros((B,), dtype=torch.int32, device=dev)
     else:
         Z = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
         labels = torch.empty((B, P), dtype=torch.int32, device=dev)
-        status = torch.zeros((B,), dtype=torch.int32, device=dev)
         need = lib.mspa_track_linkage_workspace_bytes(B, P)
         if need < 0:
             raise _lib.MspaError(_lib.MSPA_EINVAL, f"track_linkage: {P} points, at most {_lib.LINKAGE_MAX_POINTS} are supported")
@@ -1033,7 +998,7 @@ def track_rigid_groups(tracks_xyz: torch.Tensor, threshold: float = 0.1, smoothi
     """rigid_body_segmentation (OM_C:49-92) with both halves on the device: K7, then K7b, and only the labels (4 P bytes) and
     the status come back.  [T,P,3] f64 tracks -> the reference's list of index lists (``np.where(labels == i)`` for i = 1..max).
     Raises what SciPy raises: ValueError for a non-finite distance and for fewer than two points."""
-    _require(tracks_xyz.dim() == 3, "tracks_xyz.dim() == 3")
+    _check_tracks("tracks_xyz", tracks_xyz)
     if tracks_xyz.shape[1] < 2:
         raise ValueError("The number of observations cannot be determined on an empty distance matrix.")
     _, labels, status = track_linkage(track_rigidity_loss(tracks_xyz, smoothing_factor), threshold)
@@ -1049,30 +1014,24 @@ def track_rigid_groups(tracks_xyz: torch.Tensor, threshold: float = 0.1, smoothi
 def object_extents(vis_bits: torch.Tensor, xyz: torch.Tensor, obj_offsets: torch.Tensor, obj_vertices: torch.Tensor):
     """Enqueue K8: per (object, image) min / max xyz of the object's visible vertices and their count.
     vis_bits [F, n_words] int64, xyz [V,3] f64, objects as CSR (int32).  Returns (lo [O,F,3], hi [O,F,3], count [O,F])."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(vis_bits.dtype == torch.int64 and vis_bits.dim() == 2 and vis_bits.is_contiguous(), "vis_bits.dtype == torch.int64 and vis_bits.dim() == 2 and vis_bits.is_contiguous()")
-    _require(xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous(), "xyz.dtype == torch.float64 and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.is_contiguous(")
-    _require(obj_offsets.dtype == torch.int32 and obj_vertices.dtype == torch.int32, "obj_offsets.dtype == torch.int32 and obj_vertices.dtype == torch.int32")
-    F, n_words = vis_bits.shape
-    O = obj_offsets.numel() - 1
+    F, n_words = _check_bits("vis_bits", vis_bits)
+    _check("xyz", xyz, torch.float64, (None, 3))
+    O = _check("obj_offsets", obj_offsets, torch.int32, ((1,),)).numel() - 1
+    _check("obj_vertices", obj_vertices, torch.int32, (None,))
     dev = vis_bits.device
     lo = torch.empty((O, F, 3), dtype=torch.float64, device=dev)
     hi = torch.empty((O, F, 3), dtype=torch.float64, device=dev)
     count = torch.empty((O, F), dtype=torch.int32, device=dev)
-    _lib.check(lib.mspa_object_extents(_ptr(vis_bits), F, n_words, _ptr(xyz), xyz.shape[0], _ptr(obj_offsets),
-                                       _ptr(obj_vertices), obj_vertices.numel(), O, _ptr(lo), _ptr(hi), _ptr(count),
-                                       _stream_ptr()))
+    _lib.check(_lib.load().mspa_object_extents(_ptr(vis_bits), F, n_words, _ptr(xyz), xyz.shape[0], _ptr(obj_offsets),
+                                               _ptr(obj_vertices), obj_vertices.numel(), O, _ptr(lo), _ptr(hi), _ptr(count),
+                                               _stream_ptr()))
     return lo, hi, count
 
 
 def track_pair_distances(world: torch.Tensor, points: Sequence[int], visible_frames: Sequence[np.ndarray]):
     """Enqueue K5c: for each selected point, the distances between its world positions in every two of its visible
     frames (i < j, row-major).  Returns a list of float64 NumPy arrays, one per point (n(n-1)/2 entries)."""
-    _require_gpu()
-    lib = _lib.load()
-    _require(world.dtype == torch.float64 and world.dim() == 3 and world.is_contiguous(), "world.dtype == torch.float64 and world.dim() == 3 and world.is_contiguous()")
-    T, P, _ = world.shape
+    T, P = _check_tracks("world", world)
     S = len(points)
     if S == 0:
         return []
@@ -1095,8 +1054,8 @@ def track_pair_distances(world: torch.Tensor, points: Sequence[int], visible_fra
         f_off_t = torch.from_numpy(f_off.astype(np.int32)).to(dev)
         frames_t = torch.from_numpy(frames).to(dev)
         o_off_t = torch.from_numpy(o_off).to(dev)
-        _lib.check(lib.mspa_track_pair_distances(_ptr(world), T, P, _ptr(pts_t), _ptr(f_off_t), _ptr(frames_t), S,
-                                                 int(lens.max()), _ptr(o_off_t), _ptr(out), _stream_ptr()))
+        _lib.check(_lib.load().mspa_track_pair_distances(_ptr(world), T, P, _ptr(pts_t), _ptr(f_off_t), _ptr(frames_t), S,
+                                                         int(lens.max()), _ptr(o_off_t), _ptr(out), _stream_ptr()))
     host = out.cpu().numpy()
     return [host[o_off[s]:o_off[s + 1]] for s in range(S)]
 
@@ -1119,17 +1078,23 @@ def prep_spans(n_vertices: Sequence[int], device) -> dict:
             "vert_off_host": vert_off, "vert_off": torch.from_numpy(vert_off).to(device), "word_off": torch.from_numpy(word_off).to(device)}
 
 
+def _check_spans(spans: dict) -> Tuple[int, int]:
+    """The ``prep_spans`` tables as the K11 launches read them -> (n_scenes, n_vertices)."""
+    for k in ("vert_off", "word_off"):
+        _check(f"spans[{k!r}]", spans[k], torch.int64, (spans["n_scenes"] + 1,))
+    return spans["n_scenes"], spans["n_vertices"]
+
+
 def prep_labels(spans: dict, seg: torch.Tensor, tab_off: torch.Tensor, seg2inst: torch.Tensor, seg2label: torch.Tensor,
                 lab_off: torch.Tensor, label_value: torch.Tensor):
     """Enqueue ``mspa_prep_labels``: (instance_ids, label_ids) as int32 tensors holding uint32 bits, and the label index (int32)."""
-    _require_gpu()
-    S, N = spans["n_scenes"], spans["n_vertices"]
-    _require(seg.dtype == torch.int32 and seg.shape == (N,), "seg: int32 [n_vertices]")
-    _require(tab_off.dtype == torch.int64 and tab_off.shape == (S + 1,) and lab_off.dtype == torch.int64 and lab_off.shape == (S + 1,),
-             "tab_off / lab_off: int64 [n_scenes + 1]")
-    _require(seg2inst.dtype == torch.int32 and seg2label.dtype == torch.int32 and seg2inst.shape == seg2label.shape and seg2inst.dim() == 1,
-             "seg2inst / seg2label: int32 tables of one length")
-    _require(label_value.dtype == torch.int32 and label_value.dim() == 1, "label_value: int32 (uint32 bits)")
+    S, N = _check_spans(spans)
+    _check("seg", seg, torch.int32, (N,))
+    _check("tab_off", tab_off, torch.int64, (S + 1,))
+    _check("lab_off", lab_off, torch.int64, (S + 1,))
+    _check("seg2inst", seg2inst, torch.int32, (None,))
+    _check("seg2label", seg2label, torch.int32, (seg2inst.shape[0],))          # the two tables: one length
+    _check("label_value", label_value, torch.int32, (None,))                   # uint32 bits
     dev = seg.device
     inst = torch.empty((N,), dtype=torch.int32, device=dev)
     label = torch.empty((N,), dtype=torch.int32, device=dev)
@@ -1142,10 +1107,9 @@ def prep_labels(spans: dict, seg: torch.Tensor, tab_off: torch.Tensor, seg2inst:
 
 def prep_align(spans: dict, vertices: torch.Tensor, axis_align: torch.Tensor) -> torch.Tensor:
     """Enqueue ``mspa_prep_align``: [N, 6] float32 -> [N, 6] float64, xyz through each scene's 4x4 (``np.dot(pts, A.T)`` bits)."""
-    _require_gpu()
-    S, N = spans["n_scenes"], spans["n_vertices"]
-    _require(vertices.dtype == torch.float32 and vertices.shape == (N, 6), "vertices: float32 [n_vertices, 6]")
-    _require(axis_align.dtype == torch.float64 and axis_align.shape == (S, 4, 4), "axis_align: float64 [n_scenes, 4, 4]")
+    S, N = _check_spans(spans)
+    _check("vertices", vertices, torch.float32, (N, 6))
+    _check("axis_align", axis_align, torch.float64, (S, 4, 4))
     out = torch.empty((N, 6), dtype=torch.float64, device=vertices.device)
     _lib.check(_lib.load().mspa_prep_align(_ptr(vertices), _ptr(spans["vert_off"]), _ptr(spans["word_off"]), S, N, spans["n_waves"], _ptr(axis_align),
                                            _ptr(out), _stream_ptr()))
@@ -1156,12 +1120,11 @@ def prep_objects(spans: dict, instance_ids: torch.Tensor, vertices: torch.Tensor
     """Enqueue ``mspa_prep_objects`` and K9 on its membership rows.  ``n_objects[s]``: object slots of scene s (slot k - 1 <-> id k).
     Returns device tensors: count [M], lo / hi_unaligned and lo / hi_aligned [M, 3] float64, unique [S], and the stable split as CSR
     (``offsets`` [M + 1] int64, ``indices`` int32: scene-local vertex numbers, ascending within an object)."""
-    _require_gpu()
-    S, N = spans["n_scenes"], spans["n_vertices"]
-    _require(len(n_objects) == S, "n_objects: one per scene")
-    _require(instance_ids.dtype == torch.int32 and instance_ids.shape == (N,), "instance_ids: int32 [n_vertices]")
-    _require(vertices.dtype == torch.float32 and vertices.shape == (N, 6) and aligned.dtype == torch.float64 and aligned.shape == (N, 6),
-             "vertices float32 / aligned float64 [n_vertices, 6]")
+    S, N = _check_spans(spans)
+    _require(len(n_objects) == S, f"n_objects: one per scene ({S}), got {len(n_objects)}")
+    _check("instance_ids", instance_ids, torch.int32, (N,))
+    _check("vertices", vertices, torch.float32, (N, 6))
+    _check("aligned", aligned, torch.float64, (N, 6))
     dev = instance_ids.device
     obj_off_host = _ragged_offsets(n_objects)
     M, n_words = int(obj_off_host[-1]), spans["max_words"]
