@@ -6,14 +6,13 @@
 #include <string>
 
 #include "../../include/mspa.h"
+#include "pair_route.h"   // kWave: the one constant K3's CPU-built route header shares with every kernel
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "libmspa is written for gfx950 (MI355X) only: 16-byte LDS-DMA, v_mfma_i32_32x32x32_i8, native f64 min/max atomics"
 #endif
 
 namespace mspa {
-
-constexpr int kWave = 64;
 
 // thread-local error text behind mspa_last_error_string()
 std::string &last_error();

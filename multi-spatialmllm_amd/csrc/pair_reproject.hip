@@ -22,7 +22,9 @@
 //     tiles over a colour grid that differs from the depth grid (ScanNet's 1296 x 968 over 640 x 480).
 #include "mspa_common.h"
 
+#include <array>
 #include <type_traits>
+#include <utility>
 
 namespace mspa {
 
@@ -35,9 +37,10 @@ struct PairArgs {
     uint32_t P;            // H*W
     uint32_t div_magic;    // floor(2^32 / W) + 1 : i / W == umulhi(i, magic) for i*W < 2^32
     double sx, sy;         // dw / W, dh / H  (IH:359-360, OPS:272-273)
-    int strips;            // exact kernel: 4096-pixel strips per pair;  fast kernel: groups of 4 wave tiles
+    int strips;            // workgroups per pair (Route::groups), two meanings: the exact kernel's 4096-pixel strips, the other
+                           // kernels' groups of wave tiles (4 per workgroup; the tight kernel: tight_bw_of its set)
     int n_stripes, n_tiles;   // fast kernel: 64-column stripes per row band, wave tiles per pair
-    int n_wave_tiles;         // == n_tiles
+    int n_wave_tiles;         // == n_tiles (one tile per wave); a field of its own only because the kernel-argument layout is fixed
     uint32_t stripe_magic;    // floor(2^32 / n_stripes) + 1
     uint64_t *vis_bits;
     uint8_t *vis_u8;
@@ -59,19 +62,8 @@ struct PairArgs {
     int hwi, hhi;
 };
 
-// Output sets.  A kernel instantiated with GENERIC = true tests every output pointer at run time
-// (wave-uniform branches); the specialised instances know their set at compile time, which frees
-// ~20 SGPRs of pointers and removes the dead stores' address arithmetic.
-enum : uint32_t {
-    O_VIS_BITS = 1u << 0, O_VIS_U8 = 1u << 1, O_VALID_U8 = 1u << 2, O_PIX = 1u << 3, O_XYZ32 = 1u << 4,
-    O_RGBA = 1u << 5, O_XYZ64 = 1u << 6, O_UV64 = 1u << 7, O_DEPTH64 = 1u << 8, O_COUNTS = 1u << 9, O_CPIX = 1u << 10,
-};
-constexpr uint32_t kSetCorr = O_VIS_BITS | O_PIX | O_COUNTS;                         // correspondence
-constexpr uint32_t kSetDense = O_VIS_U8 | O_PIX | O_XYZ32 | O_RGBA | O_COUNTS;       // coloured point cloud
-constexpr uint32_t kSetDenseXyz = O_VIS_U8 | O_PIX | O_XYZ32 | O_COUNTS;              // point cloud without colour (rgb = 0)
-constexpr uint32_t kSetMinimal = O_VIS_BITS | O_COUNTS;                              // overlap only
-constexpr uint32_t kSetCompact = O_VIS_BITS | O_CPIX | O_COUNTS;                     // correspondences of the visible pixels only
-
+// Output sets (O_*, kSet*: pair_route.h): a kernel instantiated with GENERIC = true tests every output pointer at run time,
+// the specialised instances know their set at compile time.
 template <uint32_t SET, bool GENERIC>
 struct Outs {
     template <uint32_t BIT, typename T>
@@ -80,9 +72,6 @@ struct Outs {
     }
 };
 
-constexpr int kThreads = 256;
-constexpr int kIters = 16;                       // 4096 pixels per workgroup
-constexpr int kStrip = kThreads * kIters;
 constexpr int kGroup = 4;                        // pixels per lane processed between matrix reloads
 
 // guard band of the fast kernels: kGuardPx and guard_from_bounds in mspa_common.h
@@ -366,9 +355,6 @@ __device__ __forceinline__ double uniform(double v) {   // VGPR holding a wave-u
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
     return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
-
-constexpr int kTileRows = 16;                    // a wave owns a 64-column x 16-row tile
-constexpr int kRowGroup = 4;                     // rows whose depth-2 gathers are in flight together
 
 // Fast kernel.
 //  * Mapping: lane <-> image column, the wave walks down kTileRows rows.  The column is loop-invariant
@@ -711,12 +697,8 @@ __global__ __launch_bounds__(kThreads) void pair_fast_kernel(const uint16_t *__r
 //     vector pipe); risky rows are recorded per wave (ballot -> VGPR lane) instead of per-lane bit masks;
 //   * 48 rows per wave tile amortise the per-tile matrix composition;
 //   * a group of 4 rows none of whose 256 pixels can land in frame 2 skips gather, guard and depth test.
-constexpr int kTightRows = 48;                         // tile height of the correspondence family (= MSPA_CORR_TILE_H)
-// The dense sets carry a 3 KB transpose stage per wave: with 48-row tiles that is 36 KB of LDS per workgroup (four per CU),
-// with 32-row tiles 28 KB (five): measured 1.22 -> 1.17 ms per 1 000 pairs (dense without colour words, tools/ab_k3.py)
-constexpr int kTightRowsDense = 32;
-// rows whose depth-2 gathers are in flight together: the sets without a transpose stage (minimal, compact) may take more
-constexpr int tight_rg_of(uint32_t set) { return (set & (O_PIX | O_XYZ32 | O_RGBA | O_VIS_U8)) ? kRowGroup : 4; }
+// Tile heights, waves per workgroup and waves per SIMD of every output set, with their measurements: pair_route.h
+// (tight_rows_of, tight_rg_of, tight_bw_of, tight_minwaves_of).
 // Two variants of round 5 were measured at noise level and removed (tools/ab_scannet.py / ab_k3.py, one box, ms per 1 000
 // pairs, shipped -> variant).  The pair's composed matrix once per WORKGROUP (wave 0 -> LDS -> the others behind a workgroup
 // barrier, 12 broadcast reads + 24 v_readfirstlane) instead of per wave (~100 VALU issues of a tile's ~400 of fixed work) --
@@ -726,45 +708,6 @@ constexpr int tight_rg_of(uint32_t set) { return (set & (O_PIX | O_XYZ32 | O_RGB
 // minimal 1.343 -> 1.361, compact 1.798 -> 1.793: a culled tile's twelve serial round trips are hidden by the other waves
 // already.
 constexpr int kScaledCullBatch = 4;    // SCALED form, culled tile: rows whose samples are requested together for the valid-sample count
-// Tile height of the SCALED form (no LDS tile: height costs no occupancy; one lane per tile row holds its visibility word, so
-// 64 at most).  A tile's fixed work -- box scan, composition, culling test, ~400 VALU issues and their round trips -- is paid
-// per tile whatever it goes on to do, and at ScanNet's shape about half the tiles are culled: the minimal set runs 10 % faster
-// on 64-row tiles (1.298 vs 1.445 ms per 1 000 pairs), the correspondence set 7 % slower (1.821 vs 1.708: coarser culling
-// writes more of its index table), tools/ab_scannet.py round 5.  The compacted set's tile is part of the API (48).
-constexpr int kScaledRows = 48;
-constexpr int kScaledRowsNoPix = 64;
-// A wave of the SCALED form takes ONE tile.  Walking several vertically adjacent tiles per wave -- launch, the pair's matrices,
-// the column's depth-grid offsets and the other per-stripe constants paid once for them, the culling still per tile -- was
-// measured at ScanNet's shape (tools/ab_scannet.py, round 5, ms per 1 000 pairs at 1 / 2 / 3 / 4 tiles) and rejected:
-// corr 1.745 / 2.102 / 2.125 / 2.256, minimal 1.349 / 2.021 / 2.055 / 1.996 -- bit-identical and 20-50 % SLOWER: what was live
-// across the tile loop cost the row loop its registers (minimal: 42 VGPRs spilled to scratch in it).  For the compacted set
-// it never worked at all: with its spills the SGPR quad of the inline-asm `idxen` store came back wrong (memory fault).
-constexpr int tight_rows_of(uint32_t set, bool scaled = false) {
-    return (set & (O_XYZ32 | O_RGBA | O_VIS_U8)) ? kTightRowsDense
-           : (scaled && !(set & O_CPIX)) ? ((set & O_PIX) ? kScaledRows : kScaledRowsNoPix) : kTightRows;
-}
-// waves (= tiles) per workgroup, per output set (tools/ab_k3.py, one box, ms per 1 000 pairs at 1 / 2 / 4 / 8 waves): the sets
-// without an index table like small workgroups -- a workgroup's LDS is released only when its slowest tile is done --
-// minimal 0.325 / 0.309 / 0.319 / 0.351, compact 0.388 / 0.377 / 0.388 / 0.424; corr 0.525 / 0.505 / 0.503 / 0.558; the dense
-// point set without colour a large one, dense_xyz 1.303 / 1.200 / 1.149 / 1.132 (with colour words 4 stay better than 8:
-// 1.572 vs 1.587).
-// The SCALED form (no LDS depth tile: a workgroup's size costs no occupancy) runs best at four for every set
-// (tools/ab_scannet.py at ScanNet's shape, ms per 1 000 pairs at 1 / 2 / 4 / 8 waves: minimal 2.76 / 1.94 / 1.55-1.63 / 1.63,
-// compact 3.03 / 2.18 / 1.93 / 2.01, corr 2.55 / - / 1.72-1.80 / 1.79).
-constexpr int tight_bw_of(uint32_t set, bool scaled = false) {
-    return scaled ? 4
-           : (set & O_RGBA) ? 4
-           : (set & (O_XYZ32 | O_VIS_U8)) ? 8
-           : (set & O_PIX) ? 4 : 2;
-}
-// waves per SIMD the register allocator must leave room for (second argument of __launch_bounds__): the sets without an
-// index table run best at six (80 VGPRs); round 4's guard-band bookkeeping had pushed `minimal` to 82 = five waves, +5 %
-// (the SCALED correspondence set sat at 97 VGPRs = four waves: held at five; the whole-tile correspondence set is not held)
-constexpr int tight_minwaves_of(uint32_t set, bool scaled) {
-    return (set & (O_XYZ32 | O_RGBA | O_VIS_U8)) ? 1
-           : (set & O_PIX) ? (scaled ? 5 : 1)
-           : 6;
-}
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 
@@ -832,13 +775,15 @@ __device__ __forceinline__ uint32_t mbcnt64(unsigned long long m, uint32_t base)
 //     buffer returns 0 = "no sample") and store through one (dropped); ragged bottom band: a run-time row count;
 //   * the bitset: W % 16 == 0 makes a tile row's 64 bits four ALIGNED 16-bit pieces of the row-major bitset whatever the
 //     row -- four 2-byte stores per tile (lane = row) instead of one 8-byte store, no atomics, no stripe that shifts with the row.
-template <uint32_t SET, bool STREAM, int ROWS, int RG, bool SCALED = false>
+template <uint32_t SET, bool STREAM, bool SCALED>
 __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of(SET, SCALED)) void pair_fast_tight_kernel(const uint16_t *__restrict__ depth,
                                                                    const uint8_t *__restrict__ rgb,
                                                                    const double *__restrict__ mats,
                                                                    const int32_t *__restrict__ pairs, PairArgs a) {
     using O = Outs<SET, false>;
     constexpr int kTightBW = tight_bw_of(SET, SCALED);
+    constexpr int ROWS = tight_rows_of(SET, SCALED);   // tile height and row group: the same functions size the host's grid
+    constexpr int RG = tight_rg_of(SET);
     constexpr bool WANT_XYZ = (SET & O_XYZ32) != 0;
     constexpr bool COMPACT = (SET & O_CPIX) != 0;
     constexpr bool FRACT_GUARD = !COMPACT && !(SCALED && (SET & O_PIX));   // stage 2's tie / bound test by v_fract (see there)
@@ -871,7 +816,7 @@ __global__ __launch_bounds__(tight_bw_of(SET, SCALED) * kWave, tight_minwaves_of
 
     // wave tile -> (row band, column stripe); both wave-uniform
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // One tile per wave.  The walk over TPW vertically adjacent tiles (measured and rejected, see above tight_rows_of) keeps its loop
+    // One tile per wave.  The walk over TPW vertically adjacent tiles (measured and rejected, see pair_route.h above tight_rows_of) keeps its loop
     // form with TPW = 1: written as straight-line code the same arithmetic comes out of the compiler with another register
     // allocation in every instantiation, and the measurements above belong to this code.
     constexpr int TPW = 1;
@@ -1621,18 +1566,21 @@ static thread_local int g_last_pair_kernel = MSPA_KERNEL_NONE;
 
 extern "C" int mspa_pair_reproject_last_kernel(void) { return g_last_pair_kernel; }
 
-// whole-tile shapes the tight kernel takes (W % 64 == 0, H % 48 == 0, colour grid == depth grid, 32-bit byte offsets)
-static bool tight_shape(int32_t dh, int32_t dw, int32_t H, int32_t W, int rows = kTightRows) {
-    return dh == H && dw == W && (W % 64 == 0) && (H % rows == 0) && ((uint64_t)H * (uint64_t)W * 4 < (1ull << 31));
+// The kernel of kKeys[I] (pair_route.h).  Its template arguments are read out of the very key route() hands a launch, so the
+// instantiation a key names and the one that is compiled for it cannot differ; kKeys is the list of what is compiled.
+using PairKernel = void (*)(const uint16_t *, const uint8_t *, const double *, const int32_t *, PairArgs);
+template <int I>
+static PairKernel kernel_of() {
+    constexpr Key k = kKeys[I];
+    if constexpr (k.kernel == kKernelExact) return pair_exact_kernel<k.ident>;
+    else if constexpr (k.kernel == kKernelFast) return pair_fast_kernel<k.ident, k.whole_tiles, k.set, k.set == 0u, k.linear>;
+    else return pair_fast_tight_kernel<k.set, k.stream, k.scaled>;
 }
+template <int... I>
+static std::array<PairKernel, kNumKeys> kernel_table(std::integer_sequence<int, I...>) { return {{kernel_of<I>()...}}; }
+static const std::array<PairKernel, kNumKeys> kKernels = kernel_table(std::make_integer_sequence<int, kNumKeys>{});
 
-// shapes the tight kernel takes in its SCALED form (rectangular tiles on a colour grid at least as fine as the depth grid):
-// bitset rows in whole 16-bit pieces, whole 4-row groups, depth rows in whole 8-byte pieces, 32-bit byte offsets
-static bool rect_shape(int32_t dh, int32_t dw, int32_t H, int32_t W) {
-    return !tight_shape(dh, dw, H, W) && dw <= W && dh <= H && (W % 16 == 0) && (H % 4 == 0) && (dw % 4 == 0) && (dh % 2 == 0) &&
-           ((uint64_t)H * (uint64_t)W * 4 < (1ull << 31)) && ((uint64_t)dh * (uint64_t)dw * 2 < (1ull << 31));
-}
-
+// validate, route, fill PairArgs, look the key up, launch
 static int pair_reproject_impl(const uint16_t *depth, const uint8_t *rgb, const double *frame_mats,
                                int32_t n_frames, const int32_t *pairs, int64_t n_pairs, int32_t dh,
                                int32_t dw, int32_t H, int32_t W, uint64_t *out_vis_bits,
@@ -1643,22 +1591,37 @@ static int pair_reproject_impl(const uint16_t *depth, const uint8_t *rgb, const 
     if (n_frames <= 0 || n_pairs < 0) return fail(MSPA_EINVAL, "mspa_pair_reproject: bad frame/pair count");
     if (!depth || !frame_mats || (!pairs && n_pairs > 0))
         return fail(MSPA_EINVAL, "mspa_pair_reproject: null input pointer");
-    if (dh < 2 || dw < 2 || H < 2 || W < 2 || dh > 32767 || dw > 32767 || H > 32767 || W > 32767)
-        return fail(MSPA_EINVAL, "mspa_pair_reproject: image size out of range [2, 32767]");
-    const uint64_t P = (uint64_t)H * (uint64_t)W;
-    if (P * (uint64_t)W >= (1ull << 32)) return fail(MSPA_EINVAL, "mspa_pair_reproject: H*W*W must be < 2^32");
+    uint32_t set = 0;
+    set |= out_vis_bits ? O_VIS_BITS : 0; set |= out_vis_u8 ? O_VIS_U8 : 0; set |= out_valid_u8 ? O_VALID_U8 : 0;
+    set |= out_pix_i16 ? O_PIX : 0; set |= out_xyz_f32 ? O_XYZ32 : 0; set |= out_rgba ? O_RGBA : 0;
+    set |= out_xyz_f64 ? O_XYZ64 : 0; set |= out_uv_f64 ? O_UV64 : 0; set |= out_depth_f64 ? O_DEPTH64 : 0;
+    set |= out_counts ? O_COUNTS : 0; set |= out_cpix ? (O_CPIX | O_COUNTS) : 0;   // compacted set: counters optional at run time
+    // the tight kernel's LDS-DMA moves depth in 4-byte units and its 16-byte stores need aligned outputs
+    const bool aligned = (((uintptr_t)depth & 3u) == 0) && (((uintptr_t)out_pix_i16 & 15u) == 0) &&
+                         (((uintptr_t)out_vis_bits & 7u) == 0) && (((uintptr_t)out_cpix & 15u) == 0) &&
+                         (((uintptr_t)out_xyz_f32 & 15u) == 0) && (((uintptr_t)out_rgba & 15u) == 0) &&
+                         (((uintptr_t)out_vis_u8 & 3u) == 0);
+    const Route r = route(dh, dw, H, W, set, aligned, flags);
+    if (r.err && r.err != kRouteNeedsTight) return fail(MSPA_EINVAL, route_error_text(r.err));
     if (out_rgba && !rgb) return fail(MSPA_EINVAL, "mspa_pair_reproject: out_rgba needs rgb");
-    if (flags & ~(MSPA_PAIR_FAST | MSPA_PAIR_STREAM | MSPA_PAIR_WORD_STRIPES)) return fail(MSPA_EINVAL, "mspa_pair_reproject: unknown flag");
     if (n_pairs == 0) return MSPA_OK;
     hipStream_t s = (hipStream_t)stream;
+    if (out_counts) {      // 2 us per launch (tools/ab_k3.py: 0.5044 vs 0.5062 ms without / with)
+        int rc = check_hip(hipMemsetAsync(out_counts, 0, sizeof(int32_t) * 2 * n_pairs, s), "hipMemsetAsync(counts)");
+        if (rc) return rc;
+    }
+    if (r.err || (out_cpix && !out_tile_counts)) return fail(MSPA_EINVAL, route_error_text(kRouteNeedsTight));
 
     PairArgs a;
     a.n_pairs = n_pairs;
-    a.dh = dh; a.dw = dw; a.H = H; a.W = W; a.P = (uint32_t)P;
+    a.dh = dh; a.dw = dw; a.H = H; a.W = W; a.P = (uint32_t)H * (uint32_t)W;
     a.div_magic = (uint32_t)((1ull << 32) / (uint64_t)W) + 1u;
     a.sx = (double)dw / (double)W;
     a.sy = (double)dh / (double)H;
-    a.strips = (int)((P + kStrip - 1) / kStrip);
+    a.strips = r.groups;       // workgroups per pair: 4096-pixel strips (exact kernel) or groups of r.waves wave tiles (the others)
+    a.n_stripes = r.n_stripes;
+    a.n_tiles = a.n_wave_tiles = r.n_tiles;   // n_wave_tiles: one tile per wave (TPW == 1), kept for the kernel-argument layout
+    a.stripe_magic = r.n_stripes ? (uint32_t)((1ull << 32) / (uint64_t)r.n_stripes) + 1u : 0u;
     a.vis_bits = out_vis_bits; a.vis_u8 = out_vis_u8; a.valid_u8 = out_valid_u8; a.pix_i16 = out_pix_i16;
     a.xyz_f32 = out_xyz_f32; a.rgba = out_rgba; a.xyz_f64 = out_xyz_f64; a.uv_f64 = out_uv_f64;
     a.depth_f64 = out_depth_f64; a.counts = out_counts;
@@ -1670,117 +1633,13 @@ static int pair_reproject_impl(const uint16_t *depth, const uint8_t *rgb, const 
     a.hw = (double)a.hwi; a.hh = (double)a.hhi;
     a.khw = a.hw + kGuardPx; a.khh = a.hh + kGuardPx;
 
-    if (out_counts) {      // 2 us per launch (tools/ab_k3.py: 0.5044 vs 0.5062 ms without / with)
-        int rc = check_hip(hipMemsetAsync(out_counts, 0, sizeof(int32_t) * 2 * n_pairs, s), "hipMemsetAsync(counts)");
-        if (rc) return rc;
-    }
-    const bool ident = (dh == H && dw == W);
-    // float64 outputs are defined as the reference's own operation order: they force the exact kernel
-    // ... and so does a bitset output whose words straddle the 64-column stripes (W % 64 != 0, e.g. ScanNet's
-    // 1296-wide colour grid): the stripe-mapped fast kernel would need two atomicOr per wave-row there and
-    // measures slower than the exact kernel's word-aligned linear mapping (7.7 vs 6.7 ms per 1 000 pairs).
-    // ... and so does a depth grid LARGER than the colour grid (sx or sy > 1; no dataset has one): the guard band is built from
-    // colour-grid quantities and its half-guard margin is only argued for sx, sy <= 1.
-    const bool fast = (flags & MSPA_PAIR_FAST) && !out_xyz_f64 && !out_uv_f64 && !out_depth_f64 && dw <= W && dh <= H;
-    const bool linear = fast && out_vis_bits && (W % 64 != 0);   // bitset on a width that is not a multiple of 64
-    uint32_t set = 0;
-    set |= out_vis_bits ? O_VIS_BITS : 0; set |= out_vis_u8 ? O_VIS_U8 : 0; set |= out_valid_u8 ? O_VALID_U8 : 0;
-    set |= out_pix_i16 ? O_PIX : 0; set |= out_xyz_f32 ? O_XYZ32 : 0; set |= out_rgba ? O_RGBA : 0;
-    set |= out_counts ? O_COUNTS : 0; set |= out_cpix ? (O_CPIX | O_COUNTS) : 0;   // compacted set: counters optional at run time
-    // the tight kernel's LDS-DMA moves depth in 4-byte units and its 16-byte stores need aligned outputs
-    const bool aligned = (((uintptr_t)depth & 3u) == 0) && (((uintptr_t)out_pix_i16 & 15u) == 0) &&
-                         (((uintptr_t)out_vis_bits & 7u) == 0) && (((uintptr_t)out_cpix & 15u) == 0) &&
-                         (((uintptr_t)out_xyz_f32 & 15u) == 0) && (((uintptr_t)out_rgba & 15u) == 0) &&
-                         (((uintptr_t)out_vis_u8 & 3u) == 0);
-    const bool tight24 = fast && aligned && tight_shape(dh, dw, H, W, tight_rows_of(set)) &&
-                         (set == kSetCorr || set == kSetDense || set == kSetDenseXyz || set == kSetMinimal || set == kSetCompact);
-    // The tight kernel's SCALED form (rectangular tiles) takes the correspondence / minimal / compacted sets on every
-    // rect_shape, ScanNet's own (1296 x 968 colour over 640 x 480 depth) included: at four waves per workgroup it beat rounds
-    // 2-3's word-stripe kernel for that shape (corr 1.72-1.80 vs 1.90-2.05, minimal 1.55-1.63 vs 1.64-1.69 ms per 1 000 pairs,
-    // profiles/r04_ab_scannet.txt, r05_ab_scannet*.txt), which was removed; MSPA_PAIR_WORD_STRIPES, which selected it, is ignored
-    const bool rect = fast && !tight24 && aligned && rect_shape(dh, dw, H, W) &&
-                      (set == kSetCompact || set == kSetCorr || set == kSetMinimal);
-    if (out_cpix && !((tight24 || rect) && out_tile_counts))
-        return fail(MSPA_EINVAL, "pair_reproject_impl: the fused compacted set needs the tight kernel and a tile-count table");
-    if (fast) {
-        const int tile_rows = (tight24 || rect) ? tight_rows_of(set, rect) : kTileRows;
-        a.n_stripes = (W + 63) / 64;
-        a.n_tiles = (linear && !rect) ? (int)((P + (int64_t)kTileRows * 64 - 1) / ((int64_t)kTileRows * 64))
-                                      : a.n_stripes * ((H + tile_rows - 1) / tile_rows);
-        a.stripe_magic = (uint32_t)((1ull << 32) / (uint64_t)a.n_stripes) + 1u;
-        const int bw = rect ? tight_bw_of(set, true) : tight24 ? tight_bw_of(set) : (kThreads / kWave);
-        a.n_wave_tiles = a.n_tiles;
-        a.strips = (a.n_tiles + bw - 1) / bw;
-    } else {
-        a.n_stripes = a.n_tiles = a.n_wave_tiles = 0;
-        a.stripe_magic = 0;
-    }
     const int64_t groups = (n_pairs + n_xcd - 1) / n_xcd;
     const int64_t blocks = groups * n_xcd * a.strips;
     if (blocks > 0x7fffffffLL) return fail(MSPA_EINVAL, "mspa_pair_reproject: too many workgroups; split the batch");
-    const dim3 grid((uint32_t)blocks), block(kThreads);
-    g_last_pair_kernel = !fast ? MSPA_KERNEL_PAIR_EXACT
-                         : rect ? MSPA_KERNEL_PAIR_FAST_RECT
-                         : tight24 ? MSPA_KERNEL_PAIR_FAST_TIGHT
-                         : linear ? MSPA_KERNEL_PAIR_FAST_LINEAR : MSPA_KERNEL_PAIR_FAST;
-    if (!fast) {
-        if (ident) hipLaunchKernelGGL(pair_exact_kernel<true>, grid, block, 0, s, depth, rgb, frame_mats, pairs, a);
-        else hipLaunchKernelGGL(pair_exact_kernel<false>, grid, block, 0, s, depth, rgb, frame_mats, pairs, a);
-    } else if (rect) {
-#define MSPA_LAUNCH_RECT(SET_) \
-    do { \
-        if (flags & MSPA_PAIR_STREAM) \
-            hipLaunchKernelGGL((pair_fast_tight_kernel<SET_, true, tight_rows_of(SET_, true), tight_rg_of(SET_), true>), grid, dim3(tight_bw_of(SET_, true) * kWave), 0, s, depth, rgb, frame_mats, pairs, a); \
-        else \
-            hipLaunchKernelGGL((pair_fast_tight_kernel<SET_, false, tight_rows_of(SET_, true), tight_rg_of(SET_), true>), grid, dim3(tight_bw_of(SET_, true) * kWave), 0, s, depth, rgb, frame_mats, pairs, a); \
-    } while (0)
-        if (set == kSetCorr) MSPA_LAUNCH_RECT(kSetCorr);
-        else if (set == kSetCompact) MSPA_LAUNCH_RECT(kSetCompact);
-        else MSPA_LAUNCH_RECT(kSetMinimal);
-#undef MSPA_LAUNCH_RECT
-    } else if (tight24) {
-#define MSPA_LAUNCH_TIGHT(SET_) \
-    do { \
-        if (flags & MSPA_PAIR_STREAM) \
-            hipLaunchKernelGGL((pair_fast_tight_kernel<SET_, true, tight_rows_of(SET_), tight_rg_of(SET_)>), grid, dim3(tight_bw_of(SET_) * kWave), 0, s, depth, rgb, frame_mats, pairs, a); \
-        else \
-            hipLaunchKernelGGL((pair_fast_tight_kernel<SET_, false, tight_rows_of(SET_), tight_rg_of(SET_)>), grid, dim3(tight_bw_of(SET_) * kWave), 0, s, depth, rgb, frame_mats, pairs, a); \
-    } while (0)
-        if (set == kSetCorr) MSPA_LAUNCH_TIGHT(kSetCorr);
-        else if (set == kSetDense) MSPA_LAUNCH_TIGHT(kSetDense);
-        else if (set == kSetDenseXyz) MSPA_LAUNCH_TIGHT(kSetDenseXyz);
-        else if (set == kSetCompact) MSPA_LAUNCH_TIGHT(kSetCompact);
-        else MSPA_LAUNCH_TIGHT(kSetMinimal);
-#undef MSPA_LAUNCH_TIGHT
-    } else {
-#define MSPA_LAUNCH_FAST(ID, TI, SET_, GEN) \
-    hipLaunchKernelGGL((pair_fast_kernel<ID, TI, SET_, GEN>), grid, block, 0, s, depth, rgb, frame_mats, pairs, a)
-        const bool tight = (W % 64 == 0) && (H % kTileRows == 0);
-        if (ident && tight) {           // the BASELINE shape: 640x480 colour == depth
-            if (set == kSetCorr) MSPA_LAUNCH_FAST(true, true, kSetCorr, false);
-            else if (set == kSetDense) MSPA_LAUNCH_FAST(true, true, kSetDense, false);
-            else if (set == kSetMinimal) MSPA_LAUNCH_FAST(true, true, kSetMinimal, false);
-            else MSPA_LAUNCH_FAST(true, true, 0u, true);
-        } else if (linear) {
-#define MSPA_LAUNCH_LINEAR(ID, SET_, GEN) \
-    hipLaunchKernelGGL((pair_fast_kernel<ID, false, SET_, GEN, true>), grid, block, 0, s, depth, rgb, frame_mats, pairs, a)
-            if (ident) {
-                if (set == kSetCorr) MSPA_LAUNCH_LINEAR(true, kSetCorr, false);
-                else if (set == kSetMinimal) MSPA_LAUNCH_LINEAR(true, kSetMinimal, false);
-                else MSPA_LAUNCH_LINEAR(true, 0u, true);
-            } else {
-                if (set == kSetCorr) MSPA_LAUNCH_LINEAR(false, kSetCorr, false);
-                else if (set == kSetMinimal) MSPA_LAUNCH_LINEAR(false, kSetMinimal, false);
-                else MSPA_LAUNCH_LINEAR(false, 0u, true);
-            }
-#undef MSPA_LAUNCH_LINEAR
-        } else if (ident) {
-            MSPA_LAUNCH_FAST(true, false, 0u, true);
-        } else {
-            MSPA_LAUNCH_FAST(false, false, 0u, true);
-        }
-#undef MSPA_LAUNCH_FAST
-    }
+    const int ki = key_index(r.key);
+    if (ki < 0) return fail(MSPA_EINVAL, "pair_reproject_impl: route() named a kernel that kKeys does not list");
+    g_last_pair_kernel = r.family;
+    hipLaunchKernelGGL(kKernels[ki], dim3((uint32_t)blocks), dim3(r.threads), 0, s, depth, rgb, frame_mats, pairs, a);
     return check_hip(hipGetLastError(), "pair_reproject kernel launch");
 }
 
@@ -1796,36 +1655,34 @@ extern "C" int mspa_pair_reproject(const uint16_t *depth, const uint8_t *rgb, co
                                out_counts, nullptr, nullptr, flags, stream);
 }
 
-static bool corr_args_ok(int32_t H, int32_t W) { return H >= 2 && W >= 2 && H <= 32767 && W <= 32767; }
+extern "C" int64_t mspa_corr_tiles(int32_t H, int32_t W) { return size_ok(H, W) ? corr_tiles(H, W) : -1; }
 
-extern "C" int64_t mspa_corr_tiles(int32_t H, int32_t W) {
-    if (!corr_args_ok(H, W)) return -1;
-    return (int64_t)((W + MSPA_CORR_TILE_W - 1) / MSPA_CORR_TILE_W) * ((H + MSPA_CORR_TILE_H - 1) / MSPA_CORR_TILE_H);
+// The compacted set is fused (no dense table) exactly where route() gives it a kernel: only the tight kernel writes O_CPIX.
+static bool corr_fused(int32_t dh, int32_t dw, int32_t H, int32_t W, bool aligned, uint32_t flags) {
+    return route(dh, dw, H, W, kSetCompact, aligned, flags).err == kRouteOk;
 }
 
 extern "C" int64_t mspa_pair_correspondences_workspace_bytes(int64_t n_pairs, int32_t dh, int32_t dw, int32_t H, int32_t W,
                                                              uint32_t flags) {
-    if (n_pairs < 0 || !corr_args_ok(H, W)) return -1;
-    if ((flags & MSPA_PAIR_FAST) && (tight_shape(dh, dw, H, W) || rect_shape(dh, dw, H, W))) return 0;   // fused: no dense table
-    return n_pairs * (int64_t)H * W * 4;
+    if (n_pairs < 0 || !size_ok(H, W)) return -1;
+    return corr_fused(dh, dw, H, W, true, flags) ? 0 : n_pairs * (int64_t)H * W * 4;   // the query cannot see pointers
 }
 
 extern "C" int mspa_compact_correspondences(const uint64_t *vis_bits, const int16_t *pix_i16, int64_t n_pairs, int32_t H,
                                             int32_t W, int16_t *out_cpix_i16, int32_t *out_tile_counts,
                                             mspa_stream_t stream) {
-    if (n_pairs < 0 || !corr_args_ok(H, W)) return fail(MSPA_EINVAL, "mspa_compact_correspondences: bad pair count / image size");
+    if (n_pairs < 0 || !size_ok(H, W)) return fail(MSPA_EINVAL, "mspa_compact_correspondences: bad pair count / image size");
     if (n_pairs == 0) return MSPA_OK;
     if (!vis_bits || !pix_i16 || !out_cpix_i16 || !out_tile_counts)
         return fail(MSPA_EINVAL, "mspa_compact_correspondences: null pointer");
     if (((uintptr_t)pix_i16 & 3u) || ((uintptr_t)out_cpix_i16 & 3u))
         return fail(MSPA_EINVAL, "mspa_compact_correspondences: pixel-index tables must be 4-byte aligned");
-    const int n_stripes = (W + MSPA_CORR_TILE_W - 1) / MSPA_CORR_TILE_W;
-    const int n_tiles = n_stripes * ((H + MSPA_CORR_TILE_H - 1) / MSPA_CORR_TILE_H);
+    const int n_tiles = corr_tiles(H, W);
     const int64_t waves = n_pairs * n_tiles;
     const int64_t blocks = (waves + (kThreads / kWave) - 1) / (kThreads / kWave);
     if (blocks > 0x7fffffffLL) return fail(MSPA_EINVAL, "mspa_compact_correspondences: too many workgroups; split the batch");
     hipLaunchKernelGGL(compact_corr_kernel, dim3((uint32_t)blocks), dim3(kThreads), 0, (hipStream_t)stream, vis_bits,
-                       reinterpret_cast<const uint32_t *>(pix_i16), n_pairs, H, W, n_stripes, n_tiles,
+                       reinterpret_cast<const uint32_t *>(pix_i16), n_pairs, H, W, corr_stripes(W), n_tiles,
                        reinterpret_cast<uint32_t *>(out_cpix_i16), out_tile_counts);
     return check_hip(hipGetLastError(), "compact_corr_kernel launch");
 }
@@ -1843,8 +1700,8 @@ extern "C" int mspa_pair_correspondences(const uint16_t *depth, const double *fr
     const int64_t need = mspa_pair_correspondences_workspace_bytes(n_pairs, dh, dw, H, W, flags);
     if (need < 0) return fail(MSPA_EINVAL, "mspa_pair_correspondences: bad pair count / image size");
     // the fused kernel's LDS-DMA moves depth in 4-byte units: a depth table that is only 2-byte aligned takes the dense route
-    const bool depth_aligned = ((uintptr_t)depth & 3u) == 0;
-    if (need == 0 && depth_aligned)
+    // (the two output pointers were checked above: this is the alignment pair_reproject_impl will hand route())
+    if (corr_fused(dh, dw, H, W, ((uintptr_t)depth & 3u) == 0, flags))
         return pair_reproject_impl(depth, nullptr, frame_mats, n_frames, pairs, n_pairs, dh, dw, H, W, out_vis_bits, nullptr,
                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, out_counts, out_cpix_i16,
                                    out_tile_counts, flags, stream);

@@ -634,7 +634,7 @@ def pair_correspondences(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.T
         _check("workspace", workspace, (torch.int32, torch.uint8), (None,))
     need = int(lib.mspa_pair_correspondences_workspace_bytes(n, DH, DW, H, W, flags))
     _require(need >= 0, "image_hw and the depth frames' size: within [2, 32767]")
-    if need == 0 and _ptr(depth) & 3:
+    if need == 0 and _ptr(depth) & 3:      # the pointer rule of csrc/pair_route.h route(), which the size query cannot apply
         # a depth VIEW at an odd 2-byte offset: the fused kernel's 4-byte LDS-DMA cannot take it and the C entry point goes
         # through the dense table, which needs a workspace although the size query (it cannot see the pointer) said 0
         need = n * H * W * 4
