@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 220            /* 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 230            /* 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -593,6 +593,57 @@ int64_t mspa_png_encode_capacity(int32_t h, int32_t w);
 int64_t mspa_png_encode_workspace_bytes(int64_t n, int32_t h, int32_t w);
 int mspa_png_encode_device(const int16_t *depth_dev, int64_t n, int32_t h, int32_t w, uint8_t *out_dev, int64_t out_pitch,
                            int64_t *nbytes_dev, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * The visibility index's `values` column chunk ON THE DEVICE (csrc/parquet_pages.hip, K12; arithmetic in csrc/snappy_core.h):
+ * parquet v1 data pages -- PLAIN BYTE_ARRAY, RLE definition levels, Snappy -- from arrow's string layout (int32 offsets
+ * [rows + 1], uint8 data) as mspa_format_lists_device leaves it.  The compressor is the library's own deterministic algorithm
+ * (any Snappy decoder reads its streams; the bytes are not Google's): a stream is varint(n) and the elements of the input's
+ * independent 64 KiB blocks.  A g++ build of snappy_core.h is the reference the device equals byte for byte.
+ *
+ * mspa_snappy_capacity  worst-case bytes of the stream of n input bytes, 32 + n + n / 6; -1 for n outside 0 .. 2^31 - 1.
+ * mspa_snappy_compress_host  the reference: src[0, n) -> dst (dst_capacity >= mspa_snappy_capacity(n)); returns the stream's
+ *   length, or MSPA_EINVAL.
+ * mspa_snappy_workspace_bytes  bytes of block slots for n_blocks blocks (76 544 each); -1 for a bad count.
+ * mspa_snappy_compress_device  a batch of streams: stream s is src_dev[offsets_dev[s], + nbytes_dev[s]) (int64; streams may be
+ *   empty, overlap or leave gaps; every one must lie inside [0, src_bytes)), block_prefix_dev [n_streams + 1] the exclusive
+ *   prefix sum of ceil(nbytes / 65536) and n_blocks its last entry (the caller's plumbing, as for mspa_format_lists_device).
+ *   Block b's elements go to slots_dev + 76 544 b, their byte count to out_block_sizes_dev[b] (int64); -1 there marks a block
+ *   whose table entries do not describe a stream inside src (nothing was read for it).
+ * mspa_snappy_compact_device  the streams, back to back, into out_dev: size_prefix_dev [n_blocks + 1] is the exclusive prefix
+ *   sum of the block sizes, preamble_prefix_dev [n_streams + 1] that of the preambles' lengths (varint(nbytes): 1 .. 5 bytes).
+ *   Stream s occupies out_dev[size_prefix[block_prefix[s]] + preamble_prefix[s], size_prefix[block_prefix[s + 1]] +
+ *   preamble_prefix[s + 1]).  bad_flag_dev (int32, zeroed by the caller) is raised when a destination falls outside out_bytes;
+ *   such bytes are not written.
+ * mspa_parquet_page_cuts_host  the page-cut rule on host offsets: a page ends after the first value at which its PLAIN bytes
+ *   (4 + len per value) reach page_bytes.  out_cuts [pages + 1] (first value of each page, then rows) when not null; returns
+ *   the page count, MSPA_EINVAL for decreasing offsets or a cuts_capacity that is too small.
+ * mspa_parquet_page_payload_bytes_host / mspa_parquet_page_payload_host  the reference of one page's uncompressed payload for
+ *   the values [v0, v1): u32le(L), L bytes of levels (varint(num_values << 1), 0x01), the PLAIN values.
+ * mspa_parquet_string_pages_device  all pages' payloads back to back: cuts_dev [n_pages + 1] (int64, as above) and
+ *   payload_offsets_dev [n_pages + 1] (int64, exclusive prefix sum of the payload lengths; last entry payload_bytes) ->
+ *   out_payload_dev [payload_bytes].  The kernel checks the tables against the offsets and every index against rows and
+ *   data_bytes; bad_flag_dev (int32, zeroed by the caller) is raised on a mismatch and the bytes concerned are not written.
+ * All device calls only enqueue on `stream`; the caller owns every buffer; a wrong argument (a null pointer included) returns
+ * MSPA_EINVAL before anything is enqueued.
+ */
+int64_t mspa_snappy_capacity(int64_t n);
+int64_t mspa_snappy_compress_host(const uint8_t *src, int64_t n, uint8_t *dst, int64_t dst_capacity);
+int64_t mspa_snappy_workspace_bytes(int64_t n_blocks);
+int mspa_snappy_compress_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
+                                int64_t n_streams, const int64_t *block_prefix_dev, int64_t n_blocks, uint8_t *slots_dev,
+                                int64_t slots_bytes, int64_t *out_block_sizes_dev, void *stream);
+int mspa_snappy_compact_device(const int64_t *nbytes_dev, int64_t n_streams, const int64_t *block_prefix_dev, int64_t n_blocks,
+                               const uint8_t *slots_dev, int64_t slots_bytes, const int64_t *size_prefix_dev,
+                               const int64_t *preamble_prefix_dev, uint8_t *out_dev, int64_t out_bytes, int32_t *bad_flag_dev,
+                               void *stream);
+int64_t mspa_parquet_page_cuts_host(const int32_t *offsets, int64_t rows, int64_t page_bytes, int64_t *out_cuts, int64_t cuts_capacity);
+int64_t mspa_parquet_page_payload_bytes_host(const int32_t *offsets, int64_t v0, int64_t v1);
+int mspa_parquet_page_payload_host(const int32_t *offsets, const uint8_t *data, int64_t v0, int64_t v1, uint8_t *dst,
+                                   int64_t dst_capacity);
+int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t rows, const uint8_t *data_dev, int64_t data_bytes,
+                                     const int64_t *cuts_dev, const int64_t *payload_offsets_dev, int64_t n_pages, int64_t payload_bytes,
+                                     uint8_t *out_payload_dev, int32_t *bad_flag_dev, void *stream);
 
 /*
  * Image resizing ON THE DEVICE (csrc/resize.hip, arithmetic in csrc/resize_core.h): n 8-bit RGB images of one shape resampled

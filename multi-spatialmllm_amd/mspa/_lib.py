@@ -19,6 +19,7 @@ CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
 JPEG_DESC_BYTES = 4224
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
 LINKAGE_MAX_POINTS = 2048
+SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
@@ -136,6 +137,18 @@ _SIGNATURES = {
     "mspa_track_linkage_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "mspa_track_linkage": (c_int, [c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p]),
+    "mspa_snappy_capacity": (c_int64, [c_int64]),
+    "mspa_snappy_compress_host": (c_int64, [c_void_p, c_int64, c_void_p, c_int64]),
+    "mspa_snappy_workspace_bytes": (c_int64, [c_int64]),
+    "mspa_snappy_compress_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_void_p, c_void_p]),
+    "mspa_snappy_compact_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_void_p]),
+    "mspa_parquet_page_cuts_host": (c_int64, [c_void_p, c_int64, c_int64, c_void_p, c_int64]),
+    "mspa_parquet_page_payload_bytes_host": (c_int64, [c_void_p, c_int64, c_int64]),
+    "mspa_parquet_page_payload_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
+    "mspa_parquet_string_pages_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                 c_void_p, c_void_p]),
     "mspa_track_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                         c_double, c_double, c_void_p, c_void_p, c_void_p]),
 }

@@ -806,6 +806,115 @@ def format_lists_device(offsets: torch.Tensor, values: torch.Tensor, tokens: Opt
     return text[:total], text_offsets
 
 
+def snappy_capacity(n: int) -> int:
+    """Worst-case bytes of the Snappy stream of ``n`` input bytes (mspa_snappy_capacity)."""
+    cap = int(_lib.load().mspa_snappy_capacity(int(n)))
+    _require(cap > 0, "n: 0 <= n < 2^31")
+    return cap
+
+
+def snappy_compress_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor):
+    """K12: a batch of byte streams -- stream s is ``src[offsets[s] : offsets[s] + nbytes[s]]`` (``src`` uint8, ``offsets`` /
+    ``nbytes`` int64, all on the device; streams may be empty) -- each compressed into one Snappy stream by the library's own
+    deterministic compressor (csrc/snappy_core.h; byte for byte mspa_snappy_compress_host).  Returns (out uint8 [total], starts
+    int64 [n + 1]) on the device: stream s is ``out[starts[s] : starts[s + 1]]``.  Three small read-backs (block count, total,
+    the kernels' flag): the call returns with the streams written."""
+    out, starts, bad = _snappy_compress(src, offsets, nbytes)
+    _require(int(bad.item()) == 0, "snappy_compress_device: a destination fell outside the output")
+    return out, starts
+
+
+def _snappy_compress(src, offsets, nbytes):
+    """``snappy_compress_device`` without its last read-back: (out, starts, the compact kernels' flag, still on the device)."""
+    lib = _lib.load()
+    n = _check_streams(offsets, nbytes)
+    _check("src", src, torch.uint8, (None,))
+    dev = src.device
+    if n == 0:
+        return (torch.empty((0,), dtype=torch.uint8, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev),
+                torch.zeros((1,), dtype=torch.int32, device=dev))
+    # torch as plumbing: the prefix sums of blocks and of preamble lengths, and the argument check no kernel should have to make
+    block_prefix = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum((nbytes + (_lib.SNAPPY_BLOCK - 1)) // _lib.SNAPPY_BLOCK, dim=0, out=block_prefix[1:])
+    vlen = 1 + (nbytes >= 1 << 7).to(torch.int64) + (nbytes >= 1 << 14) + (nbytes >= 1 << 21) + (nbytes >= 1 << 28)
+    vprefix = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    torch.cumsum(vlen, dim=0, out=vprefix[1:])
+    inside = ((offsets >= 0) & (nbytes >= 0) & (nbytes <= 0x7fffffff) & (offsets <= src.numel() - nbytes)).all()
+    head = torch.stack([block_prefix[-1], inside.to(torch.int64)]).cpu()
+    _require(int(head[1]) == 1, "offsets / nbytes: every stream lies inside src and is shorter than 2 GiB")
+    n_blocks = int(head[0])
+    _require(n_blocks <= 0x7fffffff, "nbytes: fewer than 2^31 blocks of 64 KiB in one call")
+    slots = _workspace(int(lib.mspa_snappy_workspace_bytes(n_blocks)), dev)
+    sizes = torch.empty((max(n_blocks, 1),), dtype=torch.int64, device=dev)
+    _lib.check(lib.mspa_snappy_compress_device(_ptr(src), src.numel(), _ptr(offsets), _ptr(nbytes), n, _ptr(block_prefix), n_blocks,
+                                               _ptr(slots), slots.numel(), _ptr(sizes), _stream_ptr()))
+    size_prefix = torch.zeros((n_blocks + 1,), dtype=torch.int64, device=dev)
+    if n_blocks:
+        torch.cumsum(sizes[:n_blocks], dim=0, out=size_prefix[1:])
+    head = torch.stack([size_prefix[-1] + vprefix[-1], sizes[:n_blocks].min() if n_blocks else size_prefix[0]]).cpu()
+    _require(int(head[1]) >= 0, "snappy_compress_device: a block was refused by the kernel (stream table out of range)")
+    total = int(head[0])
+    out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_snappy_compact_device(_ptr(nbytes), n, _ptr(block_prefix), n_blocks, _ptr(slots), slots.numel(), _ptr(size_prefix),
+                                              _ptr(vprefix), _ptr(out), total, _ptr(bad), _stream_ptr()))
+    starts = size_prefix[block_prefix] + vprefix
+    return out, starts, bad
+
+
+def parquet_string_pages_device(text_offsets: torch.Tensor, data: torch.Tensor, page_bytes: int = 1 << 20, return_payload: bool = False):
+    """K12: a string column in arrow's layout on the device (``text_offsets`` int32 [rows + 1], ``data`` uint8: what
+    ``format_lists_device`` returns) -> its parquet v1 data pages, PLAIN BYTE_ARRAY with RLE definition levels (no nulls),
+    Snappy-compressed.  A page ends after the first value at which its PLAIN bytes reach ``page_bytes``.  Returns a dict:
+    ``chunk`` (uint8, device: the pages' compressed bytes back to back), ``compressed`` / ``uncompressed`` / ``num_values``
+    (int64 numpy, per page) and, with ``return_payload``, ``payload`` (uint8, device: the uncompressed payloads back to back).
+    The offsets come to the host (the page cuts are a serial rule over them); the text does not.  Synchronises the current
+    stream."""
+    lib = _lib.load()
+    rows = _check("text_offsets", text_offsets, torch.int32, ((1,),)).numel() - 1
+    _check("data", data, torch.uint8, (None,))
+    _require(int(page_bytes) >= 1, "page_bytes >= 1")
+    _require(data.numel() <= 0x7fffffff, "data: less than 2 GiB of text")
+    dev = data.device
+    offs = text_offsets.cpu().numpy()
+    empty = {"chunk": torch.empty((0,), dtype=torch.uint8, device=dev), "compressed": np.zeros(0, np.int64),
+             "uncompressed": np.zeros(0, np.int64), "num_values": np.zeros(0, np.int64)}
+    if return_payload:
+        empty["payload"] = torch.empty((0,), dtype=torch.uint8, device=dev)
+    if rows == 0:
+        return empty
+    _require(int(offs[0]) >= 0 and int(offs[-1]) <= data.numel() and bool((np.diff(offs) >= 0).all()),
+             "text_offsets: non-decreasing and inside data")
+    cuts = np.empty(rows + 1, dtype=np.int64)
+    n_pages = int(lib.mspa_parquet_page_cuts_host(offs.ctypes.data, rows, int(page_bytes), cuts.ctypes.data, rows + 1))
+    if n_pages < 0:
+        _lib.check(n_pages)
+    cuts = cuts[:n_pages + 1]
+    nv = np.diff(cuts)
+    levels = 1 + 1 + (nv >= 1 << 6) + (nv >= 1 << 13) + (nv >= 1 << 20) + (nv >= 1 << 27)       # varint(nv << 1), then 0x01
+    plain = 4 * nv + (offs[cuts[1:]].astype(np.int64) - offs[cuts[:-1]].astype(np.int64))
+    pay = 4 + levels + plain
+    _require(int(pay.max()) <= 0x7fffffff, "a page of 2 GiB or more: raise page_bytes' granularity")
+    table = np.zeros((3, n_pages + 1), dtype=np.int64)                                          # cuts, payload offsets, payload sizes
+    table[0] = cuts
+    np.cumsum(pay, out=table[1, 1:])
+    table[2, :n_pages] = pay
+    total = int(table[1, -1])
+    table_dev = torch.from_numpy(table).to(dev)
+    payload = torch.empty((total,), dtype=torch.uint8, device=dev)
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_parquet_string_pages_device(_ptr(text_offsets), rows, _ptr(data) if data.numel() else None, data.numel(),
+                                                    _ptr(table_dev[0]), _ptr(table_dev[1]), n_pages, total, _ptr(payload), _ptr(bad),
+                                                    _stream_ptr()))
+    chunk, starts, bad2 = _snappy_compress(payload, table_dev[1, :n_pages].contiguous(), table_dev[2, :n_pages].contiguous())
+    head = torch.cat([starts, bad.to(torch.int64), bad2.to(torch.int64)]).cpu().numpy()
+    _require(int(head[-2]) == 0 and int(head[-1]) == 0, "parquet_string_pages_device: the page tables do not describe the text")
+    out = {"chunk": chunk, "compressed": np.diff(head[:n_pages + 1]), "uncompressed": pay.astype(np.int64), "num_values": nv.astype(np.int64)}
+    if return_payload:
+        out["payload"] = payload
+    return out
+
+
 def bits_transpose(bits: torch.Tensor) -> torch.Tensor:
     """K9: [R, n_words] int64 bit matrix -> its transpose [n_words * 64, ceil(R / 64)] (padding bits zero)."""
     R, n_words = _check_bits("bits", bits)

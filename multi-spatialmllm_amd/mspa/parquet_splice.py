@@ -219,6 +219,87 @@ def encode_row_group(table, **writer_options) -> bytes:
     return sink.getvalue()
 
 
+# parquet.thrift numbers used by ``assemble_row_group``
+_BYTE_ARRAY, _PLAIN, _RLE, _SNAPPY, _DATA_PAGE = 6, 0, 3, 1, 0
+_TEMPLATES: dict = {}
+
+
+def _template_footer(schema, writer_options: tuple):
+    """FileMetaData of a row-less pyarrow encode of ``schema`` (the schema elements, the ``ARROW:schema`` key-value metadata, the
+    creator and the column orders), cached per process and schema."""
+    key = (schema.to_string(show_schema_metadata=True), schema.metadata and tuple(sorted(schema.metadata.items())), writer_options)
+    meta = _TEMPLATES.get(key)
+    if meta is None:
+        meta = _TEMPLATES[key] = split_file(encode_row_group(schema.empty_table(), **dict(writer_options)))[1]
+    return meta
+
+
+def page_header(num_values: int, uncompressed: int, compressed: int) -> bytes:
+    """thrift ``PageHeader`` of a v1 data page: PLAIN values, RLE definition and repetition levels, no statistics."""
+    w = _Writer()
+    w.struct([(1, T_I32, _DATA_PAGE), (2, T_I32, int(uncompressed)), (3, T_I32, int(compressed)),
+              (5, T_STRUCT, [(1, T_I32, int(num_values)), (2, T_I32, _PLAIN), (3, T_I32, _RLE), (4, T_I32, _RLE)])])
+    return bytes(w.o)
+
+
+def assemble_row_group(key_table, values_name: str, chunk, compressed, uncompressed, num_values, **writer_options) -> bytes:
+    """A self-contained one-row-group parquet file, like ``encode_row_group``'s, whose LAST column's pages were made elsewhere.
+
+    ``key_table``: the columns in front (a pyarrow table; for the visibility index the one ``key`` column) -- encoded by pyarrow
+    with ``writer_options`` and taken over verbatim, pages and ``ColumnChunk`` metadata with their min / max statistics.
+    ``values_name``: the name of the last column, a string column without nulls.  ``chunk``: its data pages' compressed payloads
+    back to back (bytes-like; K12, ``engine.parquet_string_pages_device``); ``compressed`` / ``uncompressed`` / ``num_values``:
+    per page.  The page headers and the chunk's ``ColumnMetaData`` (BYTE_ARRAY, [PLAIN, RLE], SNAPPY, no statistics) are written
+    here through this module's thrift codec; schema, key-value metadata, creator and column orders come from a row-less pyarrow
+    encode of the full schema, so a file may mix row groups of both origins."""
+    import pyarrow as pa
+    rows = key_table.num_rows
+    if rows == 0 or len(compressed) == 0:
+        raise ValueError("parquet_splice: assemble_row_group needs at least one row and one page")
+    if not (len(compressed) == len(uncompressed) == len(num_values)) or int(sum(int(v) for v in num_values)) != rows:
+        raise ValueError("parquet_splice: the pages do not hold the key table's rows")
+    chunk = memoryview(chunk).cast("B")
+    if int(sum(int(c) for c in compressed)) != len(chunk):
+        raise ValueError("parquet_splice: the pages' compressed sizes do not add up to the chunk")
+    schema = key_table.schema.append(pa.field(values_name, pa.string()))
+    template = _template_footer(schema.remove_metadata(), tuple(sorted(writer_options.items())))
+    key_pages, key_meta = split_file(encode_row_group(key_table.replace_schema_metadata(None), **writer_options))
+    _et, groups = _get(key_meta, 4)
+    if len(groups) != 1:
+        raise ValueError("parquet_splice: the key columns did not encode as one row group")
+    rg = groups[0]
+    _ct, cols = _get(rg, 1)
+    out = bytearray(MAGIC)
+    out += key_pages
+    first_page = len(out)
+    pos, total_unc = 0, 0
+    for c, u, nv in zip(compressed, uncompressed, num_values):
+        head = page_header(nv, u, c)
+        out += head
+        out += chunk[pos:pos + int(c)]
+        pos += int(c)
+        total_unc += len(head) + int(u)
+    total_comp = len(out) - first_page
+    column_meta = [(1, T_I32, _BYTE_ARRAY), (2, T_LIST, (T_I32, [_PLAIN, _RLE])), (3, T_LIST, (T_BINARY, [values_name.encode()])),
+                   (4, T_I32, _SNAPPY), (5, T_I64, rows), (6, T_I64, total_unc), (7, T_I64, total_comp), (9, T_I64, first_page)]
+    # ColumnChunk.file_offset: whatever convention the writer of the key chunk follows (0 since parquet-format 2.10, the chunk's end before)
+    cc = [(2, T_I64, len(out) if _get(cols[0], 2) else 0), (3, T_STRUCT, column_meta)]
+    rg = list(rg)
+    _set(rg, 1, T_LIST, (T_STRUCT, list(cols) + [cc]))
+    _set(rg, 2, T_I64, _get(rg, 2, 0) + total_unc)                          # RowGroup.total_byte_size
+    if _get(rg, 6) is not None:
+        _set(rg, 6, T_I64, _get(rg, 6) + total_comp)                        # RowGroup.total_compressed_size
+    meta = list(template)
+    _set(meta, 3, T_I64, rows)
+    _set(meta, 4, T_LIST, (T_STRUCT, [rg]))
+    w = _Writer()
+    w.struct(meta)
+    out += w.o
+    out += struct.pack("<I", len(w.o))
+    out += MAGIC
+    return bytes(out)
+
+
 class SplicedParquetWriter:
     """``append(mini_file_bytes)`` in the order the row groups are to appear; ``close()`` writes the footer.  ``num_rows`` and
     ``num_row_groups`` are kept up to date.  Every mini-file must carry the same schema (checked)."""

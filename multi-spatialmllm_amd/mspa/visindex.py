@@ -14,9 +14,20 @@ from __future__ import annotations
 
 import dataclasses
 import json
+import os
 from typing import Dict, List, Optional
 
 import numpy as np
+
+
+def encode_mode() -> str:
+    """Who encodes the index's ``values`` column chunk: "host" (the default: pyarrow, on the encoder thread) or "device"
+    (``MSPA_VISINDEX_ENCODE=device``: K12 writes the Snappy-compressed data pages on the GPU and only they cross PCIe).  Read at
+    every call."""
+    value = os.environ.get("MSPA_VISINDEX_ENCODE", "host").strip().lower() or "host"
+    if value not in ("host", "device"):
+        raise ValueError(f"MSPA_VISINDEX_ENCODE={value!r}: expected 'host' or 'device'")
+    return value
 
 
 @dataclasses.dataclass
@@ -31,6 +42,9 @@ class VisibilityCSR:
     # (int32 offsets [rows + 1], uint8 data): what ``to_arrow`` uses instead of the host formatters when present
     i2p_text: Optional[tuple] = None
     p2i_text: Optional[tuple] = None
+    # the ``values`` column chunk already encoded on the device (K12, engine.parquet_string_pages_device): its data pages'
+    # compressed bytes (uint8) and, per page, compressed size, uncompressed size and value count -- what ``to_row_group`` uses
+    values_pages: Optional[dict] = None
 
     def empty_images(self) -> List[str]:
         n = np.diff(self.i2p_offsets)
@@ -97,14 +111,37 @@ class VisibilityCSR:
             i2p_vals, p2i_vals = preformatted(F, self.i2p_text), preformatted(N, self.p2i_text)
         else:
             i2p_vals, p2i_vals = self._format_on_host(lib, string_array, ptr, pa)
-        # keys
+        return pa.table({"key": self._key_column(scene_id), "values": pa.concat_arrays([i2p_vals, p2i_vals])})
+
+    def _key_column(self, scene_id: str):
+        """The ``key`` column: image_to_points rows first."""
+        import pyarrow as pa
+        from . import _lib
+        lib = _lib.load()
+        N = self.n_points
         i2p_keys = pa.array([f"{scene_id}:image_to_points:{i}" for i in self.image_ids], type=pa.string())
         prefix = f"{scene_id}:point_to_images:".encode()
         cap = (len(prefix) + 21) * N + 16
         text, offs = np.empty(cap, dtype=np.uint8), np.empty(N + 1, dtype=np.int32)
         nb = lib.mspa_format_int_keys_host(prefix, 0, N, text.ctypes.data, cap, offs.ctypes.data) if N else 0
-        p2i_keys = string_array(N, text, offs, nb) if N else pa.array([], type=pa.string())
-        return pa.table({"key": pa.concat_arrays([i2p_keys, p2i_keys]), "values": pa.concat_arrays([i2p_vals, p2i_vals])})
+        if nb < 0:
+            _lib.check(int(nb))
+        p2i_keys = (pa.StringArray.from_buffers(N, pa.py_buffer(offs), pa.py_buffer(text[:nb])) if N
+                    else pa.array([], type=pa.string()))
+        return pa.concat_arrays([i2p_keys, p2i_keys])
+
+    def to_row_group(self, scene_id: str) -> bytes:
+        """This scene's row group as a self-contained one-row-group parquet file (what ``SplicedParquetWriter.append`` takes).
+        With ``values_pages`` (the device encoded the values chunk: ``from_bits(..., pages=True)``) only the ``key`` column goes
+        through pyarrow and the file is put together by ``parquet_splice.assemble_row_group``; otherwise it is pyarrow's encode
+        of ``to_arrow`` -- the same schema, so one file may hold row groups of both kinds."""
+        import pyarrow as pa
+        from . import parquet_splice
+        if self.values_pages is None:
+            return parquet_splice.encode_row_group(self.to_arrow(scene_id), use_dictionary=False)
+        pg = self.values_pages
+        return parquet_splice.assemble_row_group(pa.table({"key": self._key_column(scene_id)}), "values", pg["chunk"], pg["compressed"],
+                                                 pg["uncompressed"], pg["num_values"], use_dictionary=False)
 
     def quoted_image_ids(self) -> List[bytes]:
         return [json.dumps(i).encode() for i in self.image_ids]
@@ -134,12 +171,15 @@ class VisibilityCSR:
         return i2p_vals, p2i_vals
 
 
-def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, indices: bool = True) -> VisibilityCSR:
+def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, indices: bool = True, pages: bool = False,
+              page_bytes: int = 1 << 20) -> VisibilityCSR:
     """K1's bitsets [F, ceil(N/64)] (device int64 tensor) -> both CSR tables, compacted on the device.
     ``text``: also write both lists' JSON text on the device (K10) and bring it along as arrow string buffers -- what
     ``to_arrow`` then uses (only when the image ids are in sorted() order, MVI:117: always, for ScanNet's zero-padded frame
     numbers).  ``indices=False``: the index arrays themselves stay on the device (a parquet sweep that keeps nothing needs only
-    the text: 83 MB instead of 83 + 39)."""
+    the text: 83 MB instead of 83 + 39).  ``pages`` (with ``text``): the text stays on the device too -- K12 turns it into the
+    ``values`` column chunk's Snappy-compressed data pages (of ``page_bytes`` PLAIN bytes) and only those come along, as
+    ``values_pages``; image ids that are not sorted, or 2 GiB of text, fall back to ``text``."""
     from . import engine
     F = len(image_ids)
     if F == 0 or n_points == 0:
@@ -152,9 +192,17 @@ def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, ind
     ids = list(image_ids)
     text = text and ids == sorted(ids)
     want = [o1, i1 if indices or not text else None, o2, i2 if indices or not text else None]
+    encoded = None
     if text:
         csr0 = VisibilityCSR(ids, n_points, None, None, None, None)
-        want += list(engine.format_lists_device(o1, i1)[::-1]) + list(engine.format_lists_device(o2, i2, csr0.quoted_image_ids())[::-1])
+        t1, t2 = engine.format_lists_device(o1, i1), engine.format_lists_device(o2, i2, csr0.quoted_image_ids())
+        if pages and t1[0].numel() + t2[0].numel() <= 0x7fffffff:
+            # one string column, image_to_points rows first (as to_arrow concatenates them) -> its data pages, on the device
+            offsets = torch.cat([t1[1][:-1], t2[1] + t1[0].numel()])
+            encoded = engine.parquet_string_pages_device(offsets, torch.cat([t1[0], t2[0]]), page_bytes)
+            want.append(encoded.pop("chunk"))
+        else:
+            want += list(t1[::-1]) + list(t2[::-1])
     # ~100 MB per 320-frame scene: into pinned blocks (torch's caching host allocator), all copies behind ONE wait on the
     # CURRENT stream -- the sweeps call this on an encoder thread with a stream of its own, next to the sweep thread's kernels
     host = []
@@ -168,7 +216,9 @@ def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, ind
     torch.cuda.current_stream(bits.device).synchronize()
     host = [None if h is None else h.numpy() for h in host]
     csr = VisibilityCSR(ids, n_points, *host[:4])
-    if text:
+    if encoded is not None:
+        csr.values_pages = dict(encoded, chunk=host[4])
+    elif text:
         csr.i2p_text, csr.p2i_text = (host[4], host[5]), (host[6], host[7])
     return csr
 

@@ -75,12 +75,12 @@ def _visibility_csr(scene):
     launched = torch.cuda.Event()
     launched.record(torch.cuda.current_stream(bits.device))
 
-    def finish(text=False, indices=True):
+    def finish(text=False, indices=True, pages=False):
         with torch.cuda.device(bits.device):
             side = sweep.side_stream(bits.device)
             side.wait_event(launched)
             with torch.cuda.stream(side):
-                return visindex.from_bits(bits, ids, n_points, text=text, indices=indices)     # returns with the tables on the host
+                return visindex.from_bits(bits, ids, n_points, text=text, indices=indices, pages=pages)   # returns with the tables on the host
     return finish
 
 
@@ -101,6 +101,7 @@ def run_split(scene_info_path, output_file, warning_file, num_workers=8, keep=Tr
     import numpy as np
     from mspa import parquet_splice, shard, sweep, visindex
     from spatial_engine.utils.scannet_utils.handler.info_handler import SceneInfoHandler
+    encode = visindex.encode_mode()                # a bad MSPA_VISINDEX_ENCODE raises here, before anything is read
     scene_infos = SceneInfoHandler(scene_info_path)
     all_scene_ids = scene_infos.get_all_scene_ids()
     if ctx is None:
@@ -114,6 +115,9 @@ def run_split(scene_info_path, output_file, warning_file, num_workers=8, keep=Tr
         print("[run_split] DEBUG mode. Only processing first scene.")
     print(f"[run_split] Found {len(all_scene_ids)} scenes in {scene_info_path}")
     as_pkl = output_file.endswith(".pkl")
+    # MSPA_VISINDEX_ENCODE=device: the values chunk of every scene's row group is encoded on the GPU (K12) and the text never
+    # leaves it; the default, "host", is pyarrow on the encoder thread.  The two give files that read equal, not equal bytes.
+    device_pages = encode == "device" and not as_pkl
     want_csr = as_pkl or keep                      # rank 0 rebuilds the nested dict from the CSR tables
     timings = timings if timings is not None else sweep.Timings()
     costs = scene_infos.scene_costs(all_scene_ids, ctx.world if ctx is not None else 1)
@@ -134,7 +138,8 @@ def run_split(scene_info_path, output_file, warning_file, num_workers=8, keep=Tr
         def finish_scene():
             # the lists' JSON text is written on the device (K10) when a parquet file is what is asked for; the index arrays
             # themselves come to the host only if somebody wants them (the .pkl output, keep=True)
-            csr = later(text=not as_pkl, indices=want_csr) if callable(later) else later
+            options = {"pages": True} if device_pages else {}
+            csr = later(text=not as_pkl, indices=want_csr, **options) if callable(later) else later
             lines = [f"[Warning] {scene_id}: {image_id} has no in-bound points.\n" for image_id in csr.empty_images()]
             blobs = ["".join(lines).encode()]
             if not as_pkl:
@@ -142,7 +147,7 @@ def run_split(scene_info_path, output_file, warning_file, num_workers=8, keep=Tr
                 # arrow's buffers -> this scene's row group, encoded and compressed HERE; what leaves this rank is finished
                 # parquet bytes.  No dictionary pages: every key and every JSON list is unique, one would be built, overflow and
                 # be dropped.  63 ms of formatting + compression per 320-frame scene.
-                blobs.append(parquet_splice.encode_row_group(csr.to_arrow(scene_id), use_dictionary=False))
+                blobs.append(csr.to_row_group(scene_id))
             if want_csr:
                 blobs += [np.ascontiguousarray(getattr(csr, f)) for f in _CSR_FIELDS]
             return blobs
