@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kOThreads) void pair_overlap_kernel(OverlapArgs a) 
 // visits F(F-1)/2 pairs, and one wave per pair re-reads both 16 KB rows from L2 for each of them (1.67 GB through L2
 // for a 320-frame scene) and popcounts a & b AND a | b.  Here a workgroup owns a 32 x 32 block of (a, b) rows and a
 // 64-word slice of the bitsets; each of its four waves takes one 16-word chunk of that slice: the 64 rows' chunk is staged
-// in the wave's own LDS region (coalesced 16-byte loads, 128 contiguous bytes per row), every lane keeps a 4 x 4 sub-block
+// in the wave's own LDS region (16 bytes per lane as two 8-byte loads, a row's chunk contiguous), every lane keeps a 4 x 4 sub-block
 // of pair counters in registers and reads 4 + 4 row fragments per two words (ds_read_b128) for 32 pair-words -- 4 bytes of
 // LDS traffic per pair-word instead of 16 bytes of L2 traffic -- and only |a & b| is counted: the union is
 // |a| + |b| - |a & b| with |a| the diagonal entry.  The four waves' counters are summed through LDS, and the block writes
@@ -93,8 +93,8 @@ struct TileArgs {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// one chunk of the tile's 64 rows: kLoadsPerChunk 16-byte loads per lane (kLanesPerRow lanes cover a row's chunk)
-template <bool ALIGNED16>
+// one chunk of the tile's 64 rows: kLoadsPerChunk pairs of 8-byte loads per lane (kLanesPerRow lanes cover a row's chunk);
+// word by word, because this form's rows need not start on a 16-byte boundary
 __device__ __forceinline__ void load_chunk(const TileArgs &a, int ta, int tb, int64_t w0, int lrow, int lcol,
                                            u32x4 (&v)[kLoadsPerChunk]) {
 #pragma unroll
@@ -107,12 +107,8 @@ __device__ __forceinline__ void load_chunk(const TileArgs &a, int ta, int tb, in
         const int64_t w = w0 + lcol * 2;
         u32x4 x = {0u, 0u, 0u, 0u};
         if (row_ok && w0 < a.n_words) {
-            if (ALIGNED16) {
-                if (w < a.n_words) x = *reinterpret_cast<const u32x4 *>(src + w);      // n_words even: w + 1 exists too
-            } else {
-                const uint64_t p = w < a.n_words ? src[w] : 0ull, q = (w + 1) < a.n_words ? src[w + 1] : 0ull;
-                x = u32x4{(uint32_t)p, (uint32_t)(p >> 32), (uint32_t)q, (uint32_t)(q >> 32)};
-            }
+            const uint64_t p = w < a.n_words ? src[w] : 0ull, q = (w + 1) < a.n_words ? src[w + 1] : 0ull;
+            x = u32x4{(uint32_t)p, (uint32_t)(p >> 32), (uint32_t)q, (uint32_t)(q >> 32)};
         }
         v[k] = x;
     }
@@ -141,10 +137,11 @@ __device__ __forceinline__ void count_chunk(uint32_t *my, int lrow, int lcol, in
     wave_lds_fence();                                                    // the next chunk overwrites what was just read
 }
 
+// The popcount form of the tile.  It runs when the matrix-core form below cannot: an odd n_words, or a row table that does
+// not start on a 16-byte boundary (launch_tiles); every bitset K1 writes into a fresh tensor takes the other one.
 // Occupancy is the point of the sizes above: a wave issues one VALU instruction every ~5.7 cycles on its own
 // (profiles/r02_valu_rates.txt: 5.7 cycles per instruction at one wave per SIMD, 2.2 at eight), so this popcount-bound
 // kernel needs many resident waves, i.e. few registers (one staged chunk at a time, the next one in flight) and little LDS.
-template <bool ALIGNED16>
 __global__ __launch_bounds__(kTileWaves *kWave, 5) void overlap_tile_kernel(TileArgs a) {
     // tile list: all (ta, tb) for a rectangle; for a symmetric problem only ta <= tb, enumerated row by row of the triangle
     int ta, tb;
@@ -174,10 +171,10 @@ __global__ __launch_bounds__(kTileWaves *kWave, 5) void overlap_tile_kernel(Tile
     int acc[4][4] = {};
     const int64_t w0 = (int64_t)slice * kSliceWords + (int64_t)wave * (kChunkWords * kWaveChunks);
     u32x4 cur[kLoadsPerChunk], nxt[kLoadsPerChunk];
-    load_chunk<ALIGNED16>(a, ta, tb, w0, lrow, lcol, cur);
+    load_chunk(a, ta, tb, w0, lrow, lcol, cur);
 #pragma unroll
     for (int q = 0; q < kWaveChunks; ++q) {
-        if (q + 1 < kWaveChunks) load_chunk<ALIGNED16>(a, ta, tb, w0 + (q + 1) * kChunkWords, lrow, lcol, nxt);
+        if (q + 1 < kWaveChunks) load_chunk(a, ta, tb, w0 + (q + 1) * kChunkWords, lrow, lcol, nxt);
         if (w0 + q * kChunkWords < a.n_words) count_chunk(my, lrow, lcol, ti, tj, cur, acc);      // wave-uniform condition
 #pragma unroll
         for (int k = 0; k < kLoadsPerChunk; ++k) cur[k] = nxt[k];
@@ -391,10 +388,10 @@ static int launch_tiles(const uint64_t *bits_a, int n_a, const uint64_t *bits_b,
     if (aligned) {                                   // the matrix-core form needs whole 16-byte pieces of every row
         hipLaunchKernelGGL(overlap_tile_mfma_kernel, grid, dim3(kTileWaves * kWave), 0, s, t);
         return check_hip(hipGetLastError(), "overlap_tile_mfma_kernel launch");
+    } else {
+        hipLaunchKernelGGL(overlap_tile_kernel, grid, dim3(kTileWaves * kWave), 0, s, t);
+        return check_hip(hipGetLastError(), "overlap_tile_kernel launch");
     }
-    if (aligned) hipLaunchKernelGGL(overlap_tile_kernel<true>, grid, dim3(kTileWaves * kWave), 0, s, t);
-    else hipLaunchKernelGGL(overlap_tile_kernel<false>, grid, dim3(kTileWaves * kWave), 0, s, t);
-    return check_hip(hipGetLastError(), "overlap_tile_kernel launch");
 }
 
 }  // namespace mspa

@@ -711,12 +711,6 @@ constexpr int kScaledCullBatch = 4;    // SCALED form, culled tile: rows whose s
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int med3_0(int x, int hi) {   // clamp(x, 0, hi), hi wave-uniform
-    int r;
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
-    return r;
-}
-
 // Drop a wave-uniform 64-bit value (a ballot) into lane `lane` (wave-uniform) of a VGPR pair: 2 VALU issues.
 // v_writelane_b32 may name only ONE SGPR besides M0 (constant-bus rule of gfx9), so the lane select travels in M0.
 // Nothing else in the loop uses M0 (gfx9 LDS instructions do not; the tile's LDS-DMA requests were issued before it).

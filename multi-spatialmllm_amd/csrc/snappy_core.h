@@ -53,8 +53,6 @@ constexpr int64_t kMaxStream = 0x7fffffff;     // n of one stream (a varint of a
 MSPA_HD int64_t capacity(int64_t n) { return 32 + n + n / 6; }
 constexpr int64_t kSlot = (32 + kBlock + kBlock / 6 + 63) / 64 * 64;   // a block's worst-case output, rounded up to 64
 
-MSPA_HD int64_t blocks_of(int64_t n) { return (n + kBlock - 1) / kBlock; }
-
 MSPA_HD int varint_len(uint64_t v) {
     int k = 1;
     while (v >= 128) {

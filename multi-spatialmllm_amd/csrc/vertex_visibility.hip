@@ -108,7 +108,8 @@ __global__ __launch_bounds__(kVThreads) void vertex_visibility_kernel(const doub
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Fast form (no float64 outputs requested): the two 3x4 products of IH:57-66 are composed ONCE per image --
+// The derivation the compacted kernel below rests on (no float64 outputs requested; it was written for the round-2
+// one-lane-per-vertex kernel, removed since: DESIGN.md, K1).  The two 3x4 products of IH:57-66 are composed ONCE per image --
 // M = K * inv(A E), twelve entries, one per thread of the block, parked in LDS -- and a vertex costs 9 FMAs, a
 // reciprocal with one Newton step and two multiplies instead of 24 FP64 operations and two IEEE divisions.  Bit-exactness
 // is kept exactly as in K3's fast path: a lane whose decisions (half-to-even rounding of the pixel index, the image bounds,
@@ -134,160 +135,21 @@ __device__ __forceinline__ void image_guard_coefficients(const double *__restric
     out4[2] = 2.0 * b[1];
     out4[3] = __builtin_fma(2.0, b[3], kGuardZmmFloor);
 }
-constexpr int kVBatch = 8;                       // images whose depth gathers are in flight together
-
-template <bool IDENT>
-__global__ __launch_bounds__(kVThreads) void vertex_visibility_fast_kernel(const double *__restrict__ xyz,
-                                                                           const double *__restrict__ cam_mats,
-                                                                           const uint16_t *__restrict__ depth,
-                                                                           VertexArgs a) {
-    const uint32_t xcd = blockIdx.x % a.n_xcd;
-    const uint32_t slot = blockIdx.x / a.n_xcd;
-    const uint32_t vblock = slot % a.vblocks;
-    const uint32_t group = (slot / a.vblocks) * a.n_xcd + xcd;
-    if (group >= a.igroups) return;
-    const int img0 = (int)group * kImgPerBlock;
-    const int img1 = min(img0 + kImgPerBlock, a.n_images);
-
-    __shared__ double lds_m[kImgPerBlock][12];
-    __shared__ __attribute__((aligned(16))) double lds_g[kImgPerBlock][4];
-    __shared__ int lds_pinhole[kImgPerBlock];
-    if (threadIdx.x < kImgPerBlock * 12) {
-        const int im = threadIdx.x / 12, e = threadIdx.x % 12, r = e / 4, cidx = e % 4;
-        if (img0 + im < img1) {
-            const double *__restrict__ Einv = cam_mats + (int64_t)(img0 + im) * (MSPA_CAM_MATS * 16);
-            const double *__restrict__ K = Einv + 16;
-            double acc = K[4 * r + 0] * Einv[0 + cidx];
-            acc = __builtin_fma(K[4 * r + 1], Einv[4 + cidx], acc);
-            acc = __builtin_fma(K[4 * r + 2], Einv[8 + cidx], acc);
-            if (cidx == 3) acc += K[4 * r + 3];
-            lds_m[im][e] = acc * 1000.0;
-            if (e == 0) lds_pinhole[im] = (K[8] == 0.0 && K[9] == 0.0 && K[10] == 1.0 && K[11] == 0.0) ? 1 : 0;
-        }
-    } else if (threadIdx.x >= 128 && threadIdx.x < 128 + kImgPerBlock && img0 + (int)(threadIdx.x - 128) < img1) {
-        image_guard_coefficients(cam_mats + (int64_t)(img0 + (int)(threadIdx.x - 128)) * (MSPA_CAM_MATS * 16), (double)max(a.W, a.H),
-                                 lds_g[threadIdx.x - 128]);
-    }
-    const int64_t i = (int64_t)vblock * kVThreads + threadIdx.x;
-    const bool live = i < a.n_points;
-    const int64_t ic = live ? i : a.n_points - 1;
-    const int lane = threadIdx.x & 63;
-    const double x = xyz[ic * a.point_stride];
-    const double y = xyz[ic * a.point_stride + a.comp_stride];
-    const double z = xyz[ic * a.point_stride + 2 * a.comp_stride];
-    const double psum = (__builtin_fabs(x) + __builtin_fabs(y)) + __builtin_fabs(z);
-    const int64_t dpix = (int64_t)a.dh * a.dw;
-    const double Wd = (double)a.W, Hd = (double)a.H;
-    const int hi_x = a.dw - 1, hi_y = a.dh - 1;
-    const uint32_t dw2 = (uint32_t)a.dw * 2u;
-    __syncthreads();
-
-    // Images go through in batches of kVBatch: all projections and depth gathers of a batch are issued before the first
-    // sample is used, so a wave pays ONE memory round trip per batch instead of one per image (eight dependent round
-    // trips per wave left the kernel latency-bound at 8 waves per SIMD).  Lane predicates travel as ballot words (SGPRs).
-    for (int b0 = img0; b0 < img1; b0 += kVBatch) {
-        double izs[kVBatch];
-        uint32_t dv[kVBatch];
-        unsigned long long cand_m[kVBatch], risky_m[kVBatch];
-#pragma unroll
-        for (int q = 0; q < kVBatch; ++q) {
-            const int img = min(b0 + q, img1 - 1);               // a ragged last batch repeats its last image (not stored)
-            const int im = img - img0;
-            const uint16_t *__restrict__ dimg = depth + (int64_t)img * dpix;
-            const double *m = lds_m[im];
-            const double ix = __builtin_fma(m[0], x, __builtin_fma(m[1], y, __builtin_fma(m[2], z, m[3])));
-            const double iy = __builtin_fma(m[4], x, __builtin_fma(m[5], y, __builtin_fma(m[6], z, m[7])));
-            const double iz = __builtin_fma(m[8], x, __builtin_fma(m[9], y, __builtin_fma(m[10], z, m[11])));   // mm
-            double rz = __builtin_amdgcn_rcp(iz);
-            rz = __builtin_fma(__builtin_fma(-iz, rz, 1.0), rz, rz);
-            const double u = ix * rz, v = iy * rz;
-            const double us = IDENT ? u : u * a.sx, vs = IDENT ? v : v * a.sy;
-            const double ru = __builtin_rint(us), rv = __builtin_rint(vs);
-            const double zmin = __builtin_fma(lds_g[im][0], psum, lds_g[im][1]);      // this vertex, this image (see the top)
-            // saturating conversion (NaN -> 0), clamp by v_med3; the gather goes through a buffer resource of the frame with a
-            // 32-bit byte offset (64-bit address arithmetic cost five more instructions per image in an instruction-bound
-            // kernel).  The `cand ? offset : 0` below compiles to an exec-masked load: non-candidates (three lanes in four)
-            // never reach the address unit.  Letting them gather at their clamped border pixel was 18 % slower, a plain
-            // v_cndmask select (all lanes load, non-candidates sample 0) 25 % slower
-            int xi, yi;
-            asm("v_med3_i32 %0, %1, 0, %2" : "=v"(xi) : "v"((int)ru), "s"(hi_x));
-            asm("v_med3_i32 %0, %1, 0, %2" : "=v"(yi) : "v"((int)rv), "s"(hi_y));
-            // candidate = what the reference would accept, widened by the guard (a lane inside the widening is risky); within
-            // zmin of the camera plane u and v mean nothing: candidate whatever they say, and risky below
-            // ... and only if it is also within 2 max(W, H) zmin of the optical axis: nothing else near the plane can be accepted
-            const double tn = 2.0 * __builtin_fmax(Wd, Hd) * zmin;
-            const bool nearz = !(__builtin_fabs(iz) > zmin) & (__builtin_fabs(ix) < tn) & (__builtin_fabs(iy) < tn);
-            const bool cand = live & (((u > -kVGuardPx) & (u < Wd + kVGuardPx) & (v > -kVGuardPx) & (v < Hd + kVGuardPx) &
-                                       (iz > zmin)) | nearz);
-            // guard < |t| < 0.5 - guard for both coordinates  <=>  max(||tu| - .25|, ||tv| - .25|) < .25 - guard
-            const double wu = __builtin_fabs(us - ru) - 0.25, wv = __builtin_fabs(vs - rv) - 0.25;
-            unsigned long long rk = __builtin_amdgcn_ballot_w64(!(__builtin_fmax(__builtin_fabs(wu), __builtin_fabs(wv)) < 0.25 - kVGuardPx)) |
-                                    __builtin_amdgcn_ballot_w64(nearz);
-            if (!IDENT) {   // the bounds are integers of the COLOUR grid, the rounding ties belong to the depth grid
-                const double bu = __builtin_fmin(__builtin_fabs(u), __builtin_fabs(u - Wd));
-                const double bv = __builtin_fmin(__builtin_fabs(v), __builtin_fabs(v - Hd));
-                rk |= __builtin_amdgcn_ballot_w64(!(__builtin_fmin(bu, bv) > kVGuardPx));
-            }
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)dimg, 0, (int)(dpix * 2), 0x00020000);
-            dv[q] = __builtin_amdgcn_raw_buffer_load_b16(rs, cand ? (int)(__umul24((uint32_t)yi, dw2) + ((uint32_t)xi << 1)) : 0, 0, 0);
-            izs[q] = iz;
-            cand_m[q] = __builtin_amdgcn_ballot_w64(cand);
-            risky_m[q] = rk;
-        }
-#pragma unroll
-        for (int q = 0; q < kVBatch; ++q) {
-            const int img = b0 + q;
-            if (img >= img1) break;                              // block-uniform
-            const int im = img - img0;
-            const double sd = izs[q] - (double)dv[q];
-            unsigned long long word = cand_m[q] & __builtin_amdgcn_ballot_w64(sd < 0.0);
-            const double gz = __builtin_fma(lds_g[im][2], psum, lds_g[im][3]);
-            const unsigned long long rk = cand_m[q] & (risky_m[q] | __builtin_amdgcn_ballot_w64(!(__builtin_fabs(sd) > gz)));
-            const bool pin = lds_pinhole[im] != 0;               // block-uniform
-            if (rk != 0 || !pin) {                               // rare: the reference chain (IH:57-69, 337-386) for those lanes
-                const double *__restrict__ Einv = cam_mats + (int64_t)img * (MSPA_CAM_MATS * 16);
-                const double *__restrict__ K = Einv + 16;
-                const uint16_t *__restrict__ dimg = depth + (int64_t)img * dpix;
-                const bool mine = pin ? (((rk >> lane) & 1ull) != 0) : live;
-                bool vis = ((word >> lane) & 1ull) != 0;
-                if (mine) {
-                    const double qx = affine_row(Einv + 0, x, y, z);
-                    const double qy = affine_row(Einv + 4, x, y, z);
-                    const double qz = affine_row(Einv + 8, x, y, z);
-                    const double jx = affine_row(K + 0, qx, qy, qz);
-                    const double jy = affine_row(K + 4, qx, qy, qz);
-                    const double jz = affine_row(K + 8, qx, qy, qz);
-                    int ex, ey;
-                    vis = depth_test(true, jx / jz, jy / jz, qz, dimg, a.dh, a.dw, a.H, a.W, a.sx, a.sy, ex, ey);
-                }
-                word = __builtin_amdgcn_ballot_w64(vis);
-            }
-            if (lane == 0) {
-                if (a.bits && (i < a.n_points)) a.bits[(int64_t)img * a.n_words + (i >> 6)] = word;
-                if (a.count_atomic) {
-                    const int c = __popcll(word);
-                    if (c) atomicAdd(a.count_atomic + img, c);
-                }
-            }
-            if (live && a.mask) a.mask[(int64_t)img * a.n_points + i] = (uint8_t)((word >> lane) & 1ull);
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
-// Compacted form of the fast kernel.  Three (vertex, image) pairs in four fail the frustum test, yet on an unordered vertex
-// array every wave holds some candidate for every image, so no wave-level early-out ever fires and the fast kernel spends
-// its ~55 VALU issues per (wave, image) on mostly idle lanes -- and it is instruction-bound.  Here the block works in phases:
+// Compacted form of the composed kernel.  Three (vertex, image) pairs in four fail the frustum test, yet on an unordered vertex
+// array every wave holds some candidate for every image, so no wave-level early-out ever fires and one lane per vertex spends
+// its ~55 VALU issues per (wave, image) on mostly idle lanes -- and is instruction-bound.  Here the block works in phases:
 //   A  every thread decides candidacy of its vertex for the block's images on the homogeneous triple, BEFORE the division
 //      (iz > 0:  u > -b  <=>  ix > -b iz;  u < W + b  <=>  ix < (W + b) iz), 17 issues per image, and the candidates
 //      (vertex, image) are compacted into an LDS list (ballot + mbcnt ranks, one LDS atomic per wave);
 //   B  the threads walk the dense list: projection again for the listed pair (vertex from LDS, matrix row set of its image
 //      from LDS), reciprocal, rounding, guards, depth gather (one buffer resource spans the block's frames), depth test;
-//      guarded lanes take the reference chain exactly as before; visible pairs OR their bit into an LDS bit table;
+//      guarded lanes take the reference chain; visible pairs OR their bit into an LDS bit table;
 //   C  the table leaves as the same coalesced bitset words / byte mask / counts.
 // The tie guard of phase B is TWICE the candidate band of phase A, so a lane the band let in from just outside the image
 // (|u| < b) is always re-evaluated; lanes with |iz| under the depth guard and images with a non-pinhole K are listed
-// unconditionally and re-evaluated.  Same integers as the other two kernels (tests/test_gpu_parity.py: goldens, adversarial
+// unconditionally and re-evaluated.  Same integers as the reference-order kernel (tests/test_gpu_parity.py: goldens, adversarial
 // cameras, ScanNet's two grids, non-pinhole K).
 // ---------------------------------------------------------------------------------------------------------
 constexpr double kVBandPx = kVGuardPx;       // phase A: candidate band around the image, on the homogeneous coordinates
@@ -316,6 +178,7 @@ void vertex_visibility_compact_kernel(const double *__restrict__ xyz,
     __shared__ uint16_t lds_list[kVThreads * kImgPerBlock];          // tid | image << 8 | (near the camera plane and axis) << 15
     __shared__ double lds_gz[kVThreads];                              // per vertex: depth-test guard (mm)
     static_assert(kImgPerBlock <= 64, "list entry: 6 bits of image index under the flag bit");
+    static_assert(kImgPerBlock * 12 <= kVThreads, "one thread per entry of the block's composed matrices");
     __shared__ uint32_t lds_bits[kImgPerBlock][kVThreads / 32];
     __shared__ uint32_t lds_n;
     if (tid < kImgPerBlock * 12) {
@@ -566,6 +429,35 @@ __global__ __launch_bounds__(kVThreads) void check_visibility_kernel(const doubl
     if (vis_out) vis_out[i] = (inb && byd) ? 1 : 0;
 }
 
+// Which K1 kernel a call takes.  float64 outputs are DEFINED as the reference's operation order, and so are a general
+// homogeneous coordinate and a depth scale other than the millimetre the composed kernel folds in; everything else (bitset,
+// byte mask, counts) takes the compacted kernel, which reproduces the same integers -- as long as the 32-bit byte offsets of its
+// one buffer resource span a block's kImgPerBlock depth frames, i.e. up to 2^27 - 1 pixels per frame (11 585 x 11 585).  A larger
+// frame takes the reference-order kernel and its 64-bit pointers: the same integers, at a time per call that nobody has measured
+// (no dataset has such a frame; the round-2 kernel that used to take them had never run at that size either).
+enum K1Kernel { kK1ExactHomog, kK1Exact, kK1CompactIdent, kK1CompactScaled };
+
+constexpr K1Kernel vertex_route(int32_t dh, int32_t dw, int32_t H, int32_t W, bool homogeneous, bool f64_outputs, bool millimetres) {
+    if (homogeneous) return kK1ExactHomog;
+    if (f64_outputs || !millimetres) return kK1Exact;
+    if ((int64_t)kImgPerBlock * dh * dw * 2 >= 0x7fffffffLL) return kK1Exact;
+    return dh == H && dw == W ? kK1CompactIdent : kK1CompactScaled;
+}
+static_assert(vertex_route(480, 640, 480, 640, false, false, true) == kK1CompactIdent, "depth grid == colour grid");
+static_assert(vertex_route(480, 640, 968, 1296, false, false, true) == kK1CompactScaled, "ScanNet's two grids");
+static_assert(vertex_route(480, 640, 480, 640, true, false, true) == kK1ExactHomog &&
+              vertex_route(480, 640, 968, 1296, true, true, false) == kK1ExactHomog &&
+              vertex_route(32767, 32767, 32767, 32767, true, false, true) == kK1ExactHomog, "a homogeneous coordinate, any shape");
+static_assert(vertex_route(480, 640, 480, 640, false, true, true) == kK1Exact &&
+              vertex_route(480, 640, 968, 1296, false, true, true) == kK1Exact, "float64 outputs");
+static_assert(vertex_route(480, 640, 480, 640, false, false, false) == kK1Exact &&
+              vertex_route(480, 640, 968, 1296, false, false, false) == kK1Exact, "a depth scale other than millimetres");
+static_assert(vertex_route(11585, 11585, 11585, 11585, false, false, true) == kK1CompactIdent &&
+              vertex_route(11585, 11585, 32767, 32767, false, false, true) == kK1CompactScaled, "the largest frame of 32-bit offsets");
+static_assert(vertex_route(11586, 11586, 11586, 11586, false, false, true) == kK1Exact &&
+              vertex_route(11586, 11586, 32767, 32767, false, false, true) == kK1Exact, "the first frame beyond them");
+static_assert(vertex_route(32767, 32767, 32767, 32767, false, false, true) == kK1Exact, "the largest frame the API admits");
+
 }  // namespace mspa
 
 using namespace mspa;
@@ -638,22 +530,13 @@ extern "C" int mspa_vertex_visibility_ex(const double *xyz, int64_t n_points, in
     a.igroups = (uint32_t)by;
     a.n_xcd = (uint32_t)n_xcd;
     a.dscale = depth_value_scale;
-    // float64 outputs are DEFINED as the reference's operation order; everything else (bitset, byte mask, counts) takes the
-    // composed + guarded kernel, which reproduces the same integers
-    const bool compact = (int64_t)kImgPerBlock * dh * dw * 2 < 0x7fffffffLL && kImgPerBlock * 12 <= kVThreads;
-    // ... and so do a general homogeneous coordinate and a depth scale other than the millimetre the composed kernels fold in
-    if (homogeneous)
-        hipLaunchKernelGGL(vertex_visibility_kernel<true>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
-    else if (out_uv || out_depth || depth_value_scale != 0.001)
-        hipLaunchKernelGGL(vertex_visibility_kernel<false>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
-    else if (compact && dh == H && dw == W)
-        hipLaunchKernelGGL(vertex_visibility_compact_kernel<true>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
-    else if (compact)
-        hipLaunchKernelGGL(vertex_visibility_compact_kernel<false>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
-    else if (dh == H && dw == W)
-        hipLaunchKernelGGL(vertex_visibility_fast_kernel<true>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
-    else
-        hipLaunchKernelGGL(vertex_visibility_fast_kernel<false>, dim3((uint32_t)blocks), dim3(kVThreads), 0, s, xyz, cam_mats, depth, a);
+    const dim3 grid((uint32_t)blocks), block(kVThreads);
+    switch (vertex_route(dh, dw, H, W, homogeneous != 0, out_uv || out_depth, depth_value_scale == 0.001)) {
+    case kK1ExactHomog: hipLaunchKernelGGL(vertex_visibility_kernel<true>, grid, block, 0, s, xyz, cam_mats, depth, a); break;
+    case kK1Exact: hipLaunchKernelGGL(vertex_visibility_kernel<false>, grid, block, 0, s, xyz, cam_mats, depth, a); break;
+    case kK1CompactIdent: hipLaunchKernelGGL(vertex_visibility_compact_kernel<true>, grid, block, 0, s, xyz, cam_mats, depth, a); break;
+    case kK1CompactScaled: hipLaunchKernelGGL(vertex_visibility_compact_kernel<false>, grid, block, 0, s, xyz, cam_mats, depth, a); break;
+    }
     int rc = check_hip(hipGetLastError(), "vertex_visibility_kernel launch");
     if (rc || !count_from_bits) return rc;
     const int per_block = kVThreads / kWave;

@@ -534,6 +534,47 @@ def test_scene_overlap_tiled(F, n_bits):
     assert np.array_equal(sym, masks.astype(np.int64) @ masks.astype(np.int64).T)
 
 
+@pytest.mark.parametrize("F,n_words", [(33, 66), (5, 2)])
+def test_scene_overlap_tiled_unaligned_table(F, n_words):
+    """The popcount tile kernel's OTHER condition: an even word count (the test above reaches that kernel through odd ones
+    only) in a row table that starts 8 bytes past a 16-byte boundary.  Same integers and the same float64 quotients as the
+    same bits in a fresh, aligned tensor (the matrix-core form) and as NumPy: exact equality.  (33, 66): a ragged second row
+    tile, one whole 64-word slice plus a two-word tail; (5, 2): one partial tile, less than one chunk."""
+    rng = np.random.default_rng(F * 1000 + n_words)
+    masks = rng.random((F, n_words * 64)) < rng.random((F, 1)) * 0.4
+    masks[3] = False                       # an all-zero row, and a second one: their pair has an empty union -> NaN (CFR:136)
+    masks[F // 2] = False
+    words = torch.from_numpy(np.ascontiguousarray(np.packbits(masks, axis=1, bitorder="little").view(np.int64))).to(DEV)
+    buf = torch.zeros((F * n_words + 1,), dtype=torch.int64, device=DEV)
+    bits = buf[1:].view(F, n_words)
+    bits.copy_(words)
+    assert bits.is_contiguous() and bits.data_ptr() % 16 == 8 and words.data_ptr() % 16 == 0
+    got_o, got_i, got_u = engine.scene_overlap(bits, want_counts=True)
+    ref_o, ref_i, ref_u = engine.scene_overlap(words, want_counts=True)
+    torch.cuda.synchronize()
+    assert torch.equal(got_i, ref_i) and torch.equal(got_u, ref_u)
+    assert nan_equal_bits(got_o.cpu().numpy(), ref_o.cpu().numpy())
+    gram = masks.astype(np.int64) @ masks.astype(np.int64).T
+    i, j = np.triu_indices(F, 1)           # all_pairs order (CFR:176-178)
+    cnt = np.diag(gram)
+    inter, uni = gram[i, j], cnt[i] + cnt[j] - gram[i, j]
+    assert np.array_equal(got_i.cpu().numpy(), inter) and np.array_equal(got_u.cpu().numpy(), uni)
+    with np.errstate(invalid="ignore"):
+        want = inter.astype(np.float64) / uni.astype(np.float64) * 100.0
+    assert nan_equal_bits(got_o.cpu().numpy(), want)
+    assert np.isnan(want).sum() == 1
+    # rectangle form and its symmetric shortcut, either table unaligned
+    nb = max(1, F // 3)
+    other = rng.random((nb, n_words * 64)) < 0.3
+    words_b = torch.from_numpy(np.ascontiguousarray(np.packbits(other, axis=1, bitorder="little").view(np.int64))).to(DEV)
+    want_rect = other.astype(np.int64) @ masks.astype(np.int64).T
+    assert np.array_equal(engine.overlap_matrix(words_b, bits).cpu().numpy(), want_rect)
+    assert np.array_equal(engine.overlap_matrix(bits, words_b).cpu().numpy(), want_rect.T)
+    assert np.array_equal(engine.overlap_matrix(words_b, words).cpu().numpy(), want_rect)
+    assert np.array_equal(engine.overlap_matrix(bits, bits).cpu().numpy(), gram)
+    assert np.array_equal(engine.overlap_matrix(words, words).cpu().numpy(), gram)
+
+
 @pytest.mark.parametrize("R,n_bits", [(1, 64), (5, 700), (64, 4096 + 64), (70, 131072), (320, 8192 + 64 * 5)])
 def test_bitset_csr_and_transpose(R, n_bits):
     """K9: device-side compaction of a bit matrix and of its transpose == np.nonzero, row by row."""
