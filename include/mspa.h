@@ -646,6 +646,57 @@ int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t ro
                                      uint8_t *out_payload_dev, int32_t *bad_flag_dev, void *stream);
 
 /*
+ * The way back -- a `values` column chunk's pages to the image_to_points rows' bitsets ON THE DEVICE (csrc/parquet_pages.hip;
+ * the Snappy decoder's rules in csrc/snappy_core.h).  What a reader of the index otherwise does on the host: decompress, walk
+ * the PLAIN values, json.loads every list, pack the bits.
+ *
+ * mspa_snappy_decompress_host  the reference: one raw Snappy stream src[0, src_len) (varint(n), then literals with 0 .. 4
+ *   length bytes, copy-1 / copy-2 / copy-4 elements, overlapping copies included; any writer's) -> dst[0, expected).  Returns
+ *   `expected`, or a negative code: -16 the preamble is not varint(expected); -17 an element runs past the input; -18 the
+ *   output would pass `expected`; -19 a copy with offset 0 or one that reaches in front of the output; -20 input left over
+ *   after `expected` bytes; -21 the input ended early; MSPA_EINVAL for a null pointer or a size outside 0 .. 2^31 - 1.
+ *   Nothing outside [src, src + src_len) is read and nothing outside [dst, dst + expected) written, whatever the stream.
+ * mspa_snappy_decompress_device  a batch: stream s is src_dev[offsets_dev[s], + nbytes_dev[s]) (int64; streams may be empty,
+ *   overlap or leave gaps) and decodes to out_dev[out_offsets_dev[s], + out_bytes_dev[s]).  status_dev[s] (int32): 0 decoded,
+ *   byte for byte the host's output; otherwise declined with the host's code, or MSPA_EINVAL for a table entry that does not
+ *   lie inside [0, src_bytes) / [0, out_bytes) (nothing is touched then).  A declined stream's output bytes are unspecified
+ *   but stay inside its own span.  One wave per stream; no copy offset is refused.
+ * mspa_parquet_plain_spans_device  pages_dev holds the needed pages' uncompressed payloads; page p is page_offsets_dev[p] +
+ *   page_bytes_dev[p] (int64) and holds page_values_dev[p] values.  has_levels = 1: the payload opens with u32le(L) and L bytes
+ *   of RLE definition levels, which must be ONE run of ones (varint(num_values << 1), 0x01: no nulls); 0: a required column,
+ *   the values open the payload.  Rows row_begin_dev[p] .. row_begin_dev[p + 1] of the row table (int64, n_pages + 1 entries)
+ *   belong to page p; row_index_dev[r] is the row's value number inside its page, ascending within a page.  Writes
+ *   out_start_dev[r] (position of the value's text in pages_dev) and out_len_dev[r]; page_status_dev[p]: 0, 1 a length or a
+ *   table entry outside the page, 2 levels that are not a run of ones (the rows of such a page get 0 / 0).
+ * mspa_index_rows_brackets_device  row r's text must be '[' ... ']' with JSON white space around: out_inner_start_dev /
+ *   out_inner_len_dev = what lies between; row_status_dev[r] = 1 and an empty span otherwise.
+ * mspa_index_rows_gather_device  the spans back to back: inner_prefix_dev [n_rows + 1] is the exclusive prefix sum of the
+ *   inner lengths and text_bytes its last entry (< 2 GiB) -> out_text_dev, the layout mspa_parse_int_list_flags_device and
+ *   mspa_parse_int_list_device take (with inner_prefix_dev as their text_offsets).
+ * mspa_index_lists_to_bits_device  values_dev (int32) / offsets_dev [n_rows + 1] as mspa_parse_int_list_device leaves them ->
+ *   out_bits_dev [n_rows, n_words] uint64, bit i of word w = vertex 64 w + i (scene.pack_index_lists' layout), rows zeroed
+ *   first; n_points <= 64 n_words.  Lists ascend: a value below its predecessor raises 32 in row_status_dev[r] (cleared by the
+ *   call), a value outside [0, n_points) 64 -- such a row's bits are unspecified; a duplicate is harmless, an empty list a zero row.
+ * All device calls only enqueue on `stream`; a wrong argument (a null pointer included) returns MSPA_EINVAL before anything is
+ * enqueued; no kernel uses atomics.
+ */
+int64_t mspa_snappy_decompress_host(const uint8_t *src, int64_t src_len, uint8_t *dst, int64_t expected);
+int mspa_snappy_decompress_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
+                                  int64_t n_streams, uint8_t *out_dev, int64_t out_bytes, const int64_t *out_offsets_dev,
+                                  const int64_t *out_bytes_dev, int32_t *status_dev, void *stream);
+int mspa_parquet_plain_spans_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
+                                    const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages, int32_t has_levels,
+                                    const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows, int64_t *out_start_dev,
+                                    int64_t *out_len_dev, int32_t *page_status_dev, void *stream);
+int mspa_index_rows_brackets_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *start_dev, const int64_t *len_dev,
+                                    int64_t n_rows, int64_t *out_inner_start_dev, int64_t *out_inner_len_dev, int32_t *row_status_dev,
+                                    void *stream);
+int mspa_index_rows_gather_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *inner_start_dev,
+                                  const int64_t *inner_prefix_dev, int64_t n_rows, uint8_t *out_text_dev, int64_t text_bytes, void *stream);
+int mspa_index_lists_to_bits_device(const int32_t *values_dev, int64_t n_values, const int64_t *offsets_dev, int64_t n_rows,
+                                    int64_t n_points, uint64_t *out_bits_dev, int64_t n_words, int32_t *row_status_dev, void *stream);
+
+/*
  * Image resizing ON THE DEVICE (csrc/resize.hip, arithmetic in csrc/resize_core.h): n 8-bit RGB images of one shape resampled
  * to one target shape, bit-identical to Pillow's `Image.resize((W, H), resample)` for resample = BILINEAR (filter 2) and
  * BICUBIC (filter 3, Pillow's default): float64 weights per axis turned into 22-bit fixed point, a horizontal pass rounded to

@@ -239,6 +239,298 @@ __global__ __launch_bounds__(256) void pack_pages_kernel(const int32_t *__restri
     if (!ok) atomicOr(bad, 1);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ reading
+// The way back: a values chunk's pages -> the image_to_points rows' bitsets, without the text ever leaving the device.
+//
+//   decompress   one wave per Snappy stream (a page of ~1 MiB).  The element chain is sequential, so input position p, output
+//                position o and every element's fields are WAVE-UNIFORM (the head's words come through readfirstlane; every
+//                branch on them is scalar); the 64 lanes only move an element's bytes, one byte each (no element but a long
+//                literal writes more than 64).  Rules and status codes are snappy_core.h's, in decompress()'s order.
+//                - the compressed bytes sit in two registers as a sliding window of 128 aligned words (lane l holds word
+//                  base + l and base + 64 + l), filled by coalesced dword loads every 256 input bytes.  A head (<= 5 bytes)
+//                  comes out of them with v_readlane, a literal of up to 64 bytes with ds_bpermute; longer literals go from
+//                  global memory to global memory;
+//                - a copy reads the wave's own earlier output.  The last kRing = 32 KiB of it are kept in LDS (every output
+//                  byte is stored there as well as in global memory), so a copy with offset <= kRing is an LDS gather -- lane i
+//                  takes byte i mod offset of the period, which covers the overlapping (run-like) copies -- ordered behind the
+//                  stores by wave_lds_fence() (a wave's LDS operations execute in order).  A copy that reaches further back
+//                  (pyarrow's and this library's blocks allow 64 KiB, a copy-4 anything) loads from the output in global
+//                  memory behind `s_waitcnt vmcnt(0)` between a workgroup-scope release / acquire fence pair (which keeps the
+//                  compiler from moving the stores and the load across it; on gfx950 the pair alone emits no wait).  The wait
+//                  returns when every store of the wave has been acknowledged, i.e. has gone through the write-through L1 of
+//                  the CU the wave runs on to L2, and the load that follows is served by that same L1 or the L2 behind it; the
+//                  lines it reads lie at least 32 KiB behind the write front, so no line is read before it was written whole.
+//                  So no offset is declined;
+//                - 32 KiB of LDS per wave: five waves to a CU, 1 280 on the chip.  A scene has 30 - 90 pages; the ring's size does
+//                  not decide the occupancy of such a launch, its hit rate does (the lists repeat 7 - 9 bytes back).
+//   spans        one lane per needed page walks the PLAIN u32 length chain from the page's first value to its last needed row: a
+//                dependent-load chain as long as the values in front of that row.  In this project's files a scene's
+//                image_to_points rows open the chunk (a few values per ~1 MiB page); a row group that mixes scenes may put
+//                ~20 k short point_to_images rows of the scene before in front of them -- 20 k dependent L2 loads, a few
+//                milliseconds for that one lane (not measured on such a file).
+//   brackets     one lane per row: '[' and ']' behind / in front of JSON white space.
+//   gather       the texts between the brackets back to back (what K11's list parser takes), one byte per lane.
+//   lists->bits  one lane per parsed value.  A list ascends, so the values of one 64-bit word are neighbours in the value array:
+//                the lane whose predecessor lies in another word (or that opens the row) ORs the run and stores the word with a
+//                plain store into the zeroed row.  A value below its predecessor or outside [0, n_points) declines the row
+//                (plain stores of a constant: lanes that race write the same thing); a duplicate is harmless.
+// No atomics; every load and store is checked against the buffer it goes to.
+constexpr int kRing = 32768;
+constexpr uint32_t kRingMask = kRing - 1;
+
+__global__ __launch_bounds__(64) void decompress_kernel(const uint8_t *__restrict__ src, int64_t src_bytes,
+                                                        const int64_t *__restrict__ offsets, const int64_t *__restrict__ nbytes,
+                                                        uint8_t *out, int64_t out_bytes, const int64_t *__restrict__ out_offsets,
+                                                        const int64_t *__restrict__ out_sizes, int32_t *__restrict__ status) {
+    __shared__ uint8_t ring[kRing];
+    const int lane = (int)threadIdx.x;
+    const int64_t s = blockIdx.x;
+    const int64_t off = offsets[s], n = nbytes[s], oo = out_offsets[s], expected = out_sizes[s];
+    if (off < 0 || n < 0 || n > kMaxStream || off > src_bytes - n || oo < 0 || expected < 0 || expected > kMaxStream ||
+        oo > out_bytes - expected) {
+        if (lane == 0) status[s] = MSPA_EINVAL;                  // the tables do not describe spans inside src / out: nothing is touched
+        return;
+    }
+    const uint8_t *__restrict__ sp = src + off;
+    uint8_t *dp = out + oo;
+    const int64_t mis = (int64_t)((uintptr_t)sp & 3);
+
+    // the word at stream position rel (rel + mis is a multiple of 4: an aligned load); bytes outside [0, n) read as zero
+    auto fetch = [&](int64_t rel) -> uint32_t {
+        if (rel >= 0 && rel + 4 <= n) return *(const uint32_t *)(sp + rel);
+        uint32_t v = 0;
+        for (int j = 0; j < 4; ++j)
+            if (rel + j >= 0 && rel + j < n) v |= (uint32_t)sp[rel + j] << (8 * j);
+        return v;
+    };
+    // A window register is settled the moment it is loaded: the empty asm statement makes the load's result a use, so the wait
+    // for it stands HERE, once per 256 input bytes, and no load is ever in flight across the element loop -- where the compiler
+    // would otherwise have to drain the memory queue (the wave's output stores with it) in front of every element.
+    auto settle = [](uint32_t &v) { asm volatile("" : "+v"(v)); };
+    int64_t wbase = -mis;                                        // stream position of lane 0's word of W (wave-uniform)
+    uint32_t W = fetch(wbase + 4 * lane), Wn = fetch(wbase + 256 + 4 * lane);
+    settle(W);
+    settle(Wn);
+    // word j (wave-uniform, < 128) of the window
+    auto word = [&](int j) -> uint32_t {
+        const int ju = __builtin_amdgcn_readfirstlane(j);
+        return (uint32_t)(ju < 64 ? __builtin_amdgcn_readlane((int)W, ju) : __builtin_amdgcn_readlane((int)Wn, ju - 64));
+    };
+    // the (at least 5) bytes at window position k (wave-uniform, < 256)
+    auto peek = [&](int k) -> uint64_t {
+        const int ku = __builtin_amdgcn_readfirstlane(k);
+        const uint64_t two = (uint64_t)word(ku >> 2) | (uint64_t)word((ku >> 2) + 1) << 32;
+        return two >> (8 * (ku & 3));
+    };
+
+    int64_t p = 0, o = 0;                                        // wave-uniform
+    int rc = parse_preamble(peek((int)(p - wbase)), n, expected);
+    if (rc > 0) {
+        p = rc;
+        rc = 0;
+    }
+    while (rc == 0 && p < n) {
+        if (o == expected) {
+            rc = kErrTrailing;
+            break;
+        }
+        while (p - wbase >= 256) {
+            if (p - wbase >= 512) {                              // a long literal went by: seat the window anew
+                wbase = p - ((p + mis) & 3);
+                W = fetch(wbase + 4 * lane);
+            } else {
+                wbase += 256;
+                W = Wn;
+            }
+            Wn = fetch(wbase + 256 + 4 * lane);
+            settle(W);
+            settle(Wn);
+        }
+        const int k = (int)(p - wbase);
+        Element e;
+        rc = parse_element(peek(k), n - p, e);
+        if (rc == 0) rc = check_element(e, n - p, o, expected);
+        if (rc != 0) break;
+        const int64_t len = e.len;
+        if (e.literal) {
+            if (len <= 64) {                                     // out of the window: k + head + len <= 255 + 5 + 64
+                const int kk = k + e.head + lane, j = kk >> 2;
+                const uint32_t a = (uint32_t)__shfl((int)W, j & 63), b = (uint32_t)__shfl((int)Wn, j & 63);
+                const uint8_t byte = (uint8_t)((j < 64 ? a : b) >> (8 * (kk & 3)));
+                if (lane < len) {
+                    dp[o + lane] = byte;
+                    ring[(uint32_t)(o + lane) & kRingMask] = byte;
+                }
+            } else {
+                for (int64_t done = 0; done < len; done += 64) {
+                    const int64_t i = done + lane;
+                    if (i < len) {
+                        const uint8_t byte = sp[p + e.head + i];
+                        dp[o + i] = byte;
+                        ring[(uint32_t)(o + i) & kRingMask] = byte;
+                    }
+                }
+            }
+            p += e.head + len;
+        } else if (e.offset <= kRing) {                          // a copy of 1 .. 64 bytes out of the ring: one step
+            const int rem = e.offset >= len ? lane : lane % (int)e.offset;
+            uint8_t byte = 0;
+            if (lane < len) byte = ring[(uint32_t)(o - e.offset + rem) & kRingMask];
+            wave_lds_fence();
+            if (lane < len) {
+                dp[o + lane] = byte;
+                ring[(uint32_t)(o + lane) & kRingMask] = byte;
+            }
+            p += e.head;
+        } else {                                                 // ... from further back: the wave's own stores, out of global memory
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // every store of this wave has been acknowledged
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (lane < len) {
+                const uint8_t byte = dp[o - e.offset + lane];    // offset > kRing >= len: source and target apart
+                dp[o + lane] = byte;
+                ring[(uint32_t)(o + lane) & kRingMask] = byte;
+            }
+            p += e.head;
+        }
+        o += len;
+        wave_lds_fence();
+    }
+    if (rc == 0 && o < expected) rc = kErrShort;
+    if (lane == 0) status[s] = rc;
+}
+
+constexpr int32_t kPageBounds = 1;       // a length runs past the page, or the tables do not describe it
+constexpr int32_t kPageLevels = 2;       // the definition levels are not one run of ones
+constexpr int32_t kRowBrackets = 1;      // a row's text is not [ ... ]
+constexpr int32_t kRowOrder = 32;        // lists->bits: a value below its predecessor     (K11's parser owns bits 2 .. 16)
+constexpr int32_t kRowRange = 64;        // lists->bits: a value outside [0, n_points)
+
+__device__ __forceinline__ bool json_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
+
+__global__ __launch_bounds__(64) void plain_spans_kernel(const uint8_t *__restrict__ pages, int64_t pages_bytes,
+                                                         const int64_t *__restrict__ page_off, const int64_t *__restrict__ page_size,
+                                                         const int64_t *__restrict__ page_values, int64_t n_pages, int32_t has_levels,
+                                                         const int64_t *__restrict__ row_begin, const int64_t *__restrict__ row_index,
+                                                         int64_t n_rows, int64_t *__restrict__ out_start, int64_t *__restrict__ out_len,
+                                                         int32_t *__restrict__ page_status) {
+    const int64_t pg = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (pg >= n_pages) return;
+    const int64_t off = page_off[pg], size = page_size[pg], nv = page_values[pg];
+    int64_t r0 = row_begin[pg], r1 = row_begin[pg + 1];
+    int32_t bad = 0;
+    if (r0 < 0 || r1 < r0 || r1 > n_rows) {
+        page_status[pg] = kPageBounds;
+        return;
+    }
+    if (off < 0 || size < 0 || off > pages_bytes - size || nv < 0) bad = kPageBounds;
+    const uint8_t *__restrict__ q = pages + off;
+    int64_t pos = 0;
+    if (!bad && has_levels) {
+        const int32_t head = page_head_len(nv);
+        if (head > size) bad = kPageBounds;
+        for (int32_t r = 0; !bad && r < head; ++r)
+            if (q[r] != page_head_byte(nv, r)) bad = kPageLevels;
+        pos = head;
+    }
+    int64_t v = 0, r = r0;
+    for (; !bad && r < r1; ++r) {
+        const int64_t target = row_index[r];
+        if (target < v || target >= nv) {
+            bad = kPageBounds;
+            break;
+        }
+        for (;; ++v) {
+            if (pos > size - 4) {
+                bad = kPageBounds;
+                break;
+            }
+            const int64_t len = load32(q + pos);
+            if (len > size - pos - 4) {
+                bad = kPageBounds;
+                break;
+            }
+            if (v == target) {
+                out_start[r] = off + pos + 4;
+                out_len[r] = len;
+            }
+            pos += 4 + len;
+            if (v == target) break;
+        }
+        if (bad) break;
+        ++v;
+    }
+    for (; bad && r < r1; ++r) {                                 // the rows this page did not give
+        out_start[r] = 0;
+        out_len[r] = 0;
+    }
+    page_status[pg] = bad;
+}
+
+__global__ __launch_bounds__(64) void row_brackets_kernel(const uint8_t *__restrict__ pages, int64_t pages_bytes,
+                                                          const int64_t *__restrict__ start, const int64_t *__restrict__ len, int64_t n_rows,
+                                                          int64_t *__restrict__ inner_start, int64_t *__restrict__ inner_len,
+                                                          int32_t *__restrict__ row_status) {
+    const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n_rows) return;
+    int64_t a = start[r], z = a + len[r];
+    bool ok = a >= 0 && len[r] >= 2 && len[r] <= pages_bytes && a <= pages_bytes - len[r];
+    if (ok) {
+        while (a < z && json_space(pages[a])) ++a;
+        while (z > a && json_space(pages[z - 1])) --z;
+        ok = z - a >= 2 && pages[a] == '[' && pages[z - 1] == ']';
+    }
+    inner_start[r] = ok ? a + 1 : 0;
+    inner_len[r] = ok ? z - a - 2 : 0;
+    row_status[r] = ok ? 0 : kRowBrackets;
+}
+
+__global__ __launch_bounds__(256) void row_gather_kernel(const uint8_t *__restrict__ pages, int64_t pages_bytes,
+                                                         const int64_t *__restrict__ inner_start, const int64_t *__restrict__ prefix,
+                                                         int64_t n_rows, int64_t total, uint8_t *__restrict__ text) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    int64_t lo = 0, hi = n_rows;                                 // invariant: prefix[lo] <= i < prefix[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (prefix[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const int64_t from = inner_start[lo] + (i - prefix[lo]);
+    text[i] = (from >= 0 && from < pages_bytes) ? pages[from] : (uint8_t)0;      // a 0 byte is no list: the parser declines the row
+}
+
+__global__ __launch_bounds__(256) void lists_to_bits_kernel(const int32_t *__restrict__ values, int64_t n_values,
+                                                            const int64_t *__restrict__ offsets, int64_t n_rows, int64_t n_points,
+                                                            uint64_t *__restrict__ bits, int64_t n_words, int32_t *__restrict__ row_status) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_values) return;
+    int64_t lo = 0, hi = n_rows;                                 // the row: the last one with offsets[row] <= i
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (offsets[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const int64_t first = offsets[lo];
+    int64_t end = offsets[lo + 1];
+    if (end > n_values) end = n_values;
+    if (i < first || i >= end) return;                           // offsets that do not hold this value: no row's
+    const int64_t v = values[i], prev = (i > first && i > 0) ? (int64_t)values[i - 1] : -1;
+    if (v < prev) row_status[lo] = kRowOrder;
+    if (v < 0 || v >= n_points) {
+        row_status[lo] = kRowRange;
+        return;
+    }
+    if (prev >= 0 && (prev >> 6) == (v >> 6)) return;            // the lane in front owns this word
+    uint64_t w = 0;
+    for (int64_t j = i; j < end; ++j) {
+        const int64_t u = values[j];
+        if (u < 0 || (u >> 6) != (v >> 6)) break;
+        w |= 1ull << (u & 63);
+    }
+    bits[lo * n_words + (v >> 6)] = w;                           // v < n_points <= 64 n_words
+}
+
 }  // namespace snappy
 }  // namespace mspa
 
@@ -335,4 +627,85 @@ extern "C" int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev,
     hipLaunchKernelGGL(snappy::pack_pages_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, text_offsets_dev,
                        rows, data_dev, data_bytes, cuts_dev, payload_offsets_dev, n_pages, payload_bytes, out_payload_dev, bad_flag_dev);
     return check_hip(hipGetLastError(), "mspa_parquet_string_pages_device");
+}
+
+extern "C" int64_t mspa_snappy_decompress_host(const uint8_t *src, int64_t src_len, uint8_t *dst, int64_t expected) {
+    if (src_len < 0 || src_len > snappy::kMaxStream || expected < 0 || expected > snappy::kMaxStream)
+        return fail(MSPA_EINVAL, "mspa_snappy_decompress_host: 0 <= src_len, expected < 2^31");
+    if ((src_len > 0 && !src) || (expected > 0 && !dst)) return fail(MSPA_EINVAL, "mspa_snappy_decompress_host: null pointer");
+    return snappy::decompress(src, src_len, dst, expected);
+}
+
+extern "C" int mspa_snappy_decompress_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
+                                             int64_t n_streams, uint8_t *out_dev, int64_t out_bytes, const int64_t *out_offsets_dev,
+                                             const int64_t *out_bytes_dev, int32_t *status_dev, void *stream) {
+    if (src_bytes < 0 || out_bytes < 0 || n_streams < 0 || n_streams > 0x7fffffffLL)
+        return fail(MSPA_EINVAL, "mspa_snappy_decompress_device: bad size");
+    if (n_streams == 0) return MSPA_OK;
+    if (!offsets_dev || !nbytes_dev || !out_offsets_dev || !out_bytes_dev || !status_dev || (src_bytes > 0 && !src_dev) ||
+        (out_bytes > 0 && !out_dev))
+        return fail(MSPA_EINVAL, "mspa_snappy_decompress_device: null pointer");
+    hipLaunchKernelGGL(snappy::decompress_kernel, dim3((unsigned)n_streams), dim3(64), 0, (hipStream_t)stream, src_dev, src_bytes, offsets_dev,
+                       nbytes_dev, out_dev, out_bytes, out_offsets_dev, out_bytes_dev, status_dev);
+    return check_hip(hipGetLastError(), "mspa_snappy_decompress_device");
+}
+
+extern "C" int mspa_parquet_plain_spans_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
+                                               const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages,
+                                               int32_t has_levels, const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows,
+                                               int64_t *out_start_dev, int64_t *out_len_dev, int32_t *page_status_dev, void *stream) {
+    if (pages_bytes < 0 || n_pages < 0 || n_rows < 0 || n_pages > (int64_t)0x7fffffff * 64 || (has_levels != 0 && has_levels != 1))
+        return fail(MSPA_EINVAL, "mspa_parquet_plain_spans_device: bad size");
+    if (n_pages == 0) return n_rows == 0 ? MSPA_OK : fail(MSPA_EINVAL, "mspa_parquet_plain_spans_device: rows without pages");
+    if (!page_offsets_dev || !page_bytes_dev || !page_values_dev || !row_begin_dev || !page_status_dev || (pages_bytes > 0 && !pages_dev) ||
+        (n_rows > 0 && (!row_index_dev || !out_start_dev || !out_len_dev)))
+        return fail(MSPA_EINVAL, "mspa_parquet_plain_spans_device: null pointer");
+    hipLaunchKernelGGL(snappy::plain_spans_kernel, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, (hipStream_t)stream, pages_dev, pages_bytes,
+                       page_offsets_dev, page_bytes_dev, page_values_dev, n_pages, has_levels, row_begin_dev, row_index_dev, n_rows, out_start_dev,
+                       out_len_dev, page_status_dev);
+    return check_hip(hipGetLastError(), "mspa_parquet_plain_spans_device");
+}
+
+extern "C" int mspa_index_rows_brackets_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *start_dev, const int64_t *len_dev,
+                                               int64_t n_rows, int64_t *out_inner_start_dev, int64_t *out_inner_len_dev, int32_t *row_status_dev,
+                                               void *stream) {
+    if (pages_bytes < 0 || n_rows < 0 || n_rows > (int64_t)0x7fffffff * 64) return fail(MSPA_EINVAL, "mspa_index_rows_brackets_device: bad size");
+    if (n_rows == 0) return MSPA_OK;
+    if (!start_dev || !len_dev || !out_inner_start_dev || !out_inner_len_dev || !row_status_dev || (pages_bytes > 0 && !pages_dev))
+        return fail(MSPA_EINVAL, "mspa_index_rows_brackets_device: null pointer");
+    hipLaunchKernelGGL(snappy::row_brackets_kernel, dim3((unsigned)((n_rows + 63) / 64)), dim3(64), 0, (hipStream_t)stream, pages_dev, pages_bytes,
+                       start_dev, len_dev, n_rows, out_inner_start_dev, out_inner_len_dev, row_status_dev);
+    return check_hip(hipGetLastError(), "mspa_index_rows_brackets_device");
+}
+
+extern "C" int mspa_index_rows_gather_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *inner_start_dev,
+                                             const int64_t *inner_prefix_dev, int64_t n_rows, uint8_t *out_text_dev, int64_t text_bytes,
+                                             void *stream) {
+    if (pages_bytes < 0 || n_rows < 0 || text_bytes < 0 || text_bytes > 0x7fffffffLL)
+        return fail(MSPA_EINVAL, "mspa_index_rows_gather_device: bad size (less than 2 GiB of text a call)");
+    if (text_bytes == 0) return MSPA_OK;
+    if (n_rows == 0) return fail(MSPA_EINVAL, "mspa_index_rows_gather_device: text without rows");
+    if (!pages_dev || !inner_start_dev || !inner_prefix_dev || !out_text_dev) return fail(MSPA_EINVAL, "mspa_index_rows_gather_device: null pointer");
+    hipLaunchKernelGGL(snappy::row_gather_kernel, dim3((unsigned)((text_bytes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pages_dev,
+                       pages_bytes, inner_start_dev, inner_prefix_dev, n_rows, text_bytes, out_text_dev);
+    return check_hip(hipGetLastError(), "mspa_index_rows_gather_device");
+}
+
+extern "C" int mspa_index_lists_to_bits_device(const int32_t *values_dev, int64_t n_values, const int64_t *offsets_dev, int64_t n_rows,
+                                               int64_t n_points, uint64_t *out_bits_dev, int64_t n_words, int32_t *row_status_dev, void *stream) {
+    if (n_values < 0 || n_rows < 0 || n_points < 0 || n_words < 0 || n_values > (int64_t)0x7fffffff * 256 || n_points > 64 * n_words ||
+        (n_words > 0 && n_rows > ((int64_t)1 << 40) / n_words))
+        return fail(MSPA_EINVAL, "mspa_index_lists_to_bits_device: bad size (n_points <= 64 n_words)");
+    if (n_rows == 0) return n_values == 0 ? MSPA_OK : fail(MSPA_EINVAL, "mspa_index_lists_to_bits_device: values without rows");
+    if (!offsets_dev || !row_status_dev || (n_values > 0 && !values_dev) || (n_words > 0 && !out_bits_dev))
+        return fail(MSPA_EINVAL, "mspa_index_lists_to_bits_device: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_hip(hipMemsetAsync(row_status_dev, 0, (size_t)n_rows * 4, st), "mspa_index_lists_to_bits_device: clearing the status");
+    if (rc == MSPA_OK && n_words > 0)
+        rc = check_hip(hipMemsetAsync(out_bits_dev, 0, (size_t)n_rows * (size_t)n_words * 8, st), "mspa_index_lists_to_bits_device: clearing the rows");
+    if (rc) return rc;
+    if (n_values > 0)
+        hipLaunchKernelGGL(snappy::lists_to_bits_kernel, dim3((unsigned)((n_values + 255) / 256)), dim3(256), 0, st, values_dev, n_values, offsets_dev,
+                           n_rows, n_points, out_bits_dev, n_words, row_status_dev);
+    return check_hip(hipGetLastError(), "mspa_index_lists_to_bits_device");
 }

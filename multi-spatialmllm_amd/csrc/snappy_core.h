@@ -1,4 +1,4 @@
-// Snappy compression and parquet v1 data pages for the visibility index's `values` column: the arithmetic shared by the device
+// Snappy compression, Snappy decoding and parquet v1 data pages for the visibility index's `values` column: the arithmetic shared by the device
 // kernels of parquet_pages.hip (K12) and the host reference.  Everything that decides an output byte is an MSPA_HD function here,
 // so that a plain C++ build of this header is the reference the device must equal byte for byte.
 //
@@ -124,6 +124,98 @@ MSPA_HD int32_t match_len(const uint8_t *s, int32_t q, int32_t p, int32_t nb) {
     int32_t len = 4;
     while (p + len < nb && s[q + len] == s[p + len]) ++len;
     return len;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- decoding
+// The decoder reads ANY raw Snappy stream (Google's, pyarrow's, this file's): varint(n), then elements until the input ends.
+//   tag & 3 == 0  literal: len - 1 = tag >> 2 when that is < 60, else the next (tag >> 2) - 59 bytes (1 .. 4), little endian;
+//   tag & 3 == 1  copy-1:  len = 4 + (tag >> 2 & 7), offset = (tag >> 5) << 8 | next byte;
+//   tag & 3 == 2  copy-2:  len = 1 + (tag >> 2), offset = next 2 bytes;       tag & 3 == 3  copy-4: the same with 4 offset bytes.
+// A copy's source may overlap its target (offset < len): byte i of the copy is byte i mod offset of the `offset` bytes in front.
+// The rules below are everything that decides a status; the host loop (decompress) and the device kernel both go through
+// them in the same order, so the two decline the same streams with the same code.  Nothing is read outside [src, src + src_len)
+// and nothing written outside [dst, dst + expected).
+constexpr int kErrPreamble = -16;     // the preamble is not varint(expected) (or does not end inside the input)
+constexpr int kErrTruncated = -17;    // an element (its tag, its length / offset bytes or a literal's bytes) runs past the input
+constexpr int kErrOverrun = -18;      // an element would write beyond `expected` bytes
+constexpr int kErrOffset = -19;       // a copy with offset 0, or one that reaches in front of the output's first byte
+constexpr int kErrTrailing = -20;     // input left over after `expected` bytes were written
+constexpr int kErrShort = -21;        // the input ended before `expected` bytes were written
+
+struct Element {
+    int32_t head;       // tag and length / offset bytes
+    int64_t len;        // bytes it writes (>= 1)
+    int64_t offset;     // 0 for a literal (whose len bytes follow the head)
+    bool literal;
+};
+
+// `bytes`: the input's next (up to) 8 bytes, little endian, zero where the input has ended; `avail` >= 1: how many input bytes
+// are left.  Returns 0, or kErrTruncated when the head itself is cut off.
+MSPA_HD int parse_element(uint64_t bytes, int64_t avail, Element &e) {
+    const uint32_t tag = (uint32_t)bytes & 255u, kind = tag & 3u, m = tag >> 2;
+    const uint64_t rest = bytes >> 8;
+    const int32_t lit_extra = m < 60u ? 0 : (int32_t)m - 59;
+    const int32_t extra = kind == 0 ? lit_extra : kind == 1 ? 1 : kind == 2 ? 2 : 4;
+    const uint64_t field = rest & (extra == 4 ? 0xFFFFFFFFull : (1ull << (8 * extra)) - 1);      // the length / offset bytes
+    const int64_t lit_len = (lit_extra == 0 ? (int64_t)m : (int64_t)field) + 1;
+    const int64_t copy_len = kind == 1 ? 4 + (int64_t)(m & 7u) : 1 + (int64_t)m;
+    const int64_t copy_offset = kind == 1 ? (int64_t)((uint64_t)(tag >> 5) << 8 | field) : (int64_t)field;
+    e.head = 1 + extra;
+    e.len = kind == 0 ? lit_len : copy_len;
+    e.offset = kind == 0 ? 0 : copy_offset;
+    e.literal = kind == 0;
+    return e.head > avail ? kErrTruncated : 0;
+}
+
+// A parsed element against the input left (`avail`, counted from its tag), the bytes written so far and the stream's size.
+MSPA_HD int check_element(const Element &e, int64_t avail, int64_t written, int64_t expected) {
+    if (e.literal) {
+        if (e.len > avail - e.head) return kErrTruncated;
+    } else if (e.offset == 0 || e.offset > written) {
+        return kErrOffset;
+    }
+    return e.len > expected - written ? kErrOverrun : 0;
+}
+
+// The preamble: `bytes` / `avail` as for parse_element (avail may be 0).  Returns its length (1 .. 5), or kErrPreamble.
+MSPA_HD int parse_preamble(uint64_t bytes, int64_t avail, int64_t expected) {
+    uint64_t v = 0;
+    for (int i = 0; i < 5 && i < avail; ++i) {
+        const uint32_t b = (uint32_t)(bytes >> (8 * i)) & 255u;
+        v |= (uint64_t)(b & 127u) << (7 * i);
+        if (b < 128u) return v == (uint64_t)expected ? i + 1 : kErrPreamble;
+    }
+    return kErrPreamble;
+}
+
+// The next (up to) 8 bytes of s[p, n), zero beyond n.
+MSPA_HD uint64_t load_le(const uint8_t *s, int64_t p, int64_t n) {
+    uint64_t v = 0;
+    for (int i = 0; i < 8 && p + i < n; ++i) v |= (uint64_t)s[p + i] << (8 * i);
+    return v;
+}
+
+// The reference: src[0, src_len) -> dst[0, expected).  Returns `expected`, or one of the codes above.
+MSPA_HD int64_t decompress(const uint8_t *src, int64_t src_len, uint8_t *dst, int64_t expected) {
+    const int pre = parse_preamble(load_le(src, 0, src_len), src_len, expected);
+    if (pre < 0) return pre;
+    int64_t p = pre, o = 0;
+    while (p < src_len) {
+        if (o == expected) return kErrTrailing;
+        Element e;
+        int rc = parse_element(load_le(src, p, src_len), src_len - p, e);
+        if (rc == 0) rc = check_element(e, src_len - p, o, expected);
+        if (rc != 0) return rc;
+        if (e.literal) {
+            for (int64_t i = 0; i < e.len; ++i) dst[o + i] = src[p + e.head + i];
+            p += e.head + e.len;
+        } else {
+            for (int64_t i = 0; i < e.len; ++i) dst[o + i] = dst[o + i - e.offset];
+            p += e.head;
+        }
+        o += e.len;
+    }
+    return o < expected ? kErrShort : o;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pages

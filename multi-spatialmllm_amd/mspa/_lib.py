@@ -20,6 +20,8 @@ JPEG_DESC_BYTES = 4224
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
+# csrc/snappy_core.h: what mspa_snappy_decompress_host returns for, and the device writes as the status of, a stream it declines
+SNAPPY_EPREAMBLE, SNAPPY_ETRUNCATED, SNAPPY_EOVERRUN, SNAPPY_EOFFSET, SNAPPY_ETRAILING, SNAPPY_ESHORT = -16, -17, -18, -19, -20, -21
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
@@ -149,6 +151,14 @@ _SIGNATURES = {
     "mspa_parquet_page_payload_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64]),
     "mspa_parquet_string_pages_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                                  c_void_p, c_void_p]),
+    "mspa_snappy_decompress_host": (c_int64, [c_void_p, c_int64, c_void_p, c_int64]),
+    "mspa_snappy_decompress_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
+    "mspa_parquet_plain_spans_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                                c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_index_rows_brackets_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_index_rows_gather_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "mspa_index_lists_to_bits_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mspa_track_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                         c_double, c_double, c_void_p, c_void_p, c_void_p]),
 }

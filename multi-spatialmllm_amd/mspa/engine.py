@@ -915,6 +915,99 @@ def parquet_string_pages_device(text_offsets: torch.Tensor, data: torch.Tensor, 
     return out
 
 
+def snappy_decompress_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, out_sizes: torch.Tensor):
+    """A batch of raw Snappy streams decoded on the device, one wave per stream: stream s is ``src[offsets[s] : offsets[s] +
+    nbytes[s]]`` (``src`` uint8, the tables int64, all on the device; streams may be empty, overlap or leave gaps) and decodes to
+    ``out_sizes[s]`` bytes (what its preamble must say).  Returns (out uint8 [sum of out_sizes], out_offsets int64 [n + 1],
+    status int32 [n]) on the device: stream s is ``out[out_offsets[s] : out_offsets[s + 1]]`` where ``status[s] == 0`` -- byte for
+    byte mspa_snappy_decompress_host -- and was declined with the host's code (``_lib.SNAPPY_E*``; MSPA_EINVAL for a table entry
+    outside ``src``) otherwise.  One small read-back (the size to allocate)."""
+    lib = _lib.load()
+    n = _check_streams(offsets, nbytes)
+    _check("src", src, torch.uint8, (None,))
+    _check("out_sizes", out_sizes, torch.int64, (n,))
+    dev = src.device
+    out_offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    status = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.uint8, device=dev), out_offsets, status
+    torch.cumsum(out_sizes.clamp(min=0), dim=0, out=out_offsets[1:])      # a negative size is the kernel's to refuse (MSPA_EINVAL)
+    total = int(out_offsets[-1].item())
+    out = torch.empty((max(total, 1),), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mspa_snappy_decompress_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), n, _ptr(out),
+                                                 total, _ptr(out_offsets), _ptr(out_sizes), _ptr(status), _stream_ptr()))
+    return out[:total], out_offsets, status
+
+
+def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
+                       row_begin: torch.Tensor, row_index: torch.Tensor, n_points: Optional[int] = None, has_levels: bool = True):
+    """Rows of the visibility index straight from their pages to bitset rows, on the device.  ``pages`` (uint8) holds the
+    uncompressed payloads of v1 PLAIN BYTE_ARRAY data pages: page p is ``pages[page_offsets[p] : + page_sizes[p]]`` with
+    ``page_values[p]`` values (``has_levels``: behind RLE definition levels that must be one run of ones).  Rows ``row_begin[p] ..
+    row_begin[p + 1]`` of the row table belong to page p and ``row_index[r]`` is row r's value number inside its page, ascending
+    within a page (all int64, on the device).  Each row's text must be a JSON list of ascending non-negative integers.
+
+    mspa_parquet_plain_spans_device -> mspa_index_rows_brackets_device -> (prefix sum) -> mspa_index_rows_gather_device ->
+    mspa_parse_int_list_flags_device -> (prefix sum) -> mspa_parse_int_list_device -> mspa_index_lists_to_bits_device.
+
+    Returns a dict: ``bits`` int64 [rows, ceil(n_points / 64)] on the device (scene.pack_index_lists' layout), ``n_points``
+    (given, or 1 + the largest parsed value), ``page_status`` / ``row_status`` (int32 numpy; non-zero = declined: that page's
+    rows / that row belong to the host path, their ``bits`` are unspecified), ``start`` / ``length`` (int64, device: where each
+    row's text lies in ``pages``).  Less than 2 GiB of list text a call.  Synchronises (three or four small read-backs)."""
+    lib = _lib.load()
+    n_pages = _check_streams(page_offsets, page_sizes)
+    _check("pages", pages, torch.uint8, (None,))
+    _check("page_values", page_values, torch.int64, (n_pages,))
+    _check("row_begin", row_begin, torch.int64, (n_pages + 1,))
+    n_rows = _check("row_index", row_index, torch.int64, (None,)).shape[0]
+    _require(n_points is None or 0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
+    _require(n_pages > 0 or n_rows == 0, "rows need pages")
+    dev, st = pages.device, _stream_ptr()
+    i64 = dict(dtype=torch.int64, device=dev)
+    start, length = torch.zeros((n_rows,), **i64), torch.zeros((n_rows,), **i64)
+    inner_start, inner_len = torch.empty((n_rows,), **i64), torch.empty((n_rows,), **i64)
+    page_status = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    status = torch.zeros((3, max(n_rows, 1)), dtype=torch.int32, device=dev)                 # brackets, parser, bits
+    if n_rows == 0:
+        n_points = int(n_points or 1)
+        return {"bits": torch.zeros((0, (n_points + 63) // 64), **i64), "n_points": n_points, "page_status": np.zeros(n_pages, np.int32),
+                "row_status": np.zeros(0, np.int32), "start": start, "length": length}
+    pages_ptr = _ptr(pages) if pages.numel() else None
+    _lib.check(lib.mspa_parquet_plain_spans_device(pages_ptr, pages.numel(), _ptr(page_offsets), _ptr(page_sizes), _ptr(page_values), n_pages,
+                                                   1 if has_levels else 0, _ptr(row_begin), _ptr(row_index), n_rows, _ptr(start), _ptr(length),
+                                                   _ptr(page_status), st))
+    _lib.check(lib.mspa_index_rows_brackets_device(pages_ptr, pages.numel(), _ptr(start), _ptr(length), n_rows, _ptr(inner_start),
+                                                   _ptr(inner_len), _ptr(status[0]), st))
+    prefix = torch.zeros((n_rows + 1,), **i64)                                                # torch as plumbing: the prefix sums
+    torch.cumsum(inner_len, dim=0, out=prefix[1:])
+    n_bytes = int(prefix[-1].item())
+    _require(n_bytes <= 0x7fffffff, "index_rows_to_bits: 2 GiB of list text or more in one call")
+    text = torch.empty((max(n_bytes, 1),), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mspa_index_rows_gather_device(pages_ptr, pages.numel(), _ptr(inner_start), _ptr(prefix), n_rows, _ptr(text), n_bytes, st))
+    flags = torch.empty((max(n_bytes, 1),), **i64)
+    _lib.check(lib.mspa_parse_int_list_flags_device(_ptr(text), _ptr(prefix), n_rows, n_bytes, _ptr(flags), _ptr(status[1]), st))
+    T = torch.zeros((n_bytes + 1,), **i64)
+    if n_bytes:
+        torch.cumsum(flags[:n_bytes], dim=0, out=T[1:])
+    del flags
+    count = int(T[-1].item()) & 0xffffffff
+    values = torch.empty((max(count, 1),), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n_rows + 1,), **i64)
+    _lib.check(lib.mspa_parse_int_list_device(_ptr(text), _ptr(prefix), n_rows, n_bytes, _ptr(T), None, _ptr(values), count, _ptr(offsets),
+                                              _ptr(status[1]), st))
+    del T
+    if n_points is None:
+        n_points = (int(values[:count].max().item()) if count else 0) + 1
+    n_points = int(n_points)
+    n_words = (n_points + 63) // 64
+    bits = torch.empty((n_rows, n_words), **i64)
+    _lib.check(lib.mspa_index_lists_to_bits_device(_ptr(values), count, _ptr(offsets), n_rows, n_points, _ptr(bits) if n_words else None, n_words,
+                                                   _ptr(status[2]), st))
+    row_status = (status[0] | status[1] | status[2])[:n_rows]
+    back = torch.cat([page_status, row_status]).cpu().numpy()
+    return {"bits": bits, "n_points": n_points, "page_status": back[:n_pages], "row_status": back[n_pages:], "start": start, "length": length}
+
+
 def bits_transpose(bits: torch.Tensor) -> torch.Tensor:
     """K9: [R, n_words] int64 bit matrix -> its transpose [n_words * 64, ceil(R / 64)] (padding bits zero)."""
     R, n_words = _check_bits("bits", bits)

@@ -30,6 +30,17 @@ def encode_mode() -> str:
     return value
 
 
+def decode_mode() -> str:
+    """Who turns the index's ``image_to_points`` rows back into bitsets: "host" (the default: pyarrow reads the row group,
+    ``json.loads`` and ``scene.pack_index_lists`` on the CPU) or "device" (``MSPA_VISINDEX_DECODE=device``:
+    ``SceneRowGroups.scene_bits`` uploads the needed pages as they lie in the file and decompresses, parses and packs them on
+    the GPU).  Read at every call."""
+    value = os.environ.get("MSPA_VISINDEX_DECODE", "host").strip().lower() or "host"
+    if value not in ("host", "device"):
+        raise ValueError(f"MSPA_VISINDEX_DECODE={value!r}: expected 'host' or 'device'")
+    return value
+
+
 @dataclasses.dataclass
 class VisibilityCSR:
     image_ids: List[str]
@@ -238,6 +249,20 @@ class SceneRowGroups:
         self._by_scene: Dict[str, List[int]] = {}
         self._mixed: List[tuple] = []                       # (row group, first scene, last scene)
         self._cache: Dict[int, Dict[str, Dict[str, str]]] = {}
+        # what ``scene_bits`` needs besides: the file itself (raw page bytes), where ``values`` sits and how it is nested
+        self._path = os.fspath(parquet_file) if isinstance(parquet_file, (str, os.PathLike)) else None
+        self._values_col = self.file.schema_arrow.get_field_index("values")
+        self._page_tables: Dict[int, dict] = {}
+        self._keys: Dict[int, object] = {}
+        self.decode_stats = {"scenes": 0, "scenes_declined": 0, "rows": 0, "rows_declined": 0, "h2d_bytes": 0}
+        self.last_decline: Optional[str] = None
+        self.stage_times: Optional[dict] = None
+        self._stage_start = 0.0
+        self._has_levels, self._device_schema = False, False
+        if self._values_col >= 0 and self.file.metadata.num_columns == len(self.file.schema_arrow.names):
+            leaf = self.file.schema.column(self._values_col)
+            self._has_levels = leaf.max_definition_level == 1
+            self._device_schema = (leaf.physical_type == "BYTE_ARRAY" and leaf.max_repetition_level == 0 and leaf.max_definition_level <= 1)
         for g in range(md.num_row_groups):
             st = md.row_group(g).column(key_col).statistics
             if st is None or not st.has_min_max:
@@ -248,6 +273,261 @@ class SceneRowGroups:
                 self._by_scene.setdefault(lo, []).append(g)
             else:
                 self._mixed.append((g, lo, hi))
+
+    # ------------------------------------------------------------------------------------------------ pages -> bitsets, on the device
+    # parquet.thrift numbers
+    _DATA_PAGE, _PLAIN, _RLE = 0, 0, 3
+    _CODECS = {"UNCOMPRESSED": 0, "SNAPPY": 1}
+
+    def values_pages(self, g: int) -> dict:
+        """The page table of row group ``g``'s ``values`` column chunk, from the thrift page headers (``parquet_splice._Reader``):
+        ``start`` (the chunk's position in the file), ``bytes`` (its compressed size) and, per page in file order, int64 arrays
+        ``pos`` (the payload's position inside the chunk), ``compressed``, ``uncompressed``, ``num_values``, ``type``,
+        ``encoding`` (-1 where the page has none), ``levels`` (a v1 data page's definition-level encoding, else -1) and
+        ``first_row`` (rows of the group in front of it; ``n_pages + 1`` entries), ``codec`` (the chunk's, as pyarrow names it).
+        Cached: a few numbers per page."""
+        if g in self._page_tables:
+            return self._page_tables[g]
+        from . import parquet_splice as PS
+        if self._path is None:
+            raise ValueError("visindex: the page table needs the index as a file on disk")
+        col = self.file.metadata.row_group(g).column(self._values_col)
+        start = col.data_page_offset
+        if col.has_dictionary_page and col.dictionary_page_offset:
+            start = min(start, col.dictionary_page_offset)
+        size = col.total_compressed_size
+        with open(self._path, "rb") as f:
+            f.seek(start)
+            chunk = f.read(size)
+        if len(chunk) != size:
+            raise ValueError("visindex: the values chunk ends beyond the file")
+        self._mark("file_read")
+        rows, p = [], 0
+        while p < size:
+            r = PS._Reader(chunk, p)
+            h = r.struct()
+            v1, v2, dic = PS._get(h, 5), PS._get(h, 8), PS._get(h, 7)
+            body = v1 or v2 or dic or []
+            comp = PS._get(h, 3)
+            rows.append((r.p, comp, PS._get(h, 2), PS._get(body, 1, 0) if (v1 or v2) else 0, PS._get(h, 1),
+                         PS._get(body, 4 if v2 else 2, -1) if body else -1, PS._get(v1, 3, -1) if v1 else -1))
+            p = r.p + comp
+        if p != size:
+            raise ValueError("visindex: the page headers do not add up to the values chunk")
+        t = np.array(rows, dtype=np.int64).reshape(-1, 7)
+        table = {"start": int(start), "bytes": int(size), "codec": str(col.compression), "pos": t[:, 0], "compressed": t[:, 1],
+                 "uncompressed": t[:, 2], "num_values": t[:, 3], "type": t[:, 4], "encoding": t[:, 5], "levels": t[:, 6],
+                 "first_row": np.concatenate([[0], np.cumsum(t[:, 3])]), "chunk": None}
+        self._page_tables[g] = table
+        self._mark("header_walk")
+        table = dict(table, chunk=chunk)                      # the bytes go to this caller only: the cache keeps numbers
+        return table
+
+    def _group_keys(self, g: int, keep: bool):
+        """Row group ``g``'s ``key`` column as one arrow array (kept for groups that several scenes share)."""
+        if g in self._keys:
+            return self._keys[g]
+        keys = self.file.read_row_group(g, columns=["key"]).column("key").combine_chunks()
+        if keep:
+            self._keys[g] = keys
+        return keys
+
+    def image_rows(self, scene_id: str, image_ids) -> Dict[int, tuple]:
+        """{position in ``image_ids``: (row group, row in the group)} of the ``scene:image_to_points:image`` rows the index has --
+        the ``key`` column is matched with arrow compute, no Python string per row.  A key that several row groups hold
+        resolves to the group ``scene_dict`` lets win (the last one read)."""
+        import pyarrow as pa
+        import pyarrow.compute as pc
+        wanted = pa.array([f"{scene_id}:image_to_points:{i}" for i in image_ids], type=pa.string())
+        groups = [(g, False) for g in self._by_scene.get(scene_id, [])] + [(g, True) for g, lo, hi in self._mixed if lo <= scene_id <= hi]
+        found: Dict[int, tuple] = {}
+        for g, keep in groups:
+            keys = self._group_keys(g, keep)
+            if keys.type != wanted.type:
+                keys = keys.cast(wanted.type)
+            at = pc.index_in(wanted, value_set=keys).fill_null(-1).to_numpy(zero_copy_only=False)
+            for k in np.nonzero(at >= 0)[0]:
+                found[int(k)] = (g, int(at[k]))
+        return found
+
+    def needed_pages(self, g: int, rows) -> tuple:
+        """(page table of group ``g`` with its chunk's bytes, page index of every row of ``rows``, reason) -- ``reason`` is None
+        when the device path takes every page these rows lie in: v1 DATA_PAGE, PLAIN, codec SNAPPY or none, RLE definition
+        levels; otherwise it says what is in the way (a dictionary page in front does not matter by itself, dictionary-encoded
+        data pages do)."""
+        table = self.values_pages(g)
+        if table["chunk"] is None:
+            with open(self._path, "rb") as f:
+                f.seek(table["start"])
+                table = dict(table, chunk=f.read(table["bytes"]))
+            self._mark("file_read")
+        rows = np.asarray(rows, dtype=np.int64)
+        data = np.nonzero((table["type"] == 0) | (table["type"] == 3))[0]               # the pages that hold rows
+        page = data[np.searchsorted(table["first_row"][data + 1], rows, side="right").clip(max=max(len(data) - 1, 0))] if len(data) else None
+        reason = None
+        if page is None or bool((rows >= table["first_row"][-1]).any()):
+            return table, page, "rows beyond the chunk's pages"
+        used = np.unique(page)
+        if table["codec"] not in self._CODECS:
+            reason = f"codec {table['codec']}"
+        elif bool((table["type"][used] != self._DATA_PAGE).any()):
+            reason = "a data page that is not v1"
+        elif bool((table["encoding"][used] != self._PLAIN).any()):
+            reason = "a data page that is not PLAIN"
+        elif self._has_levels and bool((table["levels"][used] != self._RLE).any()):
+            reason = "definition levels that are not RLE"
+        elif int(table["uncompressed"][used].max()) > 0x7fffffff or int(table["compressed"][used].max()) > 0x7fffffff:
+            reason = "a page of 2 GiB"
+        return table, page, reason
+
+    def _mark(self, stage: str):
+        """The stage clock of tools/visindex_decode_bench.py: off unless ``stage_times`` is a dict, then every stage ends with a
+        device synchronise and its wall time is added under its name."""
+        if self.stage_times is None:
+            return
+        import time
+        import torch
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        now = time.perf_counter()
+        self.stage_times[stage] = self.stage_times.get(stage, 0.0) + now - self._stage_start
+        self._stage_start = now
+
+    def _decline(self, why: str):
+        self.decode_stats["scenes_declined"] += 1
+        self.last_decline = why
+
+    def _scene_bits_host(self, scene_id: str, image_ids, n_points, device):
+        """Today's path: ``scene_dict`` -> ``json.loads`` -> ``scene.pack_index_lists`` -> upload."""
+        import torch
+        from .scene import pack_index_lists
+        texts = self.scene_dict(scene_id)
+        present = [i for i in image_ids if f"{scene_id}:image_to_points:{i}" in texts]
+        lists = [json.loads(texts[f"{scene_id}:image_to_points:{i}"]) for i in present]
+        if n_points is None:
+            n_points = max((max(seen) for seen in lists if len(seen)), default=0) + 1
+        return present, torch.from_numpy(pack_index_lists(lists, int(n_points))).to(device)
+
+    def scene_bits(self, scene_id: str, image_ids, n_points: Optional[int] = None, device="cuda"):
+        """(present ids, bits): the requested image ids the index has, in request order, and their visible-vertex bitsets as an
+        int64 device tensor [len(present), ceil(n_points / 64)] -- ``scene.pack_index_lists``' layout; ``n_points`` None: 1 + the
+        largest index in these lists.
+
+        The rows go from the file to the device as their pages lie there: the ``values`` chunk's page headers are walked on
+        the host, the ``key`` column says which rows are wanted, only the pages that hold them are uploaded (compressed), and
+        the device decompresses (``engine.snappy_decompress_device``), finds the rows, parses the lists and sets the bits
+        (``engine.index_rows_to_bits``).  Whatever the device path does not take -- a page that is not v1 / PLAIN / Snappy or
+        uncompressed, a stream or a page it declines, a row that is not an ascending list inside ``n_points`` -- goes through
+        ``json.loads`` and ``pack_index_lists``, so the result is the host path's for every input.  ``decode_stats`` counts scenes,
+        declined scenes, rows, declined rows and uploaded bytes; ``last_decline`` says why the last scene was declined."""
+        import torch
+        from . import engine
+        from .scene import pack_index_lists
+        image_ids = list(image_ids)
+        self.decode_stats["scenes"] += 1
+        if self._path is None or not self._device_schema:
+            self._decline("not a file on disk" if self._path is None else "values is not a flat BYTE_ARRAY column")
+            return self._scene_bits_host(scene_id, image_ids, n_points, device)
+        if self.stage_times is not None:
+            import time
+            self._stage_start = time.perf_counter()
+        found = self.image_rows(scene_id, image_ids)
+        self._mark("key_read")
+        present_pos = sorted(found)
+        present = [image_ids[k] for k in present_pos]
+        if not present:
+            n = 1 if n_points is None else int(n_points)
+            return present, torch.zeros((0, (n + 63) // 64), dtype=torch.int64, device=device)
+        # the distinct rows, in (row group, row) order: what the device walks; the request refers to them by position
+        distinct = sorted(set(found.values()))
+        slot = {gr: k for k, gr in enumerate(distinct)}
+        parts, page_rows = [], []                                     # bytes to upload; per page: (src pos, comp, unc, nv, codec, rows)
+        upload = 0
+        for g in sorted({g for g, _ in distinct}, key=lambda g: [d[0] for d in distinct].index(g)):
+            rows = np.array([r for gg, r in distinct if gg == g], dtype=np.int64)
+            table, page, reason = self.needed_pages(g, rows)
+            if reason is not None:
+                self._decline(f"row group {g}: {reason}")
+                return self._scene_bits_host(scene_id, image_ids, n_points, device)
+            chunk = memoryview(table["chunk"])
+            for pg in np.unique(page):
+                pos, comp = int(table["pos"][pg]), int(table["compressed"][pg])
+                parts.append(np.frombuffer(chunk[pos:pos + comp], dtype=np.uint8))
+                page_rows.append((upload, comp, int(table["uncompressed"][pg]), int(table["num_values"][pg]), self._CODECS[table["codec"]],
+                                  rows[page == pg] - int(table["first_row"][pg])))
+                upload += comp
+        unc_total = sum(p[2] for p in page_rows)
+        if unc_total > 0x7fffffff:
+            self._decline("2 GiB of pages or more")
+            return self._scene_bits_host(scene_id, image_ids, n_points, device)
+        n_pages = len(page_rows)
+        host = torch.empty((max(upload, 1),), dtype=torch.uint8, pin_memory=True)
+        if upload:
+            np.concatenate(parts, out=host.numpy()[:upload])
+        src = host.to(device, non_blocking=True)[:upload]
+        self.decode_stats["h2d_bytes"] += upload
+        self._mark("h2d")
+        tab = np.zeros((6, n_pages + 1), dtype=np.int64)      # src offsets, compressed, uncompressed, payload offsets, values, row_begin
+        tab[0, :n_pages] = [p[0] for p in page_rows]
+        tab[1, :n_pages] = [p[1] for p in page_rows]
+        tab[2, :n_pages] = [p[2] for p in page_rows]
+        np.cumsum(tab[2, :n_pages], out=tab[3, 1:])
+        tab[4, :n_pages] = [p[3] for p in page_rows]
+        np.cumsum([len(p[5]) for p in page_rows], out=tab[5, 1:])
+        row_index = np.concatenate([p[5] for p in page_rows]).astype(np.int64)
+        tab_dev = torch.from_numpy(tab).to(device)
+        snappy = np.array([k for k, p in enumerate(page_rows) if p[4] == 1], dtype=np.int64)
+        if len(snappy) == n_pages:
+            pages, _, stream_status = engine.snappy_decompress_device(src, tab_dev[0, :n_pages].contiguous(), tab_dev[1, :n_pages].contiguous(),
+                                                                      tab_dev[2, :n_pages].contiguous())
+        else:                                                          # uncompressed chunks (and files that mix both): plain copies
+            pages = torch.empty((max(unc_total, 1),), dtype=torch.uint8, device=src.device)[:unc_total]
+            stream_status = None
+            if len(snappy):
+                sel = torch.from_numpy(snappy).to(device)
+                part, part_off, stream_status = engine.snappy_decompress_device(src, tab_dev[0].index_select(0, sel), tab_dev[1].index_select(0, sel),
+                                                                                tab_dev[2].index_select(0, sel))
+                part_off = part_off.cpu().numpy()
+            for k, p in enumerate(page_rows):
+                at = int(tab[3, k])
+                if p[4] == 1:
+                    j = int(np.searchsorted(snappy, k))
+                    pages[at:at + p[2]] = part[int(part_off[j]):int(part_off[j]) + p[2]]
+                elif p[1] != p[2]:
+                    self._decline("an uncompressed page whose sizes differ")
+                    return self._scene_bits_host(scene_id, image_ids, n_points, device)
+                else:
+                    pages[at:at + p[2]] = src[p[0]:p[0] + p[1]]
+        self._mark("decompress")
+        got = engine.index_rows_to_bits(pages, tab_dev[3, :n_pages].contiguous(), tab_dev[2, :n_pages].contiguous(),
+                                        tab_dev[4, :n_pages].contiguous(), tab_dev[5].contiguous(), torch.from_numpy(row_index).to(device),
+                                        n_points=n_points, has_levels=self._has_levels)
+        if (stream_status is not None and bool((stream_status != 0).any().item())) or bool(got["page_status"].any()):
+            self._decline("the device declined a page")
+            return self._scene_bits_host(scene_id, image_ids, n_points, device)
+        self._mark("rows_to_bits")
+        bits, width = got["bits"], got["n_points"]
+        self.decode_stats["rows"] += len(distinct)
+        declined = np.nonzero(got["row_status"])[0]
+        if len(declined):
+            # these rows' text comes back from the device's pages and takes the host path: json.loads, pack_index_lists
+            self.decode_stats["rows_declined"] += len(declined)
+            spans = torch.stack([got["start"], got["length"]])[:, torch.from_numpy(declined).to(device)].cpu().numpy()
+            lists = [json.loads(bytes(pages[int(a):int(a) + int(n)].cpu().numpy()).decode()) for a, n in zip(spans[0], spans[1])]
+            if n_points is None:
+                # the width comes from every list.  The device's figure covers every value it parsed (a row it declined for its
+                # order included; a row its parser declined counts as 0 there), these lists are the rest
+                width = max(width, max((max(seen) for seen in lists if len(seen)), default=0) + 1)
+            n_words = (width + 63) // 64
+            if n_words != bits.shape[1]:
+                wider = torch.zeros((bits.shape[0], n_words), dtype=torch.int64, device=bits.device)
+                wider[:, :min(n_words, bits.shape[1])] = bits[:, :n_words]
+                bits = wider
+            bits[torch.from_numpy(declined).to(device)] = torch.from_numpy(pack_index_lists(lists, width)).to(device)
+        order = torch.tensor([slot[found[k]] for k in present_pos], dtype=torch.int64, device=bits.device)
+        if len(order) != bits.shape[0] or not bool((order == torch.arange(len(order), device=bits.device)).all().item()):
+            bits = bits.index_select(0, order)
+        return present, bits
 
     def _split_group(self, g: int) -> Dict[str, Dict[str, str]]:
         if g not in self._cache:

@@ -45,10 +45,24 @@ def _indexed_images(scene_id, handler, visibility_dict, n_objects, warn):
     return image_ids, lists
 
 
-def process_scene(scene_id, scene_info_handler, visibility_dict):
+def _indexed_bits(scene_id, handler, index, n_objects, warn):
+    """``_indexed_images`` with the lists already packed: (image ids, their bitset rows on the GPU) straight from the index
+    file's pages (``visindex.SceneRowGroups.scene_bits``); the same warnings in the same order."""
+    wanted = list(handler.get_all_extrinsic_valid_image_ids(scene_id))
+    image_ids, bits = index.scene_bits(scene_id, wanted)
+    have = set(image_ids)
+    for image_id in wanted:
+        if image_id not in have:
+            for _ in range(n_objects):
+                warn(f"[Warning] Scene {scene_id}, image {image_id} not found in visibility dict.")
+    return image_ids, bits
+
+
+def process_scene(scene_id, scene_info_handler, visibility_dict, index=None):
     """(scene_id, {"object_to_images": {obj: [{image_id, intersection_count, visibility}]}, "image_to_objects": {img: [...]}},
     warnings) of one scene (reference: :72-151; an image counts for an object from max(1, int(5 % of its vertices)) visible
-    ones on).  ``visibility_dict``: "scene:image_to_points:img" -> JSON list text."""
+    ones on).  ``visibility_dict``: "scene:image_to_points:img" -> JSON list text; or, instead of it, ``index``: the
+    ``visindex.SceneRowGroups`` whose ``scene_bits`` hands the bitsets over (``MSPA_VISINDEX_DECODE=device``)."""
     print(f"Processing scene {scene_id}.")
     warnings_list = []
 
@@ -60,6 +74,15 @@ def process_scene(scene_id, scene_info_handler, visibility_dict):
         warn(f"[Warning] Scene {scene_id} not found in scene_info.")
         return scene_id, empty, warnings_list
     objects = _labelled_objects(scene_id, scene_info_handler, warn)
+    if index is not None:
+        image_ids, image_bits = _indexed_bits(scene_id, scene_info_handler, index, len(objects), warn)
+        if not objects or not image_ids:
+            return scene_id, empty, warnings_list
+        # only the rows' word count matters from here on: wide enough for the lists (as they came) and for the objects
+        n_words = max(image_bits.shape[1], max(int(v.max()) for v in objects.values()) // 64 + 1)
+        if n_words != image_bits.shape[1]:
+            image_bits = torch.cat([image_bits, image_bits.new_zeros((image_bits.shape[0], n_words - image_bits.shape[1]))], dim=1)
+        return scene_id, object_visibility_from_bits(image_bits, image_ids, 64 * n_words, objects), warnings_list
     image_ids, lists = _indexed_images(scene_id, scene_info_handler, visibility_dict, len(objects), warn)
     if not objects or not image_ids:
         return scene_id, empty, warnings_list
@@ -92,11 +115,15 @@ def process_split(split_name, scene_info_path, visibility_parquet_file, output_d
     scene_ids = handler.get_all_scene_ids()
     print(f"Loading visibility dict from {visibility_parquet_file}.")
     index = visindex.SceneRowGroups(visibility_parquet_file)
+    on_device = visindex.decode_mode() == "device"           # MSPA_VISINDEX_DECODE; a value that is neither raises here
     costs = [float(max(1, handler.get_num_objects(s)) * max(1, len(handler.get_all_extrinsic_valid_image_ids(s)))) for s in scene_ids]
     results, lines = {}, []
 
     def produce(position, scene_id):
-        _, result, warnings = process_scene(scene_id, handler, index.scene_dict(scene_id))
+        if on_device:
+            _, result, warnings = process_scene(scene_id, handler, None, index=index)
+        else:
+            _, result, warnings = process_scene(scene_id, handler, index.scene_dict(scene_id))
         return None, [pickle.dumps(result, protocol=pickle.HIGHEST_PROTOCOL), "".join(w + "\n" for w in warnings).encode()]
 
     def consume(position, _rows, blobs):

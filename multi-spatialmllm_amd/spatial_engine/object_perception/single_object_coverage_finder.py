@@ -38,7 +38,15 @@ covers_dimension = _cov.covers_dimension
 
 
 def _scene_bits(scene_id, image_ids, images_to_visible_points_dict, n_points):
-    """(image ids present in the index, their bitset rows on the GPU); warns for the missing ones."""
+    """(image ids present in the index, their bitset rows on the GPU); warns for the missing ones.  The index is a
+    {key: JSON text} dict, or a ``visindex.SceneRowGroups`` whose ``scene_bits`` packs the rows on the GPU."""
+    if hasattr(images_to_visible_points_dict, "scene_bits"):
+        present, bits = images_to_visible_points_dict.scene_bits(scene_id, image_ids, n_points)
+        have = set(present)
+        for img in image_ids:
+            if img not in have:
+                print(f"[Warning] Scene {scene_id}, image {img} not found in visibility dict. Skip this combination.")
+        return present, (bits if present else None)
     present, lists = [], []
     for img in image_ids:
         key = f"{scene_id}:image_to_points:{img}"
@@ -94,9 +102,12 @@ def process_scene_for_coverage(scene_id, scene_info_handler, images_to_visible_p
             if entry["image_id"] not in wanted:
                 wanted.append(entry["image_id"])
     index_key = f"{scene_id}:image_to_points:"
-    present = [img for img in wanted if index_key + img in images_to_visible_points_dict]
-    bits = (torch.from_numpy(pack_index_lists([json.loads(images_to_visible_points_dict[index_key + img]) for img in present],
-                                              len(scene_pts))).cuda() if present else None)
+    if hasattr(images_to_visible_points_dict, "scene_bits"):          # a visindex.SceneRowGroups: the rows are packed on the GPU
+        present, bits = images_to_visible_points_dict.scene_bits(scene_id, wanted, len(scene_pts))
+    else:
+        present = [img for img in wanted if index_key + img in images_to_visible_points_dict]
+        bits = (torch.from_numpy(pack_index_lists([json.loads(images_to_visible_points_dict[index_key + img]) for img in present],
+                                                  len(scene_pts))).cuda() if present else None)
     objects = {o: np.asarray(scene_info_handler.get_object_point_index(scene_id, o)) for o in per_object}
     ext = _cov.scene_extents(bits, present, scene_pts, objects) if present else None
     for object_id, visibility_list in per_object.items():
@@ -122,8 +133,11 @@ def process_scene_for_coverage(scene_id, scene_info_handler, images_to_visible_p
 
 def _load_inputs(scene_info_path, visibility_parquet_file, object_visibility_file):
     from spatial_engine.utils.scannet_utils.handler.info_handler import SceneInfoHandler, _load_any
-    return (SceneInfoHandler(scene_info_path), load_visibility_dict(visibility_parquet_file),
-            _load_any(object_visibility_file))
+    from mspa import visindex
+    # MSPA_VISINDEX_DECODE=device: no dict of the whole file -- every scene's rows go from its pages to the GPU (scene_bits)
+    index = (visindex.SceneRowGroups(visibility_parquet_file) if visindex.decode_mode() == "device"
+             else load_visibility_dict(visibility_parquet_file))
+    return SceneInfoHandler(scene_info_path), index, _load_any(object_visibility_file)
 
 
 def _run_scenes(scene_ids, handler, vis_dict, obj_vis):

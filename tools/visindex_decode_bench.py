@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Per-scene cost of reading the visibility index back into bitsets: the host path (``scene_dict`` -> ``json.loads`` ->
+``pack_index_lists`` -> upload: the code every consumer runs with ``MSPA_VISINDEX_DECODE`` unset) against
+``visindex.SceneRowGroups.scene_bits`` (the pages decompressed, walked, parsed and packed on the GPU).
+
+    python tools/visindex_decode_bench.py [--frames 320] [--points 131072] [--scenes 16] [--passes 6] [--host-scenes 4]
+
+The file: ``--scenes`` scenes of the `--workload scenes` shape (tools/visindex_encode_bench.py's ``make_bits``), each one row
+group written the way ``make_visibility_info.run_split`` writes it -- ``visindex.from_bits(...).to_row_group`` spliced by
+``parquet_splice.SplicedParquetWriter`` -- once with pyarrow's pages (``--layout host``, the default) and once with K12's
+(``--layout device``).  A pass reads every scene's bitsets (the host path: the first ``--host-scenes`` scenes) through a fresh
+``SceneRowGroups``; the first pass is the warm-up, the median is over the others, all passes are listed.  Reported per scene:
+wall, the process's CPU time (``time.process_time``: all threads, what a CPU quota counts), the bytes uploaded, and the device
+path's stages (each ended by a device synchronise, so their sum exceeds the unsplit wall a little).  Then the decode kernel
+alone, between two events on the stream: one scene's pages in one launch, and 8 scenes' pages in one launch.  Prints one JSON
+line.  Kernel-by-kernel times come from a separate ``rocprofv3 --kernel-trace --stats`` run of this tool with ``--device-only``."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "multi-spatialmllm_amd"), ROOT, os.path.dirname(os.path.abspath(__file__))]
+
+
+def write_index(path, bits, ids, points, scenes, layout):
+    from mspa import parquet_splice, visindex
+    with parquet_splice.SplicedParquetWriter(path) as w:
+        for k in range(scenes):
+            csr = visindex.from_bits(bits, ids, points, text=True, indices=False, pages=layout == "device")
+            w.append(csr.to_row_group(f"scene{k:04d}_00"))
+    return os.path.getsize(path)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=320)
+    ap.add_argument("--points", type=int, default=131072)
+    ap.add_argument("--scenes", type=int, default=16)
+    ap.add_argument("--passes", type=int, default=6, help="passes per path; the first is the warm-up")
+    ap.add_argument("--host-scenes", type=int, default=4, help="scenes of a host-path pass")
+    ap.add_argument("--visible", type=float, default=0.12)
+    ap.add_argument("--layout", choices=("host", "device"), default="host")
+    ap.add_argument("--device-only", action="store_true", help="skip the host path and the kernel-alone timings (for a profiler run)")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from mspa import engine, visindex
+    from visindex_encode_bench import make_bits
+    bits, density = make_bits(a.frames, a.points, a.visible)
+    ids = [f"{5 * f:05d}" for f in range(a.frames)]
+    scene_ids = [f"scene{k:04d}_00" for k in range(a.scenes)]
+    tmp = tempfile.mkdtemp(prefix="visindex_decode_bench_")
+    path = os.path.join(tmp, "vis.parquet")
+    file_bytes = write_index(path, bits, ids, a.points, a.scenes, a.layout)
+    print(f"index written: {file_bytes} bytes", file=sys.stderr, flush=True)
+    out = {"frames": a.frames, "vertices": a.points, "visible_fraction": round(density, 4), "scenes": a.scenes, "layout": a.layout,
+           "file_bytes": file_bytes, "warm_passes": a.passes - 1, "statistic": "median of the warm passes, per scene", "paths": {}}
+    want = bits.cpu().numpy()
+
+    def run(path_name, scenes, stages):
+        wall, cpu, h2d, st_all = [], [], [], []
+        for _ in range(a.passes):
+            index = visindex.SceneRowGroups(path)
+            if stages:
+                index.stage_times = {}
+            torch.cuda.synchronize()
+            c0, t0 = time.process_time(), time.perf_counter()
+            for s in scenes:
+                if path_name == "host":
+                    present, got = index._scene_bits_host(s, ids, a.points, "cuda")
+                else:
+                    present, got = index.scene_bits(s, ids, a.points)
+            torch.cuda.synchronize()
+            wall.append((time.perf_counter() - t0) / len(scenes))
+            cpu.append((time.process_time() - c0) / len(scenes))
+            h2d.append(index.decode_stats["h2d_bytes"] // len(scenes))
+            st_all.append({k: round(1e3 * v / len(scenes), 3) for k, v in (index.stage_times or {}).items()})
+            assert present == ids and np.array_equal(got.cpu().numpy(), want)
+            print(f"{path_name}{' staged' if stages else ''}: pass of {len(scenes)} scenes, {1e3 * wall[-1]:.1f} ms per scene", file=sys.stderr, flush=True)
+            assert path_name == "host" or (index.decode_stats["scenes_declined"] == 0 and index.decode_stats["rows_declined"] == 0)
+        res = {"scenes_per_pass": len(scenes), "wall_ms": round(1e3 * statistics.median(wall[1:]), 2),
+               "process_cpu_ms": round(1e3 * statistics.median(cpu[1:]), 2), "wall_ms_all": [round(1e3 * v, 2) for v in wall],
+               "process_cpu_ms_all": [round(1e3 * v, 2) for v in cpu]}
+        if path_name != "host":
+            res["h2d_bytes"] = int(statistics.median(h2d[1:]))
+        if stages:
+            res["stages_ms"] = {k: round(statistics.median([p[k] for p in st_all[1:]]), 3) for k in st_all[-1]}
+            res["stages_ms_all"] = st_all
+        return res
+
+    if not a.device_only:
+        out["paths"]["host"] = run("host", scene_ids[:a.host_scenes], False)
+    out["paths"]["device"] = run("device", scene_ids, False)
+    out["paths"]["device_staged"] = run("device", scene_ids, True)
+    if a.device_only:
+        print(json.dumps(out))
+        return
+
+    # the decode kernel alone: the needed pages of 1 and of 8 scenes, one launch each
+    index = visindex.SceneRowGroups(path)
+    parts, sizes = [], []
+    many = min(8, a.scenes)
+    for s in scene_ids[:many]:
+        found = index.image_rows(s, ids)
+        g = next(iter(found.values()))[0]
+        table, page, reason = index.needed_pages(g, [r for _, r in found.values()])
+        assert reason is None and table["codec"] == "SNAPPY"
+        for pg in np.unique(page):
+            pos, comp = int(table["pos"][pg]), int(table["compressed"][pg])
+            parts.append(np.frombuffer(table["chunk"][pos:pos + comp], dtype=np.uint8))
+            sizes.append((comp, int(table["uncompressed"][pg])))
+    per_scene = len(parts) // many
+    out["decode_kernel"] = {}
+    for label, n in (("one_scene", per_scene), (f"{many}_scenes", len(parts))):
+        src = torch.from_numpy(np.concatenate(parts[:n])).cuda()
+        comp = torch.tensor([c for c, _ in sizes[:n]], dtype=torch.int64, device="cuda")
+        offs = torch.cumsum(comp, 0) - comp
+        unc = torch.tensor([u for _, u in sizes[:n]], dtype=torch.int64, device="cuda")
+        ms = []
+        for _ in range(8):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _, _, status = engine.snappy_decompress_device(src, offs, comp, unc)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        assert int(status.abs().sum().item()) == 0
+        out["decode_kernel"][label] = {"pages": n, "compressed_bytes": int(comp.sum().item()), "uncompressed_bytes": int(unc.sum().item()),
+                                       "call_gpu_ms": round(statistics.median(ms[1:]), 3), "call_gpu_ms_all": [round(v, 3) for v in ms],
+                                       "note": "two events around engine.snappy_decompress_device: the kernel, one prefix sum and its read-back"}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
