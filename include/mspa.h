@@ -661,6 +661,29 @@ int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t ro
  *   byte for byte the host's output; otherwise declined with the host's code, or MSPA_EINVAL for a table entry that does not
  *   lie inside [0, src_bytes) / [0, out_bytes) (nothing is touched then).  A declined stream's output bytes are unspecified
  *   but stay inside its own span.  One wave per stream; no copy offset is refused.
+ * Decoding by blocks -- a second route with the same results.  Both writers (this library's, and Google's, which pyarrow uses)
+ * compress the input in independent blocks of 64 KiB, so in their streams every multiple of 65 536 output bytes is an element
+ * start, no element straddles one and no copy reaches in front of its block: such a stream is BLOCKWISE and every block decodes
+ * alone, one wave per block, once the blocks' positions in the compressed bytes are known.
+ * mspa_snappy_block_starts_host  the serial definition: out_starts[b] = the compressed position of the element that begins at
+ *   output 65 536 b, for b < ceil(expected / 65536), and one more entry, src_len (starts_capacity >= that many).  Returns the
+ *   block count; mspa_snappy_decompress_host's code for a stream that it declines; -22 for a stream that it decodes but that is
+ *   not blockwise; MSPA_EINVAL as above.
+ * mspa_snappy_blocks_workspace_bytes  bytes of workspace for a batch: stream_bytes >= the sum of the streams' compressed sizes
+ *   (src_bytes when they do not overlap), n_streams, n_blocks = the sum of ceil(out_bytes / 65536).  About 8 bytes per compressed
+ *   byte (the segment tables of the scan); -1 for a bad argument.
+ * mspa_snappy_block_starts_device  the scan alone, for a batch as above: block_prefix_dev [n_streams + 1] is the exclusive prefix
+ *   sum of ceil(out_bytes_dev / 65536) and n_blocks its last entry (the caller's plumbing, as for mspa_snappy_compress_device).
+ *   Stream s's starts go to starts_dev[block_prefix[s] + s ..], one more than its blocks (the last is nbytes[s]); starts_dev
+ *   has n_blocks + n_streams entries.  route_dev[s] (int32) = the stream's block count when it is blockwise and decodable, and
+ *   then its starts are mspa_snappy_block_starts_host's; 0 otherwise (its starts are unspecified).  The scan cuts a stream into
+ *   segments of 2 KiB of compressed bytes, one wave each; the only serial chain over a stream has one step per segment.
+ * mspa_snappy_decompress_blocks_device  mspa_snappy_decompress_device's arguments and results -- status_dev and the bytes are
+ *   the same for every input -- through the scan, one wave per block of every blockwise stream of two blocks or more, and then
+ *   the one-wave kernel for every other stream and for every stream with anything the matter with it.  route_dev[s] = the number
+ *   of blocks decoded in parallel, or 0 when the one-wave kernel decoded (or declined) the stream.  Nothing is read back in
+ *   between.  workspace: caller-owned, 16-byte aligned, >= mspa_snappy_blocks_workspace_bytes; a stream whose tables do not fit
+ *   stream_bytes takes the one-wave kernel.
  * mspa_parquet_plain_spans_device  pages_dev holds the needed pages' uncompressed payloads; page p is page_offsets_dev[p] +
  *   page_bytes_dev[p] (int64) and holds page_values_dev[p] values.  has_levels = 1: the payload opens with u32le(L) and L bytes
  *   of RLE definition levels, which must be ONE run of ones (varint(num_values << 1), 0x01: no nulls); 0: a required column,
@@ -684,6 +707,16 @@ int64_t mspa_snappy_decompress_host(const uint8_t *src, int64_t src_len, uint8_t
 int mspa_snappy_decompress_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
                                   int64_t n_streams, uint8_t *out_dev, int64_t out_bytes, const int64_t *out_offsets_dev,
                                   const int64_t *out_bytes_dev, int32_t *status_dev, void *stream);
+int64_t mspa_snappy_block_starts_host(const uint8_t *src, int64_t src_len, int64_t expected, int64_t *out_starts, int64_t starts_capacity);
+int64_t mspa_snappy_blocks_workspace_bytes(int64_t stream_bytes, int64_t n_streams, int64_t n_blocks);
+int mspa_snappy_block_starts_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
+                                    int64_t n_streams, const int64_t *out_bytes_dev, const int64_t *block_prefix_dev, int64_t n_blocks,
+                                    int64_t stream_bytes, void *workspace, int64_t workspace_bytes, int64_t *starts_dev, int32_t *route_dev,
+                                    void *stream);
+int mspa_snappy_decompress_blocks_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *offsets_dev, const int64_t *nbytes_dev,
+                                         int64_t n_streams, uint8_t *out_dev, int64_t out_bytes, const int64_t *out_offsets_dev,
+                                         const int64_t *out_bytes_dev, const int64_t *block_prefix_dev, int64_t n_blocks, int64_t stream_bytes,
+                                         void *workspace, int64_t workspace_bytes, int32_t *status_dev, int32_t *route_dev, void *stream);
 int mspa_parquet_plain_spans_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
                                     const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages, int32_t has_levels,
                                     const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows, int64_t *out_start_dev,

@@ -141,6 +141,7 @@ constexpr int kErrOverrun = -18;      // an element would write beyond `expected
 constexpr int kErrOffset = -19;       // a copy with offset 0, or one that reaches in front of the output's first byte
 constexpr int kErrTrailing = -20;     // input left over after `expected` bytes were written
 constexpr int kErrShort = -21;        // the input ended before `expected` bytes were written
+// (-22, kNotBlockwise, is block_starts' alone: a valid stream that does not decode block by block -- see below)
 
 struct Element {
     int32_t head;       // tag and length / offset bytes
@@ -216,6 +217,65 @@ MSPA_HD int64_t decompress(const uint8_t *src, int64_t src_len, uint8_t *dst, in
         o += e.len;
     }
     return o < expected ? kErrShort : o;
+}
+
+// ------------------------------------------------------------------------------------------------------- decoding by blocks
+// Both writers (this file's by definition, Google's -- pyarrow's -- by what its compressor does) cut the input into blocks of
+// kBlock bytes that are compressed independently.  Such a stream is BLOCKWISE: every multiple of kBlock output bytes is an
+// element start, no element straddles one, and no copy reaches in front of its block's first byte -- so each block's elements
+// decode alone, into their own kBlock bytes.  What a stream does not record is where a block's elements begin in the
+// compressed bytes; block_starts is the serial definition of that, decompress_block the decoder of one block.
+constexpr int kNotBlockwise = -22;    // a stream the decoder takes, but that is not blockwise (block_starts only)
+
+MSPA_HD int64_t block_count(int64_t expected) { return (expected + kBlock - 1) / kBlock; }
+
+// starts[b] = the compressed position of the element that begins at output b * kBlock, for b < block_count(expected), and
+// starts[block_count] = src_len (the last block's end); `cap`: entries of `starts`, nothing is written beyond them.  Returns the
+// block count; the code decompress() declines the stream with (whatever else is the matter with it); or kNotBlockwise.
+MSPA_HD int64_t block_starts(const uint8_t *src, int64_t src_len, int64_t expected, int64_t *starts, int64_t cap) {
+    const int pre = parse_preamble(load_le(src, 0, src_len), src_len, expected);
+    if (pre < 0) return pre;
+    const int64_t blocks = block_count(expected);
+    bool blockwise = true;
+    int64_t p = pre, o = 0;
+    while (p < src_len) {
+        if (o == expected) return kErrTrailing;
+        Element e;
+        int rc = parse_element(load_le(src, p, src_len), src_len - p, e);
+        if (rc == 0) rc = check_element(e, src_len - p, o, expected);
+        if (rc != 0) return rc;
+        const int64_t in_block = o % kBlock;
+        if (in_block == 0 && o / kBlock < cap) starts[o / kBlock] = p;
+        if (in_block + e.len > kBlock || (!e.literal && e.offset > in_block)) blockwise = false;
+        p += e.head + (e.literal ? e.len : 0);
+        o += e.len;
+    }
+    if (o < expected) return kErrShort;
+    if (!blockwise) return kNotBlockwise;
+    if (blocks < cap) starts[blocks] = src_len;
+    return blocks;
+}
+
+// The elements in src[p0, p1) -> dst_block[0, nb): one block of a blockwise stream.  An offset is checked against the bytes
+// written in THIS block.  Returns nb, or a code (the elements must fill exactly nb bytes from exactly [p0, p1)).
+MSPA_HD int64_t decompress_block(const uint8_t *src, int64_t p0, int64_t p1, uint8_t *dst_block, int64_t nb) {
+    int64_t p = p0, o = 0;
+    while (p < p1) {
+        if (o == nb) return kErrTrailing;
+        Element e;
+        int rc = parse_element(load_le(src, p, p1), p1 - p, e);
+        if (rc == 0) rc = check_element(e, p1 - p, o, nb);
+        if (rc != 0) return rc;
+        if (e.literal) {
+            for (int64_t i = 0; i < e.len; ++i) dst_block[o + i] = src[p + e.head + i];
+            p += e.head + e.len;
+        } else {
+            for (int64_t i = 0; i < e.len; ++i) dst_block[o + i] = dst_block[o + i - e.offset];
+            p += e.head;
+        }
+        o += e.len;
+    }
+    return o < nb ? kErrShort : o;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pages

@@ -939,6 +939,74 @@ def snappy_decompress_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: t
     return out[:total], out_offsets, status
 
 
+def _block_tables(src, offsets, nbytes, out_sizes):
+    """What the block route's two calls share: the checks, the prefix sums (torch as plumbing) and ONE small read-back -- the
+    bytes to allocate, the block count and the sum of the compressed sizes (streams may overlap: that sum sizes the workspace)."""
+    n = _check_streams(offsets, nbytes)
+    _check("src", src, torch.uint8, (None,))
+    _check("out_sizes", out_sizes, torch.int64, (n,))
+    dev = src.device
+    out_offsets = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    block_prefix = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    if n == 0:
+        return 0, out_offsets, block_prefix, 0, 0, 0
+    sizes = out_sizes.clamp(min=0, max=0x7fffffff)            # a size outside is the kernel's to refuse (MSPA_EINVAL)
+    torch.cumsum(sizes, dim=0, out=out_offsets[1:])
+    torch.cumsum((sizes + (_lib.SNAPPY_BLOCK - 1)) // _lib.SNAPPY_BLOCK, dim=0, out=block_prefix[1:])
+    inside = (offsets >= 0) & (nbytes >= 0) & (nbytes <= 0x7fffffff) & (offsets <= src.numel() - nbytes)
+    head = torch.stack([out_offsets[-1], block_prefix[-1], (nbytes * inside).sum()]).cpu()
+    total, n_blocks, stream_bytes = int(head[0]), int(head[1]), int(head[2])
+    _require(n_blocks <= 0x7fffffff, "out_sizes: fewer than 2^31 blocks of 64 KiB in one call")
+    return n, out_offsets, block_prefix, total, n_blocks, stream_bytes
+
+
+def snappy_block_starts_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, out_sizes: torch.Tensor):
+    """The block-start scan alone, for a batch of raw Snappy streams as ``snappy_decompress_device`` takes them: where each
+    64 KiB block's elements begin in the compressed bytes.  Returns (starts int64 [n_blocks + n], block_prefix int64 [n + 1],
+    route int32 [n]) on the device: stream s's starts are ``starts[block_prefix[s] + s : block_prefix[s + 1] + s + 1]`` (one more
+    than its blocks; the last is ``nbytes[s]``) where ``route[s]`` is its block count -- then they are
+    mspa_snappy_block_starts_host's; ``route[s] == 0``: the stream is empty, not blockwise or not decodable, its starts are
+    unspecified.  One small read-back (the sizes to allocate)."""
+    lib = _lib.load()
+    n, _out_offsets, block_prefix, _total, n_blocks, stream_bytes = _block_tables(src, offsets, nbytes, out_sizes)
+    dev = src.device
+    starts = torch.full((n_blocks + n,), -1, dtype=torch.int64, device=dev)
+    route = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return starts, block_prefix, route
+    ws_bytes = int(lib.mspa_snappy_blocks_workspace_bytes(stream_bytes, n, n_blocks))
+    _require(ws_bytes >= 0, "snappy_block_starts_device: sizes beyond the workspace's range")
+    ws = _workspace(ws_bytes, dev)
+    _lib.check(lib.mspa_snappy_block_starts_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), n,
+                                                   _ptr(out_sizes), _ptr(block_prefix), n_blocks, stream_bytes, _ptr(ws), ws.numel(),
+                                                   _ptr(starts), _ptr(route), _stream_ptr()))
+    return starts, block_prefix, route
+
+
+def snappy_decompress_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, out_sizes: torch.Tensor):
+    """``snappy_decompress_device`` by blocks: the same arguments, the same (out, out_offsets, status) for every input, and
+    ``route`` int32 [n] behind them.  A stream whose elements respect the 64 KiB block boundaries both writers keep (pyarrow's
+    and this library's) is decoded by one wave per block -- ``route[s]`` = its block count; every other stream, every stream of
+    one block and every stream with anything the matter with it is decoded (or declined, with the host's code) by the one-wave
+    kernel -- ``route[s] == 0``.  The workspace is about 8 bytes per compressed byte.  One small read-back (the sizes to
+    allocate)."""
+    lib = _lib.load()
+    n, out_offsets, block_prefix, total, n_blocks, stream_bytes = _block_tables(src, offsets, nbytes, out_sizes)
+    dev = src.device
+    status = torch.zeros((n,), dtype=torch.int32, device=dev)
+    route = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.uint8, device=dev), out_offsets, status, route
+    out = torch.empty((max(total, 1),), dtype=torch.uint8, device=dev)
+    ws_bytes = int(lib.mspa_snappy_blocks_workspace_bytes(stream_bytes, n, n_blocks))
+    _require(ws_bytes >= 0, "snappy_decompress_blocks_device: sizes beyond the workspace's range")
+    ws = _workspace(ws_bytes, dev)
+    _lib.check(lib.mspa_snappy_decompress_blocks_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), n,
+                                                        _ptr(out), total, _ptr(out_offsets), _ptr(out_sizes), _ptr(block_prefix), n_blocks,
+                                                        stream_bytes, _ptr(ws), ws.numel(), _ptr(status), _ptr(route), _stream_ptr()))
+    return out[:total], out_offsets, status, route
+
+
 def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
                        row_begin: torch.Tensor, row_index: torch.Tensor, n_points: Optional[int] = None, has_levels: bool = True):
     """Rows of the visibility index straight from their pages to bitset rows, on the device.  ``pages`` (uint8) holds the

@@ -254,7 +254,9 @@ class SceneRowGroups:
         self._values_col = self.file.schema_arrow.get_field_index("values")
         self._page_tables: Dict[int, dict] = {}
         self._keys: Dict[int, object] = {}
-        self.decode_stats = {"scenes": 0, "scenes_declined": 0, "rows": 0, "rows_declined": 0, "h2d_bytes": 0}
+        self.decode_stats = {"scenes": 0, "scenes_declined": 0, "rows": 0, "rows_declined": 0, "h2d_bytes": 0, "blocks": 0,
+                             "serial_streams": 0}
+        self.decode_by_blocks = True      # False: every page by the one-wave kernel (tools/visindex_decode_bench.py times both)
         self.last_decline: Optional[str] = None
         self.stage_times: Optional[dict] = None
         self._stage_start = 0.0
@@ -415,11 +417,13 @@ class SceneRowGroups:
 
         The rows go from the file to the device as their pages lie there: the ``values`` chunk's page headers are walked on
         the host, the ``key`` column says which rows are wanted, only the pages that hold them are uploaded (compressed), and
-        the device decompresses (``engine.snappy_decompress_device``), finds the rows, parses the lists and sets the bits
+        the device decompresses (``engine.snappy_decompress_blocks_device``: one wave per 64 KiB block of a page, the one-wave
+        kernel for a page that is not cut that way), finds the rows, parses the lists and sets the bits
         (``engine.index_rows_to_bits``).  Whatever the device path does not take -- a page that is not v1 / PLAIN / Snappy or
         uncompressed, a stream or a page it declines, a row that is not an ascending list inside ``n_points`` -- goes through
         ``json.loads`` and ``pack_index_lists``, so the result is the host path's for every input.  ``decode_stats`` counts scenes,
-        declined scenes, rows, declined rows and uploaded bytes; ``last_decline`` says why the last scene was declined."""
+        declined scenes, rows, declined rows, uploaded bytes, ``blocks`` (64 KiB blocks decoded in parallel) and ``serial_streams``
+        (Snappy pages the one-wave kernel took); ``last_decline`` says why the last scene was declined."""
         import torch
         from . import engine
         from .scene import pack_index_lists
@@ -477,16 +481,25 @@ class SceneRowGroups:
         row_index = np.concatenate([p[5] for p in page_rows]).astype(np.int64)
         tab_dev = torch.from_numpy(tab).to(device)
         snappy = np.array([k for k, p in enumerate(page_rows) if p[4] == 1], dtype=np.int64)
+        route = None
+
+        def decompress(offs, sizes, unc):
+            nonlocal route
+            if not self.decode_by_blocks:
+                return engine.snappy_decompress_device(src, offs, sizes, unc)
+            out, out_off, status, route = engine.snappy_decompress_blocks_device(src, offs, sizes, unc)
+            return out, out_off, status
+
         if len(snappy) == n_pages:
-            pages, _, stream_status = engine.snappy_decompress_device(src, tab_dev[0, :n_pages].contiguous(), tab_dev[1, :n_pages].contiguous(),
-                                                                      tab_dev[2, :n_pages].contiguous())
+            pages, _, stream_status = decompress(tab_dev[0, :n_pages].contiguous(), tab_dev[1, :n_pages].contiguous(),
+                                                 tab_dev[2, :n_pages].contiguous())
         else:                                                          # uncompressed chunks (and files that mix both): plain copies
             pages = torch.empty((max(unc_total, 1),), dtype=torch.uint8, device=src.device)[:unc_total]
             stream_status = None
             if len(snappy):
                 sel = torch.from_numpy(snappy).to(device)
-                part, part_off, stream_status = engine.snappy_decompress_device(src, tab_dev[0].index_select(0, sel), tab_dev[1].index_select(0, sel),
-                                                                                tab_dev[2].index_select(0, sel))
+                part, part_off, stream_status = decompress(tab_dev[0].index_select(0, sel), tab_dev[1].index_select(0, sel),
+                                                           tab_dev[2].index_select(0, sel))
                 part_off = part_off.cpu().numpy()
             for k, p in enumerate(page_rows):
                 at = int(tab[3, k])
@@ -506,6 +519,10 @@ class SceneRowGroups:
             self._decline("the device declined a page")
             return self._scene_bits_host(scene_id, image_ids, n_points, device)
         self._mark("rows_to_bits")
+        if stream_status is not None:
+            routes = route.cpu().numpy() if route is not None else np.zeros(len(snappy), dtype=np.int32)
+            self.decode_stats["blocks"] += int(routes.sum())
+            self.decode_stats["serial_streams"] += int((routes == 0).sum())
         bits, width = got["bits"], got["n_points"]
         self.decode_stats["rows"] += len(distinct)
         declined = np.nonzero(got["row_status"])[0]

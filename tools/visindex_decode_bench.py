@@ -11,9 +11,12 @@ group written the way ``make_visibility_info.run_split`` writes it -- ``visindex
 (``--layout device``).  A pass reads every scene's bitsets (the host path: the first ``--host-scenes`` scenes) through a fresh
 ``SceneRowGroups``; the first pass is the warm-up, the median is over the others, all passes are listed.  Reported per scene:
 wall, the process's CPU time (``time.process_time``: all threads, what a CPU quota counts), the bytes uploaded, and the device
-path's stages (each ended by a device synchronise, so their sum exceeds the unsplit wall a little).  Then the decode kernel
-alone, between two events on the stream: one scene's pages in one launch, and 8 scenes' pages in one launch.  Prints one JSON
-line.  Kernel-by-kernel times come from a separate ``rocprofv3 --kernel-trace --stats`` run of this tool with ``--device-only``."""
+path's stages (each ended by a device synchronise, so their sum exceeds the unsplit wall a little).  The device path runs twice
+(``--route both``): with the Snappy decode by 64 KiB blocks, which is what ``scene_bits`` does, and with the one-wave kernel
+for every page (``SceneRowGroups.decode_by_blocks = False``: the paths named ``device_one_wave``) -- both in this process, beside
+the host path.  Then the decode calls alone, between two events on the stream: one scene's pages in one call, and 8 scenes' pages
+in one call, by either route.  Prints one JSON line.  Kernel-by-kernel times (scan, block decode and last pass apart) come from
+a separate ``rocprofv3 --kernel-trace --stats`` run of this tool with ``--device-only --route blocks``."""
 import argparse
 import json
 import os
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--visible", type=float, default=0.12)
     ap.add_argument("--layout", choices=("host", "device"), default="host")
     ap.add_argument("--device-only", action="store_true", help="skip the host path and the kernel-alone timings (for a profiler run)")
+    ap.add_argument("--route", choices=("both", "blocks", "one-wave"), default="both",
+                    help="the device path's Snappy decode: one wave per 64 KiB block, the one-wave kernel for every page, or both in turn")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -61,10 +66,11 @@ def main():
            "file_bytes": file_bytes, "warm_passes": a.passes - 1, "statistic": "median of the warm passes, per scene", "paths": {}}
     want = bits.cpu().numpy()
 
-    def run(path_name, scenes, stages):
+    def run(path_name, scenes, stages, by_blocks=True):
         wall, cpu, h2d, st_all = [], [], [], []
         for _ in range(a.passes):
             index = visindex.SceneRowGroups(path)
+            index.decode_by_blocks = by_blocks
             if stages:
                 index.stage_times = {}
             torch.cuda.synchronize()
@@ -87,6 +93,8 @@ def main():
                "process_cpu_ms_all": [round(1e3 * v, 2) for v in cpu]}
         if path_name != "host":
             res["h2d_bytes"] = int(statistics.median(h2d[1:]))
+            res["blocks_per_scene"] = index.decode_stats["blocks"] // len(scenes)
+            res["serial_streams_per_scene"] = index.decode_stats["serial_streams"] // len(scenes)
         if stages:
             res["stages_ms"] = {k: round(statistics.median([p[k] for p in st_all[1:]]), 3) for k in st_all[-1]}
             res["stages_ms_all"] = st_all
@@ -94,8 +102,12 @@ def main():
 
     if not a.device_only:
         out["paths"]["host"] = run("host", scene_ids[:a.host_scenes], False)
-    out["paths"]["device"] = run("device", scene_ids, False)
-    out["paths"]["device_staged"] = run("device", scene_ids, True)
+    if a.route != "one-wave":
+        out["paths"]["device"] = run("device", scene_ids, False)
+        out["paths"]["device_staged"] = run("device", scene_ids, True)
+    if a.route != "blocks":
+        out["paths"]["device_one_wave"] = run("device", scene_ids, False, by_blocks=False)
+        out["paths"]["device_one_wave_staged"] = run("device", scene_ids, True, by_blocks=False)
     if a.device_only:
         print(json.dumps(out))
         return
@@ -120,19 +132,22 @@ def main():
         comp = torch.tensor([c for c, _ in sizes[:n]], dtype=torch.int64, device="cuda")
         offs = torch.cumsum(comp, 0) - comp
         unc = torch.tensor([u for _, u in sizes[:n]], dtype=torch.int64, device="cuda")
-        ms = []
-        for _ in range(8):
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _, _, status = engine.snappy_decompress_device(src, offs, comp, unc)
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-        assert int(status.abs().sum().item()) == 0
-        out["decode_kernel"][label] = {"pages": n, "compressed_bytes": int(comp.sum().item()), "uncompressed_bytes": int(unc.sum().item()),
-                                       "call_gpu_ms": round(statistics.median(ms[1:]), 3), "call_gpu_ms_all": [round(v, 3) for v in ms],
-                                       "note": "two events around engine.snappy_decompress_device: the kernel, one prefix sum and its read-back"}
+        entry = {"pages": n, "compressed_bytes": int(comp.sum().item()), "uncompressed_bytes": int(unc.sum().item()),
+                 "note": "two events around the engine call: the kernels, the prefix sums and one read-back"}
+        for route, call in (("blocks", engine.snappy_decompress_blocks_device), ("one_wave", engine.snappy_decompress_device)):
+            ms = []
+            for _ in range(8):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                status = call(src, offs, comp, unc)[2]
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            assert int(status.abs().sum().item()) == 0
+            entry[f"{route}_call_gpu_ms"] = round(statistics.median(ms[1:]), 3)
+            entry[f"{route}_call_gpu_ms_all"] = [round(v, 3) for v in ms]
+        out["decode_kernel"][label] = entry
     print(json.dumps(out))
 
 
