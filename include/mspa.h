@@ -646,9 +646,9 @@ int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t ro
                                      uint8_t *out_payload_dev, int32_t *bad_flag_dev, void *stream);
 
 /*
- * The way back -- a `values` column chunk's pages to the image_to_points rows' bitsets ON THE DEVICE (csrc/parquet_pages.hip;
- * the Snappy decoder's rules in csrc/snappy_core.h).  What a reader of the index otherwise does on the host: decompress, walk
- * the PLAIN values, json.loads every list, pack the bits.
+ * The way back -- a `values` column chunk's pages to the image_to_points rows' bitsets ON THE DEVICE (csrc/snappy_decode.hip,
+ * csrc/index_rows.hip; the Snappy decoder's rules in csrc/snappy_core.h).  What a reader of the index otherwise does on the
+ * host: decompress, walk the PLAIN values, json.loads every list, pack the bits.
  *
  * mspa_snappy_decompress_host  the reference: one raw Snappy stream src[0, src_len) (varint(n), then literals with 0 .. 4
  *   length bytes, copy-1 / copy-2 / copy-4 elements, overlapping copies included; any writer's) -> dst[0, expected).  Returns

@@ -54,13 +54,7 @@ __global__ __launch_bounds__(256) void lists_write_kernel(const int64_t *__restr
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nnz) return;
     // the list this item belongs to: the last r with offsets[r] <= e (empty lists in front of it share its offset: upper bound)
-    int64_t lo = 0, hi = n_lists;                                // invariant: offsets[lo] <= e < offsets[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (offsets[mid] <= e) lo = mid;
-        else hi = mid;
-    }
-    const int64_t r = lo, o = offsets[r];
+    const int64_t r = last_at_or_below(offsets, n_lists, e), o = offsets[r];
     const int64_t row_start = 2 * r + T[o] - 2 * NE[r];
     const int64_t te = T[e];
     char *p = out + row_start + 1 + (te - T[o]);

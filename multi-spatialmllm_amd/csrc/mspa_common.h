@@ -30,6 +30,22 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The last i in [0, n) with at(i) <= x, for an ascending at() with at(0) <= x and n >= 1.  Among equal entries it is the LAST one;
+// what such a tie means is the caller's to say.  at(i) is called for 0 < i < n only.
+template <typename At>
+__device__ __forceinline__ int64_t last_at_or_below(int64_t n, int64_t x, At at) {
+    int64_t lo = 0, hi = n;                                      // invariant: at(lo) <= x < at(hi)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (at(mid) <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int64_t last_at_or_below(const int64_t *__restrict__ t, int64_t n, int64_t x) {
+    return last_at_or_below(n, x, [t](int64_t i) { return t[i]; });
+}
+
 // One row of an affine 4x4 (row-major, uniform address -> scalar loads) applied to (x, y, z, 1),
 // in the order NumPy/OpenBLAS evaluates a K=4 product: m0*x, fma(m1,y,.), fma(m2,z,.), then +m3
 // (fma(m3, 1.0, acc) and acc + m3 round identically).  Compiled with -ffp-contract=off: nothing

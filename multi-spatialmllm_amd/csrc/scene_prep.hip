@@ -23,17 +23,6 @@ namespace prep {
 
 constexpr int kWavesPerBlock = 4;
 
-// last s in [0, n) with off[s] <= x (off ascending, off[0] <= x < off[n])
-__device__ __forceinline__ int64_t span_of(const int64_t *__restrict__ off, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct WaveSpan {
     int64_t scene, word, v;          // scene, word within the scene, this lane's vertex in the concatenated arrays
     bool live;
@@ -44,7 +33,7 @@ __device__ __forceinline__ bool wave_span(const int64_t *__restrict__ vert_off, 
     const int lane = threadIdx.x & 63;
     const int64_t g = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (g >= word_off[n_scenes]) return false;
-    w.scene = span_of(word_off, n_scenes, g);
+    w.scene = last_at_or_below(word_off, n_scenes, g);             // the wave's scene (scenes without vertices share their successor's offset)
     w.word = g - word_off[w.scene];
     const int64_t local = w.word * 64 + lane;
     w.live = local < vert_off[w.scene + 1] - vert_off[w.scene];
@@ -204,7 +193,7 @@ __global__ __launch_bounds__(256) void int_list_flags_kernel(const unsigned char
                                                              int32_t *__restrict__ status) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_bytes) return;
-    const int64_t a = span_of(text_off, n_arrays, i);
+    const int64_t a = last_at_or_below(text_off, n_arrays, i);               // byte i's array (empty texts in front of it share its offset)
     const unsigned char c = text[i];
     const bool next_digit = i + 1 < text_off[a + 1] && is_digit(text[i + 1]);
     int64_t f = 0;
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(256) void int_list_values_kernel(const unsigned cha
     if (i >= n_bytes) return;
     const int64_t t = T[i];
     if (((T[i + 1] - t) & 0xffffffffLL) != 1) return;                        // not the last digit of a number
-    const int64_t a = span_of(text_off, n_arrays, i);
+    const int64_t a = last_at_or_below(text_off, n_arrays, i);               // byte i's array (empty texts in front of it share its offset)
     const int64_t base = text_off[a], tb = T[base];
     const int64_t e = t & 0xffffffffLL;                                      // numbers in front of this one, over all arrays: its slot
     int32_t bad = 0;

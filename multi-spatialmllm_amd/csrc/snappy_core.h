@@ -1,6 +1,7 @@
 // Snappy compression, Snappy decoding and parquet v1 data pages for the visibility index's `values` column: the arithmetic shared by the device
-// kernels of parquet_pages.hip (K12) and the host reference.  Everything that decides an output byte is an MSPA_HD function here,
-// so that a plain C++ build of this header is the reference the device must equal byte for byte.
+// kernels of parquet_pages.hip (K12, the writer), snappy_decode.hip and index_rows.hip (the way back) and the host reference.
+// Everything that decides an output byte is an MSPA_HD function here, so that a plain C++ build of this header is the reference
+// the device must equal byte for byte.
 //
 //   * The compressor is this file's own, deterministic algorithm (not Google's): a function of the input bytes only.
 //       - a stream is varint(n), then the elements of the input's consecutive blocks of kBlock = 64 KiB bytes.  Blocks are

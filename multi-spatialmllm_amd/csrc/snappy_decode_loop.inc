@@ -1,5 +1,5 @@
-// The element loop of the Snappy decoders of parquet_pages.hip, included into each kernel that runs it: decompress_kernel, the
-// block route's decompress_blocks_kernel and decompress_flagged_kernel.  As text and not as a function on purpose: the loop is a
+// The element loop of the Snappy decoders of snappy_decode.hip, included into each kernel that runs it: decompress_kernel (both
+// instantiations) and the block route's decompress_blocks_kernel.  As text and not as a function on purpose: the loop is a
 // chain of a few hundred mostly scalar instructions whose pace moved by 4 - 7 % on the MI355X when the same statements reached
 // the one-wave kernel through a __forceinline__ function (the instruction selection around the window refill differs by four
 // instructions and the loop lands 8 bytes elsewhere; profiles/visindex_device_decode.md).  Included, the kernel's code is what

@@ -23,7 +23,7 @@ SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
 # csrc/snappy_core.h: what mspa_snappy_decompress_host returns for, and the device writes as the status of, a stream it declines
 SNAPPY_EPREAMBLE, SNAPPY_ETRUNCATED, SNAPPY_EOVERRUN, SNAPPY_EOFFSET, SNAPPY_ETRAILING, SNAPPY_ESHORT = -16, -17, -18, -19, -20, -21
 SNAPPY_NOT_BLOCKWISE = -22     # mspa_snappy_block_starts_host alone: a valid stream that does not decode block by block
-SNAPPY_SEGMENT = 2048          # csrc/parquet_pages.hip: kSeg, the compressed bytes one wave of the block-start scan takes
+SNAPPY_SEGMENT = 2048          # csrc/snappy_decode.hip: kSeg, the compressed bytes one wave of the block-start scan takes
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 

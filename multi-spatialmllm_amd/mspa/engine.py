@@ -824,6 +824,11 @@ def snappy_compress_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: tor
     return out, starts
 
 
+def _streams_inside(src, offsets, nbytes):
+    """Per stream of a table: it lies inside ``src`` and is shorter than 2 GiB (bool, on the device)."""
+    return (offsets >= 0) & (nbytes >= 0) & (nbytes <= 0x7fffffff) & (offsets <= src.numel() - nbytes)
+
+
 def _snappy_compress(src, offsets, nbytes):
     """``snappy_compress_device`` without its last read-back: (out, starts, the compact kernels' flag, still on the device)."""
     lib = _lib.load()
@@ -839,8 +844,7 @@ def _snappy_compress(src, offsets, nbytes):
     vlen = 1 + (nbytes >= 1 << 7).to(torch.int64) + (nbytes >= 1 << 14) + (nbytes >= 1 << 21) + (nbytes >= 1 << 28)
     vprefix = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
     torch.cumsum(vlen, dim=0, out=vprefix[1:])
-    inside = ((offsets >= 0) & (nbytes >= 0) & (nbytes <= 0x7fffffff) & (offsets <= src.numel() - nbytes)).all()
-    head = torch.stack([block_prefix[-1], inside.to(torch.int64)]).cpu()
+    head = torch.stack([block_prefix[-1], _streams_inside(src, offsets, nbytes).all().to(torch.int64)]).cpu()
     _require(int(head[1]) == 1, "offsets / nbytes: every stream lies inside src and is shorter than 2 GiB")
     n_blocks = int(head[0])
     _require(n_blocks <= 0x7fffffff, "nbytes: fewer than 2^31 blocks of 64 KiB in one call")
@@ -953,11 +957,17 @@ def _block_tables(src, offsets, nbytes, out_sizes):
     sizes = out_sizes.clamp(min=0, max=0x7fffffff)            # a size outside is the kernel's to refuse (MSPA_EINVAL)
     torch.cumsum(sizes, dim=0, out=out_offsets[1:])
     torch.cumsum((sizes + (_lib.SNAPPY_BLOCK - 1)) // _lib.SNAPPY_BLOCK, dim=0, out=block_prefix[1:])
-    inside = (offsets >= 0) & (nbytes >= 0) & (nbytes <= 0x7fffffff) & (offsets <= src.numel() - nbytes)
-    head = torch.stack([out_offsets[-1], block_prefix[-1], (nbytes * inside).sum()]).cpu()
+    head = torch.stack([out_offsets[-1], block_prefix[-1], (nbytes * _streams_inside(src, offsets, nbytes)).sum()]).cpu()
     total, n_blocks, stream_bytes = int(head[0]), int(head[1]), int(head[2])
     _require(n_blocks <= 0x7fffffff, "out_sizes: fewer than 2^31 blocks of 64 KiB in one call")
     return n, out_offsets, block_prefix, total, n_blocks, stream_bytes
+
+
+def _blocks_workspace(who, stream_bytes, n, n_blocks, dev):
+    """The block route's workspace for a batch; ``who``: the caller, for the message."""
+    ws_bytes = int(_lib.load().mspa_snappy_blocks_workspace_bytes(stream_bytes, n, n_blocks))
+    _require(ws_bytes >= 0, who + ": sizes beyond the workspace's range")
+    return _workspace(ws_bytes, dev)
 
 
 def snappy_block_starts_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, out_sizes: torch.Tensor):
@@ -974,9 +984,7 @@ def snappy_block_starts_device(src: torch.Tensor, offsets: torch.Tensor, nbytes:
     route = torch.zeros((n,), dtype=torch.int32, device=dev)
     if n == 0:
         return starts, block_prefix, route
-    ws_bytes = int(lib.mspa_snappy_blocks_workspace_bytes(stream_bytes, n, n_blocks))
-    _require(ws_bytes >= 0, "snappy_block_starts_device: sizes beyond the workspace's range")
-    ws = _workspace(ws_bytes, dev)
+    ws = _blocks_workspace("snappy_block_starts_device", stream_bytes, n, n_blocks, dev)
     _lib.check(lib.mspa_snappy_block_starts_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), n,
                                                    _ptr(out_sizes), _ptr(block_prefix), n_blocks, stream_bytes, _ptr(ws), ws.numel(),
                                                    _ptr(starts), _ptr(route), _stream_ptr()))
@@ -998,9 +1006,7 @@ def snappy_decompress_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nb
     if n == 0:
         return torch.empty((0,), dtype=torch.uint8, device=dev), out_offsets, status, route
     out = torch.empty((max(total, 1),), dtype=torch.uint8, device=dev)
-    ws_bytes = int(lib.mspa_snappy_blocks_workspace_bytes(stream_bytes, n, n_blocks))
-    _require(ws_bytes >= 0, "snappy_decompress_blocks_device: sizes beyond the workspace's range")
-    ws = _workspace(ws_bytes, dev)
+    ws = _blocks_workspace("snappy_decompress_blocks_device", stream_bytes, n, n_blocks, dev)
     _lib.check(lib.mspa_snappy_decompress_blocks_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), n,
                                                         _ptr(out), total, _ptr(out_offsets), _ptr(out_sizes), _ptr(block_prefix), n_blocks,
                                                         stream_bytes, _ptr(ws), ws.numel(), _ptr(status), _ptr(route), _stream_ptr()))

@@ -15,7 +15,7 @@ from __future__ import annotations
 import dataclasses
 import json
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -234,6 +234,23 @@ def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, ind
     return csr
 
 
+class _Page(NamedTuple):
+    """One page ``SceneRowGroups.scene_bits`` uploads: page ``index`` of row group ``group``'s ``values_pages`` table."""
+    group: int
+    index: int
+    data: np.ndarray          # its bytes as they lie in the file (uint8, ``compressed`` of them)
+    src: int                  # where they start in the upload: the pages' bytes back to back
+    compressed: int
+    uncompressed: int
+    num_values: int
+    snappy: bool              # False: the chunk is not compressed
+    rows: np.ndarray          # the wanted rows as value numbers inside the page (its first row is 0), ascending
+
+
+# the rows of the page table ``scene_bits`` sends to the device (one column per page, one more for the running sums' ends)
+_SRC, _COMPRESSED, _UNCOMPRESSED, _PAYLOAD, _VALUES, _ROW_BEGIN = range(6)
+
+
 class SceneRowGroups:
     """Scene-addressable reader of the visibility-index parquet (columns ``key`` = "scene:kind:item", ``values`` = JSON text;
     MVI:38-73): which row groups hold which scene is read off the ``key`` column's min / max statistics in the footer, so a rank
@@ -410,6 +427,86 @@ class SceneRowGroups:
             n_points = max((max(seen) for seen in lists if len(seen)), default=0) + 1
         return present, torch.from_numpy(pack_index_lists(lists, int(n_points))).to(device)
 
+    def _plan_pages(self, distinct: List[tuple]):
+        """``scene_bits`` step 1, on the host alone: the wanted (row group, row), ascending -> (the ``_Page``s that hold them, in
+        that order, None), or (None, why the device path does not take them)."""
+        pages, upload = [], 0
+        for g in sorted({g for g, _ in distinct}):
+            rows = np.array([r for gg, r in distinct if gg == g], dtype=np.int64)
+            table, page, reason = self.needed_pages(g, rows)
+            if reason is not None:
+                return None, f"row group {g}: {reason}"
+            chunk = memoryview(table["chunk"])
+            for pg in np.unique(page):
+                pos, comp = int(table["pos"][pg]), int(table["compressed"][pg])
+                pages.append(_Page(g, int(pg), np.frombuffer(chunk[pos:pos + comp], dtype=np.uint8), upload, comp,
+                                   int(table["uncompressed"][pg]), int(table["num_values"][pg]), self._CODECS[table["codec"]] == 1,
+                                   rows[page == pg] - int(table["first_row"][pg])))
+                upload += comp
+        if sum(p.uncompressed for p in pages) > 0x7fffffff:
+            return None, "2 GiB of pages or more"
+        return pages, None
+
+    def _decompress_pages(self, src, pages: List[_Page], tab_dev):
+        """``scene_bits`` step 3: the uploaded pages -> (their payloads back to back, the Snappy streams' status or None for none,
+        their routes or None for the one-wave kernel's).  An uncompressed page has ``compressed == uncompressed``."""
+        import torch
+        from . import engine
+        n_pages = len(pages)
+
+        def decompress(sel):                                           # the pages ``sel`` of the table; None: all of them
+            offs, sizes, unc = (tab_dev[r, :n_pages].contiguous() if sel is None else tab_dev[r].index_select(0, sel)
+                                for r in (_SRC, _COMPRESSED, _UNCOMPRESSED))
+            if not self.decode_by_blocks:
+                return (*engine.snappy_decompress_device(src, offs, sizes, unc), None)
+            return engine.snappy_decompress_blocks_device(src, offs, sizes, unc)
+
+        snappy = np.array([k for k, p in enumerate(pages) if p.snappy], dtype=np.int64)
+        if len(snappy) == n_pages:
+            payloads, _, status, route = decompress(None)
+            return payloads, status, route
+        # uncompressed chunks (and files that mix both): plain copies
+        unc_total = sum(p.uncompressed for p in pages)
+        payloads = torch.empty((max(unc_total, 1),), dtype=torch.uint8, device=src.device)[:unc_total]
+        status = route = None
+        if len(snappy):
+            part, part_off, status, route = decompress(torch.from_numpy(snappy).to(src.device))
+            part_off = part_off.cpu().numpy()
+        at = 0
+        for k, p in enumerate(pages):
+            if p.snappy:
+                j = int(np.searchsorted(snappy, k))
+                payloads[at:at + p.uncompressed] = part[int(part_off[j]):int(part_off[j]) + p.uncompressed]
+            else:
+                payloads[at:at + p.uncompressed] = src[p.src:p.src + p.compressed]
+            at += p.uncompressed
+        return payloads, status, route
+
+    def _repair_rows(self, got: dict, payloads, n_points):
+        """``scene_bits`` step 5: the rows the device declined get their text back from the device's pages and take the host path --
+        ``json.loads``, ``pack_index_lists`` -- into ``got["bits"]`` (widened where ``n_points`` is None and they say so)."""
+        import torch
+        from .scene import pack_index_lists
+        bits, width = got["bits"], got["n_points"]
+        declined = np.nonzero(got["row_status"])[0]
+        if not len(declined):
+            return bits
+        self.decode_stats["rows_declined"] += len(declined)
+        which = torch.from_numpy(declined).to(bits.device)
+        spans = torch.stack([got["start"], got["length"]])[:, which].cpu().numpy()
+        lists = [json.loads(bytes(payloads[int(a):int(a) + int(n)].cpu().numpy()).decode()) for a, n in zip(spans[0], spans[1])]
+        if n_points is None:
+            # the width comes from every list.  The device's figure covers every value it parsed (a row it declined for its
+            # order included; a row its parser declined counts as 0 there), these lists are the rest
+            width = max(width, max((max(seen) for seen in lists if len(seen)), default=0) + 1)
+        n_words = (width + 63) // 64
+        if n_words != bits.shape[1]:
+            wider = torch.zeros((bits.shape[0], n_words), dtype=torch.int64, device=bits.device)
+            wider[:, :min(n_words, bits.shape[1])] = bits[:, :n_words]
+            bits = wider
+        bits[which] = torch.from_numpy(pack_index_lists(lists, width)).to(bits.device)
+        return bits
+
     def scene_bits(self, scene_id: str, image_ids, n_points: Optional[int] = None, device="cuda"):
         """(present ids, bits): the requested image ids the index has, in request order, and their visible-vertex bitsets as an
         int64 device tensor [len(present), ceil(n_points / 64)] -- ``scene.pack_index_lists``' layout; ``n_points`` None: 1 + the
@@ -426,12 +523,15 @@ class SceneRowGroups:
         (Snappy pages the one-wave kernel took); ``last_decline`` says why the last scene was declined."""
         import torch
         from . import engine
-        from .scene import pack_index_lists
         image_ids = list(image_ids)
         self.decode_stats["scenes"] += 1
-        if self._path is None or not self._device_schema:
-            self._decline("not a file on disk" if self._path is None else "values is not a flat BYTE_ARRAY column")
+
+        def host(why):
+            self._decline(why)
             return self._scene_bits_host(scene_id, image_ids, n_points, device)
+
+        if self._path is None or not self._device_schema:
+            return host("not a file on disk" if self._path is None else "values is not a flat BYTE_ARRAY column")
         if self.stage_times is not None:
             import time
             self._stage_start = time.perf_counter()
@@ -444,103 +544,42 @@ class SceneRowGroups:
             return present, torch.zeros((0, (n + 63) // 64), dtype=torch.int64, device=device)
         # the distinct rows, in (row group, row) order: what the device walks; the request refers to them by position
         distinct = sorted(set(found.values()))
-        slot = {gr: k for k, gr in enumerate(distinct)}
-        parts, page_rows = [], []                                     # bytes to upload; per page: (src pos, comp, unc, nv, codec, rows)
-        upload = 0
-        for g in sorted({g for g, _ in distinct}, key=lambda g: [d[0] for d in distinct].index(g)):
-            rows = np.array([r for gg, r in distinct if gg == g], dtype=np.int64)
-            table, page, reason = self.needed_pages(g, rows)
-            if reason is not None:
-                self._decline(f"row group {g}: {reason}")
-                return self._scene_bits_host(scene_id, image_ids, n_points, device)
-            chunk = memoryview(table["chunk"])
-            for pg in np.unique(page):
-                pos, comp = int(table["pos"][pg]), int(table["compressed"][pg])
-                parts.append(np.frombuffer(chunk[pos:pos + comp], dtype=np.uint8))
-                page_rows.append((upload, comp, int(table["uncompressed"][pg]), int(table["num_values"][pg]), self._CODECS[table["codec"]],
-                                  rows[page == pg] - int(table["first_row"][pg])))
-                upload += comp
-        unc_total = sum(p[2] for p in page_rows)
-        if unc_total > 0x7fffffff:
-            self._decline("2 GiB of pages or more")
-            return self._scene_bits_host(scene_id, image_ids, n_points, device)
-        n_pages = len(page_rows)
-        host = torch.empty((max(upload, 1),), dtype=torch.uint8, pin_memory=True)
+        pages, why = self._plan_pages(distinct)
+        if pages is None:
+            return host(why)
+        n_pages, upload = len(pages), sum(p.compressed for p in pages)
+        staged = torch.empty((max(upload, 1),), dtype=torch.uint8, pin_memory=True)
         if upload:
-            np.concatenate(parts, out=host.numpy()[:upload])
-        src = host.to(device, non_blocking=True)[:upload]
+            np.concatenate([p.data for p in pages], out=staged.numpy()[:upload])
+        src = staged.to(device, non_blocking=True)[:upload]
         self.decode_stats["h2d_bytes"] += upload
         self._mark("h2d")
-        tab = np.zeros((6, n_pages + 1), dtype=np.int64)      # src offsets, compressed, uncompressed, payload offsets, values, row_begin
-        tab[0, :n_pages] = [p[0] for p in page_rows]
-        tab[1, :n_pages] = [p[1] for p in page_rows]
-        tab[2, :n_pages] = [p[2] for p in page_rows]
-        np.cumsum(tab[2, :n_pages], out=tab[3, 1:])
-        tab[4, :n_pages] = [p[3] for p in page_rows]
-        np.cumsum([len(p[5]) for p in page_rows], out=tab[5, 1:])
-        row_index = np.concatenate([p[5] for p in page_rows]).astype(np.int64)
+        tab = np.zeros((6, n_pages + 1), dtype=np.int64)
+        tab[_SRC, :n_pages] = [p.src for p in pages]
+        tab[_COMPRESSED, :n_pages] = [p.compressed for p in pages]
+        tab[_UNCOMPRESSED, :n_pages] = [p.uncompressed for p in pages]
+        np.cumsum(tab[_UNCOMPRESSED, :n_pages], out=tab[_PAYLOAD, 1:])
+        tab[_VALUES, :n_pages] = [p.num_values for p in pages]
+        np.cumsum([len(p.rows) for p in pages], out=tab[_ROW_BEGIN, 1:])
+        row_index = np.concatenate([p.rows for p in pages]).astype(np.int64)
         tab_dev = torch.from_numpy(tab).to(device)
-        snappy = np.array([k for k, p in enumerate(page_rows) if p[4] == 1], dtype=np.int64)
-        route = None
-
-        def decompress(offs, sizes, unc):
-            nonlocal route
-            if not self.decode_by_blocks:
-                return engine.snappy_decompress_device(src, offs, sizes, unc)
-            out, out_off, status, route = engine.snappy_decompress_blocks_device(src, offs, sizes, unc)
-            return out, out_off, status
-
-        if len(snappy) == n_pages:
-            pages, _, stream_status = decompress(tab_dev[0, :n_pages].contiguous(), tab_dev[1, :n_pages].contiguous(),
-                                                 tab_dev[2, :n_pages].contiguous())
-        else:                                                          # uncompressed chunks (and files that mix both): plain copies
-            pages = torch.empty((max(unc_total, 1),), dtype=torch.uint8, device=src.device)[:unc_total]
-            stream_status = None
-            if len(snappy):
-                sel = torch.from_numpy(snappy).to(device)
-                part, part_off, stream_status = decompress(tab_dev[0].index_select(0, sel), tab_dev[1].index_select(0, sel),
-                                                           tab_dev[2].index_select(0, sel))
-                part_off = part_off.cpu().numpy()
-            for k, p in enumerate(page_rows):
-                at = int(tab[3, k])
-                if p[4] == 1:
-                    j = int(np.searchsorted(snappy, k))
-                    pages[at:at + p[2]] = part[int(part_off[j]):int(part_off[j]) + p[2]]
-                elif p[1] != p[2]:
-                    self._decline("an uncompressed page whose sizes differ")
-                    return self._scene_bits_host(scene_id, image_ids, n_points, device)
-                else:
-                    pages[at:at + p[2]] = src[p[0]:p[0] + p[1]]
+        if any(not p.snappy and p.compressed != p.uncompressed for p in pages):
+            return host("an uncompressed page whose sizes differ")
+        payloads, stream_status, route = self._decompress_pages(src, pages, tab_dev)
         self._mark("decompress")
-        got = engine.index_rows_to_bits(pages, tab_dev[3, :n_pages].contiguous(), tab_dev[2, :n_pages].contiguous(),
-                                        tab_dev[4, :n_pages].contiguous(), tab_dev[5].contiguous(), torch.from_numpy(row_index).to(device),
-                                        n_points=n_points, has_levels=self._has_levels)
+        got = engine.index_rows_to_bits(payloads, tab_dev[_PAYLOAD, :n_pages].contiguous(), tab_dev[_UNCOMPRESSED, :n_pages].contiguous(),
+                                        tab_dev[_VALUES, :n_pages].contiguous(), tab_dev[_ROW_BEGIN].contiguous(),
+                                        torch.from_numpy(row_index).to(device), n_points=n_points, has_levels=self._has_levels)
         if (stream_status is not None and bool((stream_status != 0).any().item())) or bool(got["page_status"].any()):
-            self._decline("the device declined a page")
-            return self._scene_bits_host(scene_id, image_ids, n_points, device)
+            return host("the device declined a page")
         self._mark("rows_to_bits")
         if stream_status is not None:
-            routes = route.cpu().numpy() if route is not None else np.zeros(len(snappy), dtype=np.int32)
+            routes = route.cpu().numpy() if route is not None else np.zeros(len(stream_status), dtype=np.int32)
             self.decode_stats["blocks"] += int(routes.sum())
             self.decode_stats["serial_streams"] += int((routes == 0).sum())
-        bits, width = got["bits"], got["n_points"]
         self.decode_stats["rows"] += len(distinct)
-        declined = np.nonzero(got["row_status"])[0]
-        if len(declined):
-            # these rows' text comes back from the device's pages and takes the host path: json.loads, pack_index_lists
-            self.decode_stats["rows_declined"] += len(declined)
-            spans = torch.stack([got["start"], got["length"]])[:, torch.from_numpy(declined).to(device)].cpu().numpy()
-            lists = [json.loads(bytes(pages[int(a):int(a) + int(n)].cpu().numpy()).decode()) for a, n in zip(spans[0], spans[1])]
-            if n_points is None:
-                # the width comes from every list.  The device's figure covers every value it parsed (a row it declined for its
-                # order included; a row its parser declined counts as 0 there), these lists are the rest
-                width = max(width, max((max(seen) for seen in lists if len(seen)), default=0) + 1)
-            n_words = (width + 63) // 64
-            if n_words != bits.shape[1]:
-                wider = torch.zeros((bits.shape[0], n_words), dtype=torch.int64, device=bits.device)
-                wider[:, :min(n_words, bits.shape[1])] = bits[:, :n_words]
-                bits = wider
-            bits[torch.from_numpy(declined).to(device)] = torch.from_numpy(pack_index_lists(lists, width)).to(device)
+        bits = self._repair_rows(got, payloads, n_points)
+        slot = {gr: k for k, gr in enumerate(distinct)}
         order = torch.tensor([slot[found[k]] for k in present_pos], dtype=torch.int64, device=bits.device)
         if len(order) != bits.shape[0] or not bool((order == torch.arange(len(order), device=bits.device)).all().item()):
             bits = bits.index_select(0, order)

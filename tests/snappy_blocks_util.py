@@ -14,7 +14,7 @@ import visindex_decode_util as VU  # noqa: E402
 from visindex_decode_util import copy1, copy2, copy4, lit  # noqa: E402
 
 BLOCK = SU.BLOCK
-SEG = 2048                       # csrc/parquet_pages.hip: kSeg
+SEG = 2048                       # csrc/snappy_decode.hip: kSeg
 NOT_BLOCKWISE = -22
 
 

@@ -41,6 +41,9 @@ def test_integer_lists_equal_json_dumps():
     assert _texts(text, toff) == ["[]", "[]", "[]"]
     text, toff = engine.format_lists_device(torch.zeros(1, dtype=torch.int64).cuda(), torch.zeros(0, dtype=torch.int32).cuda())
     assert _texts(text, toff) == [] and toff.tolist() == [0]
+    # one list: an offsets table of one entry for the search of an item's list
+    text, toff = engine.format_lists_device(torch.tensor([0, 3]).cuda(), torch.tensor([4, 50, 600], dtype=torch.int32).cuda())
+    assert _texts(text, toff) == ["[4, 50, 600]"]
 
 
 def test_token_lists_equal_json_dumps_and_bad_ids_are_refused():

@@ -25,6 +25,7 @@ def test_batched_streams_equal_the_host_reference_and_round_trip():
     lib = _lib.load()
     cases = SU.streams()
     assert any(len(d) == 0 for _, d in cases[1:-1])                         # zero-length streams in the middle of the batch
+    assert any(len(a) == 0 and len(b) > 0 for (_, a), (_, b) in zip(cases, cases[1:]))      # ... one right in front of a stream with a block
     junk = b"\xEE" * 5                                                      # gaps between the streams: offsets, not a running sum
     blob, offsets = bytearray(), []
     for _, d in cases:
@@ -89,6 +90,23 @@ def test_string_pages_equal_the_host_reference(scene_text, page_bytes):
         assert len(want["compressed"]) > 50 and want["num_values"][0] == 1                 # an image row fills a page by itself
     else:
         assert len(want["compressed"]) == 1 and want["uncompressed"][0] > 2 * SU.BLOCK      # one page, a stream of many blocks
+
+
+@pytest.mark.parametrize("rows", [1, 5])
+def test_pages_that_end_on_a_threads_first_byte(rows):
+    """Every value is 22 bytes and fills a page: a payload of 4 + 2 + 4 + 22 = 32 bytes, so pages start at multiples of the 16 bytes
+    a thread packs -- the thread at 32 searches for the page of page 2's first byte.  One row: a page table of one entry."""
+    import torch
+    from mspa import _lib, engine
+    text = b"".join(b"[%020d]" % (7 ** k) for k in range(rows))
+    offsets = torch.arange(0, 22 * rows + 1, 22, dtype=torch.int32).cuda()
+    data = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).cuda()
+    got = engine.parquet_string_pages_device(offsets, data, 26, return_payload=True)
+    want = SU.host_pages(_lib.load(), offsets.cpu().numpy(), data.cpu().numpy(), 26)
+    assert want["uncompressed"] == [32] * rows and want["num_values"] == [1] * rows
+    assert got["num_values"].tolist() == want["num_values"] and got["uncompressed"].tolist() == want["uncompressed"]
+    assert got["payload"].cpu().numpy().tobytes() == want["payload"]
+    assert got["compressed"].tolist() == want["compressed"] and got["chunk"].cpu().numpy().tobytes() == want["chunk"]
 
 
 def _scenes():

@@ -122,6 +122,11 @@ def test_scan_finds_the_hosts_starts_and_routes():
         else:
             assert route[k] == 0, (name, int(route[k]), brc)
     assert taken >= 2 * 62 and any(n.startswith("seg_") for n, *_ in cases)
+    # what the kernels' searches for a block's and a segment's stream meet: a stream without blocks in front of one with blocks
+    # (they share a block_prefix entry), and a taken stream shorter than a segment in front of a longer one
+    lens, pairs = [len(s) for _, s, _, _ in cases], range(len(cases) - 1)
+    assert any(cases[k][2] == 0 and host[k + 1][2] > 0 for k in pairs)
+    assert any(0 < lens[k] < BU.SEG < lens[k + 1] and host[k][2] > 0 and host[k + 1][2] > 0 for k in pairs)
 
 
 def test_decode_equals_the_host_and_no_writers_stream_takes_the_fallback():

@@ -218,6 +218,10 @@ def test_edge_rows_decline_alone_and_the_result_is_the_host_paths(tmp_path, n_po
     assert np.array_equal(bits.cpu().numpy(), pack_index_lists([json.loads(rows[k]) for k in sub], 8))
     present, bits = index.scene_bits("sceneE", ["empty"])
     assert tuple(bits.shape) == (1, 1) and int(bits.sum()) == 0
+    present, bits = index.scene_bits("sceneE", ["one"])                       # one page, one row, one value: tables of one entry
+    assert np.array_equal(bits.cpu().numpy(), pack_index_lists([[7]], 8)) and index.decode_stats["rows_declined"] == len(declined) + 1
+    # (in the file an empty row stands in front of a non-empty one: "empty", "duplicate")
+    assert list(rows)[:2] == ["empty", "duplicate"]
 
 
 # ------------------------------------------------------------------------------------------------------------------- end to end

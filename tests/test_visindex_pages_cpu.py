@@ -81,6 +81,43 @@ def test_the_files_have_the_shapes_the_cases_are_about(files):
     assert len(set(pages_of("assembled")[1][0][1].tolist())) > 1
 
 
+def test_the_plan_of_scene_bits_names_the_pages_a_python_walk_finds_the_rows_in(files, tmp_path):
+    """Step 1 of ``scene_bits`` (``_plan_pages``: host code, no device): for scenes whose rows span several pages -- and, in
+    split_images, two row groups -- the plan holds exactly the pages of the walk that hold those rows, in file order, with the
+    headers' sizes, the rows counted from each page's first row and the pages' bytes back to back; for a file the device path
+    does not take it gives ``needed_pages``' reason behind the row group."""
+    import pyarrow as pa
+    for name in ("page_per_row", "assembled", "split_images"):
+        path = files[name][0]
+        index = visindex.SceneRowGroups(path)
+        ids, texts = VU.image_ids_of(path, "scene0000_00")
+        distinct = sorted(set(index.image_rows("scene0000_00", ids).values()))
+        pages, why = index._plan_pages(distinct)
+        assert why is None and len(pages) > 1, name
+        want = []
+        for g in sorted({g for g, _ in distinct}):
+            walk = VU.python_page_walk(path, g)
+            where = {row: k for k, w in enumerate(walk) for row, _ in w[2]}
+            rows = [r for gg, r in distinct if gg == g]
+            for k in sorted({where[r] for r in rows}):
+                first = walk[k][2][0][0]
+                want.append((g, k, walk[k][3][0], walk[k][3][1], len(walk[k][2]), [r - first for r in rows if where[r] == k]))
+        assert [(p.group, p.index, p.compressed, p.uncompressed, p.num_values, p.rows.tolist()) for p in pages] == want, name
+        assert [p.src for p in pages] == np.concatenate([[0], np.cumsum([p.compressed for p in pages])])[:-1].tolist()
+        assert all(p.snappy and len(p.data) == p.compressed for p in pages)
+        seen = []
+        for p in pages:                                                          # the bytes are those pages': the wanted texts are in them
+            body = pa.Codec("snappy").decompress(p.data.tobytes(), decompressed_size=p.uncompressed).to_pybytes()
+            seen += [i for i in ids if texts[i].encode() in body]
+        assert sorted(seen) == sorted(ids), name
+    gz = VU._write(VU.SU.index_table(), str(tmp_path / "gzip.parquet"), use_dictionary=False, compression="gzip")
+    for path, reason in ((files["defaults"][0], "row group 0: a data page that is not PLAIN"),
+                         (files["v2"][0], "row group 0: a data page that is not v1"), (gz, "row group 0: codec GZIP")):
+        index = visindex.SceneRowGroups(path)
+        ids, _ = VU.image_ids_of(path, "scene0000_00")
+        assert index._plan_pages(sorted(set(index.image_rows("scene0000_00", ids).values()))) == (None, reason)
+
+
 def test_decode_mode_reads_the_switch(monkeypatch):
     monkeypatch.delenv("MSPA_VISINDEX_DECODE", raising=False)
     assert visindex.decode_mode() == "host"

@@ -236,8 +236,9 @@ def expected_bits(texts, image_ids, n_points):
 
 
 def python_page_walk(path, group):
-    """A pure-Python walk of row group ``group``'s values chunk: [(page type, encoding, [(row in the group, value bytes)])] with the
-    rows of every DATA_PAGE (v1, PLAIN) decoded; other pages come with an empty row list.  pyarrow's codec decompresses."""
+    """A pure-Python walk of row group ``group``'s values chunk: [(page type, encoding, [(row in the group, value bytes)],
+    (compressed size, uncompressed size))] with the rows of every DATA_PAGE (v1, PLAIN) decoded; other pages come with an empty
+    row list.  pyarrow's codec decompresses."""
     import pyarrow as pa
     import pyarrow.parquet as pq
     from mspa import parquet_splice as PS
@@ -259,7 +260,7 @@ def python_page_walk(path, group):
         dph = PS._get(h, 5)
         if ptype != 0 or PS._get(dph, 2) != 0:
             nv = PS._get(dph, 1) if dph else (PS._get(PS._get(h, 8), 1) if ptype == 3 else 0)
-            out.append((ptype, None if dph is None else PS._get(dph, 2), []))
+            out.append((ptype, None if dph is None else PS._get(dph, 2), [], (comp, unc)))
             row += nv if ptype in (0, 3) else 0
             continue
         if col.compression == "SNAPPY":
@@ -275,5 +276,5 @@ def python_page_walk(path, group):
             q += 4 + n
             row += 1
         assert q == len(body)
-        out.append((ptype, 0, rows))
+        out.append((ptype, 0, rows, (comp, unc)))
     return out
