@@ -691,6 +691,23 @@ int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t ro
  *   belong to page p; row_index_dev[r] is the row's value number inside its page, ascending within a page.  Writes
  *   out_start_dev[r] (position of the value's text in pages_dev) and out_len_dev[r]; page_status_dev[p]: 0, 1 a length or a
  *   table entry outside the page, 2 levels that are not a run of ones (the rows of such a page get 0 / 0).
+ * mspa_rle_hybrid_take_host  the reference of parquet's RLE / bit-packed hybrid (csrc/rle_hybrid_core.h), the encoding of a
+ *   dictionary-coded page's indices: src[0, src_len) is runs, each behind a ULEB128 header h -- h & 1 == 0: h >> 1 times ONE
+ *   value of ceil(bit_width / 8) little-endian bytes; h & 1 == 1: h >> 1 groups of 8 values of bit_width bits, LSB first (the
+ *   last group may be padding beyond n_values).  out[i] (int32) = value rows[i]; rows (int64) ascend strictly and are
+ *   < n_values.  The walk stops at the last needed row and reads nothing outside [src, src + src_len).  Returns 0, or: -32 a
+ *   bit width outside 0 .. 32; -33 a header of more than 5 bytes or one that runs past the input; -34 a run of zero values;
+ *   -35 a run whose bytes pass the input's end; -36 the runs end before a needed row; MSPA_EINVAL for rows that do not ascend
+ *   or are >= n_values, a null pointer or a size outside 0 .. 2^31 - 1.
+ * mspa_parquet_dict_spans_device  mspa_parquet_plain_spans_device for dictionary-coded data pages (RLE_DICTIONARY,
+ *   PLAIN_DICTIONARY), with the same page and row tables: behind the levels (has_levels, as above) a page is one byte of bit
+ *   width and a hybrid stream of indices.  The page's dictionary is entries dict_begin_dev[p] .. + dict_count_dev[p] of a span
+ *   table dict_start_dev / dict_len_dev (int64, n_dict entries) -- what mspa_parquet_plain_spans_device writes for the
+ *   decompressed dictionary page (has_levels = 0, every entry a row), so pages of several row groups each name their own.
+ *   Writes out_index_dev[r] (int32, the row's index), out_start_dev[r] / out_len_dev[r] (the entry's span);
+ *   page_status_dev[p]: 0, 1 a table entry outside the page (or rows that do not ascend), 2 levels, 3 malformed runs --
+ *   page_code_dev[p] (int32) then holds mspa_rle_hybrid_take_host's code, else 0 --, 4 an index >= dict_count_dev[p]; the
+ *   rows of a declined page get -1 and 0 / 0.  One lane per page: a chain of one step per run in front of the last needed row.
  * mspa_index_rows_brackets_device  row r's text must be '[' ... ']' with JSON white space around: out_inner_start_dev /
  *   out_inner_len_dev = what lies between; row_status_dev[r] = 1 and an empty span otherwise.
  * mspa_index_rows_gather_device  the spans back to back: inner_prefix_dev [n_rows + 1] is the exclusive prefix sum of the
@@ -721,6 +738,14 @@ int mspa_parquet_plain_spans_device(const uint8_t *pages_dev, int64_t pages_byte
                                     const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages, int32_t has_levels,
                                     const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows, int64_t *out_start_dev,
                                     int64_t *out_len_dev, int32_t *page_status_dev, void *stream);
+int mspa_rle_hybrid_take_host(const uint8_t *src, int64_t src_len, int32_t bit_width, int64_t n_values, const int64_t *rows, int64_t n_rows,
+                              int32_t *out);
+int mspa_parquet_dict_spans_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
+                                   const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages, int32_t has_levels,
+                                   const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows,
+                                   const int64_t *dict_begin_dev, const int64_t *dict_count_dev, const int64_t *dict_start_dev,
+                                   const int64_t *dict_len_dev, int64_t n_dict, int32_t *out_index_dev, int64_t *out_start_dev,
+                                   int64_t *out_len_dev, int32_t *page_status_dev, int32_t *page_code_dev, void *stream);
 int mspa_index_rows_brackets_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *start_dev, const int64_t *len_dev,
                                     int64_t n_rows, int64_t *out_inner_start_dev, int64_t *out_inner_len_dev, int32_t *row_status_dev,
                                     void *stream);

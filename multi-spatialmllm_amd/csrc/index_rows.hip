@@ -7,6 +7,8 @@
 //                image_to_points rows open the chunk (a few values per ~1 MiB page); a row group that mixes scenes may put
 //                ~20 k short point_to_images rows of the scene before in front of them -- 20 k dependent L2 loads, a few
 //                milliseconds for that one lane (not measured on such a file).
+//   dict spans   one lane per needed dictionary-coded page walks the RLE / bit-packed runs of indices (csrc/rle_hybrid_core.h) to
+//                its last needed row and looks the rows up in the span table `spans` wrote for the dictionary page's entries.
 //   brackets     one lane per row: '[' and ']' behind / in front of JSON white space.
 //   gather       the texts between the brackets back to back (what K11's list parser takes), one byte per lane.
 //   lists->bits  one lane per parsed value.  A list ascends, so the values of one 64-bit word are neighbours in the value array:
@@ -16,12 +18,15 @@
 // No atomics; every load and store is checked against the buffer it goes to.
 #include "mspa_common.h"
 #include "snappy_core.h"
+#include "rle_hybrid_core.h"
 
 namespace mspa {
 namespace index_rows {
 
 constexpr int32_t kPageBounds = 1;       // a length runs past the page, or the tables do not describe it
 constexpr int32_t kPageLevels = 2;       // the definition levels are not one run of ones
+constexpr int32_t kPageRuns = 3;         // dictionary-coded pages: the index runs are malformed (rle_hybrid's code beside it)
+constexpr int32_t kPageIndex = 4;        // dictionary-coded pages: an index >= the dictionary's entry count
 constexpr int32_t kRowBrackets = 1;      // a row's text is not [ ... ]
 constexpr int32_t kRowOrder = 32;        // lists->bits: a value below its predecessor     (K11's parser owns bits 2 .. 16)
 constexpr int32_t kRowRange = 64;        // lists->bits: a value outside [0, n_points)
@@ -85,6 +90,68 @@ __global__ __launch_bounds__(64) void plain_spans_kernel(const uint8_t *__restri
         out_len[r] = 0;
     }
     page_status[pg] = bad;
+}
+
+// One lane per needed dictionary-coded page (RLE_DICTIONARY / PLAIN_DICTIONARY): [levels,] one byte of bit width, then the
+// indices as an RLE / bit-packed hybrid stream (csrc/rle_hybrid_core.h).  The lane takes the needed rows' indices through
+// rle_hybrid::take -- a chain of one step per run in front of the last needed row -- and looks each one up in the page's
+// dictionary: entries [dict_begin[pg], + dict_count[pg]) of the span table (dict_start / dict_len) that plain_spans_kernel wrote
+// for the dictionary pages' PLAIN entries.  A page that declines gives its rows index -1 and an empty span.
+__global__ __launch_bounds__(64) void dict_spans_kernel(const uint8_t *__restrict__ pages, int64_t pages_bytes,
+                                                        const int64_t *__restrict__ page_off, const int64_t *__restrict__ page_size,
+                                                        const int64_t *__restrict__ page_values, int64_t n_pages, int32_t has_levels,
+                                                        const int64_t *__restrict__ row_begin, const int64_t *__restrict__ row_index,
+                                                        int64_t n_rows, const int64_t *__restrict__ dict_begin,
+                                                        const int64_t *__restrict__ dict_count, const int64_t *__restrict__ dict_start,
+                                                        const int64_t *__restrict__ dict_len, int64_t n_dict, int32_t *out_index,
+                                                        int64_t *__restrict__ out_start, int64_t *__restrict__ out_len,
+                                                        int32_t *__restrict__ page_status, int32_t *__restrict__ page_code) {
+    const int64_t pg = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (pg >= n_pages) return;
+    const int64_t off = page_off[pg], size = page_size[pg], nv = page_values[pg], d0 = dict_begin[pg], dn = dict_count[pg];
+    const int64_t r0 = row_begin[pg], r1 = row_begin[pg + 1];
+    int32_t bad = 0, code = 0;
+    if (r0 < 0 || r1 < r0 || r1 > n_rows) {
+        page_status[pg] = kPageBounds;
+        page_code[pg] = 0;
+        return;
+    }
+    if (off < 0 || size < 0 || off > pages_bytes - size || nv < 0 || d0 < 0 || dn < 0 || d0 > n_dict - dn) bad = kPageBounds;
+    const uint8_t *__restrict__ q = pages + off;
+    int64_t pos = 0;
+    if (!bad && has_levels) {
+        const int32_t head = snappy::page_head_len(nv);
+        if (head > size) bad = kPageBounds;
+        for (int32_t r = 0; !bad && r < head; ++r)
+            if (q[r] != snappy::page_head_byte(nv, r)) bad = kPageLevels;
+        pos = head;
+    }
+    if (!bad && pos >= size) bad = kPageBounds;                  // no room for the bit width
+    if (!bad) {
+        const int rc = rle_hybrid::take(q + pos + 1, size - pos - 1, (int32_t)q[pos], nv, row_index + r0, r1 - r0, out_index + r0);
+        if (rc == rle_hybrid::kErrRows) {
+            bad = kPageBounds;
+        } else if (rc != 0) {
+            bad = kPageRuns;
+            code = rc;
+        }
+    }
+    for (int64_t r = r0; !bad && r < r1; ++r) {
+        const int64_t k = (int64_t)(uint32_t)out_index[r];       // this lane's own stores
+        if (k >= dn) {
+            bad = kPageIndex;
+            break;
+        }
+        out_start[r] = dict_start[d0 + k];
+        out_len[r] = dict_len[d0 + k];
+    }
+    for (int64_t r = r0; bad && r < r1; ++r) {                   // the rows this page did not give
+        out_index[r] = -1;
+        out_start[r] = 0;
+        out_len[r] = 0;
+    }
+    page_status[pg] = bad;
+    page_code[pg] = code;
 }
 
 __global__ __launch_bounds__(64) void row_brackets_kernel(const uint8_t *__restrict__ pages, int64_t pages_bytes,
@@ -160,6 +227,35 @@ extern "C" int mspa_parquet_plain_spans_device(const uint8_t *pages_dev, int64_t
                        page_offsets_dev, page_bytes_dev, page_values_dev, n_pages, has_levels, row_begin_dev, row_index_dev, n_rows, out_start_dev,
                        out_len_dev, page_status_dev);
     return check_hip(hipGetLastError(), "mspa_parquet_plain_spans_device");
+}
+
+extern "C" int mspa_rle_hybrid_take_host(const uint8_t *src, int64_t src_len, int32_t bit_width, int64_t n_values, const int64_t *rows,
+                                         int64_t n_rows, int32_t *out) {
+    if (src_len < 0 || src_len > 0x7fffffffLL || n_values < 0 || n_rows < 0)
+        return fail(MSPA_EINVAL, "mspa_rle_hybrid_take_host: 0 <= src_len < 2^31, 0 <= n_values, n_rows");
+    if ((src_len > 0 && !src) || (n_rows > 0 && (!rows || !out))) return fail(MSPA_EINVAL, "mspa_rle_hybrid_take_host: null pointer");
+    const int rc = rle_hybrid::take(src, src_len, bit_width, n_values, rows, n_rows, out);
+    return rc == rle_hybrid::kErrRows ? fail(MSPA_EINVAL, "mspa_rle_hybrid_take_host: rows ascend and are < n_values") : rc;
+}
+
+extern "C" int mspa_parquet_dict_spans_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
+                                              const int64_t *page_bytes_dev, const int64_t *page_values_dev, int64_t n_pages,
+                                              int32_t has_levels, const int64_t *row_begin_dev, const int64_t *row_index_dev, int64_t n_rows,
+                                              const int64_t *dict_begin_dev, const int64_t *dict_count_dev, const int64_t *dict_start_dev,
+                                              const int64_t *dict_len_dev, int64_t n_dict, int32_t *out_index_dev, int64_t *out_start_dev,
+                                              int64_t *out_len_dev, int32_t *page_status_dev, int32_t *page_code_dev, void *stream) {
+    if (pages_bytes < 0 || n_pages < 0 || n_rows < 0 || n_dict < 0 || n_pages > (int64_t)0x7fffffff * 64 || (has_levels != 0 && has_levels != 1))
+        return fail(MSPA_EINVAL, "mspa_parquet_dict_spans_device: bad size");
+    if (n_pages == 0) return n_rows == 0 ? MSPA_OK : fail(MSPA_EINVAL, "mspa_parquet_dict_spans_device: rows without pages");
+    if (!page_offsets_dev || !page_bytes_dev || !page_values_dev || !row_begin_dev || !dict_begin_dev || !dict_count_dev || !page_status_dev ||
+        !page_code_dev || (pages_bytes > 0 && !pages_dev) || (n_dict > 0 && (!dict_start_dev || !dict_len_dev)) ||
+        (n_rows > 0 && (!row_index_dev || !out_index_dev || !out_start_dev || !out_len_dev)))
+        return fail(MSPA_EINVAL, "mspa_parquet_dict_spans_device: null pointer");
+    hipLaunchKernelGGL(index_rows::dict_spans_kernel, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, (hipStream_t)stream, pages_dev, pages_bytes,
+                       page_offsets_dev, page_bytes_dev, page_values_dev, n_pages, has_levels, row_begin_dev, row_index_dev, n_rows, dict_begin_dev,
+                       dict_count_dev, dict_start_dev, dict_len_dev, n_dict, out_index_dev, out_start_dev, out_len_dev, page_status_dev,
+                       page_code_dev);
+    return check_hip(hipGetLastError(), "mspa_parquet_dict_spans_device");
 }
 
 extern "C" int mspa_index_rows_brackets_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *start_dev, const int64_t *len_dev,

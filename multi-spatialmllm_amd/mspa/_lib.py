@@ -24,6 +24,8 @@ SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
 SNAPPY_EPREAMBLE, SNAPPY_ETRUNCATED, SNAPPY_EOVERRUN, SNAPPY_EOFFSET, SNAPPY_ETRAILING, SNAPPY_ESHORT = -16, -17, -18, -19, -20, -21
 SNAPPY_NOT_BLOCKWISE = -22     # mspa_snappy_block_starts_host alone: a valid stream that does not decode block by block
 SNAPPY_SEGMENT = 2048          # csrc/snappy_decode.hip: kSeg, the compressed bytes one wave of the block-start scan takes
+# csrc/rle_hybrid_core.h: what mspa_rle_hybrid_take_host returns for, and mspa_parquet_dict_spans_device writes as the code of, runs it declines
+RLE_EBITWIDTH, RLE_EHEADER, RLE_EZERORUN, RLE_ETRUNCATED, RLE_ESHORT = -32, -33, -34, -35, -36
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
@@ -164,6 +166,10 @@ _SIGNATURES = {
                                                      c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mspa_parquet_plain_spans_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_rle_hybrid_take_host": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p]),
+    "mspa_parquet_dict_spans_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                               c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]),
     "mspa_index_rows_brackets_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mspa_index_rows_gather_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "mspa_index_lists_to_bits_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -1013,6 +1013,85 @@ def snappy_decompress_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nb
     return out[:total], out_offsets, status, route
 
 
+def _check_page_tables(page_offsets, page_sizes, page_values, row_begin, row_index):
+    """The page and row tables the span kernels read -> (n_pages, n_rows)."""
+    n_pages = _check_streams(page_offsets, page_sizes)
+    _check("page_values", page_values, torch.int64, (n_pages,))
+    _check("row_begin", row_begin, torch.int64, (n_pages + 1,))
+    n_rows = _check("row_index", row_index, torch.int64, (None,)).shape[0]
+    _require(n_pages > 0 or n_rows == 0, "rows need pages")
+    return n_pages, n_rows
+
+
+def parquet_plain_spans_device(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
+                               row_begin: torch.Tensor, row_index: torch.Tensor, has_levels: bool = True):
+    """Where the needed rows' texts lie in PLAIN BYTE_ARRAY pages (mspa_parquet_plain_spans_device; the tables as
+    ``index_rows_to_bits`` describes them) -> (start int64 [rows], length int64 [rows], page_status int32 [pages]), on the
+    device.  With ``has_levels=False`` and every entry as a row, a decompressed dictionary page gives the span table
+    ``parquet_dict_spans_device`` looks its indices up in.  Only enqueues."""
+    n_pages, n_rows = _check_page_tables(page_offsets, page_sizes, page_values, row_begin, row_index)
+    _check("pages", pages, torch.uint8, (None,))
+    dev = pages.device
+    start = torch.zeros((n_rows,), dtype=torch.int64, device=dev)
+    length = torch.zeros((n_rows,), dtype=torch.int64, device=dev)
+    page_status = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    if n_pages:
+        _lib.check(_lib.load().mspa_parquet_plain_spans_device(_ptr(pages) if pages.numel() else None, pages.numel(), _ptr(page_offsets),
+                                                               _ptr(page_sizes), _ptr(page_values), n_pages, 1 if has_levels else 0,
+                                                               _ptr(row_begin), _ptr(row_index), n_rows, _ptr(start), _ptr(length),
+                                                               _ptr(page_status), _stream_ptr()))
+    return start, length, page_status
+
+
+def parquet_dict_spans_device(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
+                              row_begin: torch.Tensor, row_index: torch.Tensor, dict_begin: torch.Tensor, dict_count: torch.Tensor,
+                              dict_start: torch.Tensor, dict_length: torch.Tensor, has_levels: bool = True):
+    """``parquet_plain_spans_device`` for dictionary-coded data pages (RLE_DICTIONARY / PLAIN_DICTIONARY: a byte of bit width,
+    then the indices as RLE / bit-packed runs), the same page and row tables.  Page p's dictionary is entries ``dict_begin[p] :
+    dict_begin[p] + dict_count[p]`` of the span table ``dict_start`` / ``dict_length`` (all int64, on the device) -- the spans of
+    the dictionary pages' entries in ``pages``.  Returns (index int32 [rows], start int64 [rows], length int64 [rows],
+    page_status int32 [pages], page_code int32 [pages]) on the device.  Status: 0 taken, 1 a table entry outside the page, 2
+    levels, 3 malformed runs -- the code is then mspa_rle_hybrid_take_host's (``_lib.RLE_E*``) --, 4 an index beyond the
+    dictionary; a declined page's rows get index -1 and an empty span.  Only enqueues."""
+    n_pages, n_rows = _check_page_tables(page_offsets, page_sizes, page_values, row_begin, row_index)
+    _check("pages", pages, torch.uint8, (None,))
+    _check("dict_begin", dict_begin, torch.int64, (n_pages,))
+    _check("dict_count", dict_count, torch.int64, (n_pages,))
+    n_dict = _check("dict_start", dict_start, torch.int64, (None,)).shape[0]
+    _check("dict_length", dict_length, torch.int64, (n_dict,))
+    dev = pages.device
+    index = torch.full((n_rows,), -1, dtype=torch.int32, device=dev)
+    start = torch.zeros((n_rows,), dtype=torch.int64, device=dev)
+    length = torch.zeros((n_rows,), dtype=torch.int64, device=dev)
+    page_status = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    page_code = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    if n_pages:
+        _lib.check(_lib.load().mspa_parquet_dict_spans_device(
+            _ptr(pages) if pages.numel() else None, pages.numel(), _ptr(page_offsets), _ptr(page_sizes), _ptr(page_values), n_pages,
+            1 if has_levels else 0, _ptr(row_begin), _ptr(row_index), n_rows, _ptr(dict_begin), _ptr(dict_count),
+            _ptr(dict_start) if n_dict else None, _ptr(dict_length) if n_dict else None, n_dict, _ptr(index), _ptr(start), _ptr(length),
+            _ptr(page_status), _ptr(page_code), _stream_ptr()))
+    return index, start, length, page_status, page_code
+
+
+def rle_hybrid_take_host(stream, bit_width: int, n_values: int, rows) -> Tuple[int, np.ndarray]:
+    """mspa_rle_hybrid_take_host on the host: values ``rows`` (ascending, < ``n_values``) of the RLE / bit-packed hybrid
+    ``stream`` (bytes) -> (0 or the code it is declined with (``_lib.RLE_E*``), int32 [len(rows)]).  Rows that do not ascend or
+    are >= ``n_values`` raise (MSPA_EINVAL)."""
+    stream = bytes(stream)
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    _require(rows.ndim == 1, "rows: one dimension")
+    _require(-(1 << 31) <= int(bit_width) < (1 << 31) and 0 <= int(n_values), "bit_width: an int32; n_values >= 0")
+    _require(len(stream) <= 0x7fffffff, "stream: less than 2 GiB")
+    src = np.frombuffer(stream, dtype=np.uint8)
+    out = np.full(len(rows), -1, dtype=np.int32)
+    rc = int(_lib.load().mspa_rle_hybrid_take_host(src.ctypes.data if len(stream) else None, len(stream), int(bit_width), int(n_values),
+                                                   rows.ctypes.data if len(rows) else None, len(rows), out.ctypes.data if len(rows) else None))
+    if rc == _lib.MSPA_EINVAL:
+        _lib.check(rc)
+    return rc, out
+
+
 def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
                        row_begin: torch.Tensor, row_index: torch.Tensor, n_points: Optional[int] = None, has_levels: bool = True):
     """Rows of the visibility index straight from their pages to bitset rows, on the device.  ``pages`` (uint8) holds the
@@ -1028,28 +1107,33 @@ def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_siz
     (given, or 1 + the largest parsed value), ``page_status`` / ``row_status`` (int32 numpy; non-zero = declined: that page's
     rows / that row belong to the host path, their ``bits`` are unspecified), ``start`` / ``length`` (int64, device: where each
     row's text lies in ``pages``).  Less than 2 GiB of list text a call.  Synchronises (three or four small read-backs)."""
-    lib = _lib.load()
-    n_pages = _check_streams(page_offsets, page_sizes)
-    _check("pages", pages, torch.uint8, (None,))
-    _check("page_values", page_values, torch.int64, (n_pages,))
-    _check("row_begin", row_begin, torch.int64, (n_pages + 1,))
-    n_rows = _check("row_index", row_index, torch.int64, (None,)).shape[0]
     _require(n_points is None or 0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
-    _require(n_pages > 0 or n_rows == 0, "rows need pages")
+    start, length, page_status = parquet_plain_spans_device(pages, page_offsets, page_sizes, page_values, row_begin, row_index, has_levels)
+    return index_spans_to_bits(pages, start, length, n_points, page_status)
+
+
+def index_spans_to_bits(pages: torch.Tensor, start: torch.Tensor, length: torch.Tensor, n_points: Optional[int] = None,
+                        page_status: Optional[torch.Tensor] = None):
+    """``index_rows_to_bits`` behind the span kernels: row r's text is ``pages[start[r] : start[r] + length[r]]`` (int64, on the
+    device -- from ``parquet_plain_spans_device``, ``parquet_dict_spans_device`` or both merged) -> the same dict;
+    ``page_status`` (int32, device) rides along in the read-back of the rows' status."""
+    lib = _lib.load()
+    _check("pages", pages, torch.uint8, (None,))
+    n_rows = _check("start", start, torch.int64, (None,)).shape[0]
+    _check("length", length, torch.int64, (n_rows,))
+    _require(n_points is None or 0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
+    if page_status is None:
+        page_status = torch.zeros((0,), dtype=torch.int32, device=pages.device)
+    n_pages = _check("page_status", page_status, torch.int32, (None,)).shape[0]
     dev, st = pages.device, _stream_ptr()
     i64 = dict(dtype=torch.int64, device=dev)
-    start, length = torch.zeros((n_rows,), **i64), torch.zeros((n_rows,), **i64)
     inner_start, inner_len = torch.empty((n_rows,), **i64), torch.empty((n_rows,), **i64)
-    page_status = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
     status = torch.zeros((3, max(n_rows, 1)), dtype=torch.int32, device=dev)                 # brackets, parser, bits
     if n_rows == 0:
         n_points = int(n_points or 1)
         return {"bits": torch.zeros((0, (n_points + 63) // 64), **i64), "n_points": n_points, "page_status": np.zeros(n_pages, np.int32),
                 "row_status": np.zeros(0, np.int32), "start": start, "length": length}
     pages_ptr = _ptr(pages) if pages.numel() else None
-    _lib.check(lib.mspa_parquet_plain_spans_device(pages_ptr, pages.numel(), _ptr(page_offsets), _ptr(page_sizes), _ptr(page_values), n_pages,
-                                                   1 if has_levels else 0, _ptr(row_begin), _ptr(row_index), n_rows, _ptr(start), _ptr(length),
-                                                   _ptr(page_status), st))
     _lib.check(lib.mspa_index_rows_brackets_device(pages_ptr, pages.numel(), _ptr(start), _ptr(length), n_rows, _ptr(inner_start),
                                                    _ptr(inner_len), _ptr(status[0]), st))
     prefix = torch.zeros((n_rows + 1,), **i64)                                                # torch as plumbing: the prefix sums

@@ -234,6 +234,15 @@ def from_bits(bits, image_ids: List[str], n_points: int, text: bool = False, ind
     return csr
 
 
+def _uleb128(v: int) -> bytes:
+    out = bytearray()
+    while True:
+        out.append((v & 0x7F) | (0x80 if v > 0x7F else 0))
+        v >>= 7
+        if not v:
+            return bytes(out)
+
+
 class _Page(NamedTuple):
     """One page ``SceneRowGroups.scene_bits`` uploads: page ``index`` of row group ``group``'s ``values_pages`` table."""
     group: int
@@ -245,6 +254,16 @@ class _Page(NamedTuple):
     num_values: int
     snappy: bool              # False: the chunk is not compressed
     rows: np.ndarray          # the wanted rows as value numbers inside the page (its first row is 0), ascending
+    # page_kinds "any" only (a "plain" plan leaves the defaults).  ``kind``: _PLAIN_PAGE, _DICT_CODED (a data page of dictionary
+    # indices) or _DICTIONARY (the chunk's dictionary page: no rows; ``num_values`` = its entries); ``dictionary``: where a
+    # _DICT_CODED page's dictionary page stands in the plan; ``v2``: a DATA_PAGE_V2 -- ``data`` / ``src`` / the sizes are then
+    # those of the values part alone, behind the level bytes the host has checked
+    kind: int = 0
+    dictionary: int = -1
+    v2: bool = False
+
+
+_PLAIN_PAGE, _DICT_CODED, _DICTIONARY = range(3)
 
 
 # the rows of the page table ``scene_bits`` sends to the device (one column per page, one more for the running sums' ends)
@@ -272,7 +291,7 @@ class SceneRowGroups:
         self._page_tables: Dict[int, dict] = {}
         self._keys: Dict[int, object] = {}
         self.decode_stats = {"scenes": 0, "scenes_declined": 0, "rows": 0, "rows_declined": 0, "h2d_bytes": 0, "blocks": 0,
-                             "serial_streams": 0}
+                             "serial_streams": 0, "dict_pages": 0, "v2_pages": 0}
         self.decode_by_blocks = True      # False: every page by the one-wave kernel (tools/visindex_decode_bench.py times both)
         self.last_decline: Optional[str] = None
         self.stage_times: Optional[dict] = None
@@ -296,15 +315,23 @@ class SceneRowGroups:
     # ------------------------------------------------------------------------------------------------ pages -> bitsets, on the device
     # parquet.thrift numbers
     _DATA_PAGE, _PLAIN, _RLE = 0, 0, 3
+    _DICTIONARY_PAGE, _DATA_PAGE_V2, _PLAIN_DICTIONARY, _RLE_DICTIONARY = 2, 3, 2, 8
     _CODECS = {"UNCOMPRESSED": 0, "SNAPPY": 1}
+    # which of a scene's needed pages ``scene_bits`` takes.  "plain": v1 DATA_PAGEs with PLAIN values only -- any other needed
+    # page sends the whole scene to the host path.  "any" (what the readers set with MSPA_VISINDEX_DECODE=device): dictionary-coded
+    # data pages (RLE_DICTIONARY, PLAIN_DICTIONARY) behind their chunk's dictionary page and DATA_PAGE_V2 as well -- the
+    # layouts of pyarrow's defaults, of version="1.0" and of data_page_version="2.0"
+    page_kinds = "plain"
 
     def values_pages(self, g: int) -> dict:
         """The page table of row group ``g``'s ``values`` column chunk, from the thrift page headers (``parquet_splice._Reader``):
         ``start`` (the chunk's position in the file), ``bytes`` (its compressed size) and, per page in file order, int64 arrays
         ``pos`` (the payload's position inside the chunk), ``compressed``, ``uncompressed``, ``num_values``, ``type``,
         ``encoding`` (-1 where the page has none), ``levels`` (a v1 data page's definition-level encoding, else -1) and
-        ``first_row`` (rows of the group in front of it; ``n_pages + 1`` entries), ``codec`` (the chunk's, as pyarrow names it).
-        Cached: a few numbers per page."""
+        ``first_row`` (rows of the group in front of it; ``n_pages + 1`` entries), ``codec`` (the chunk's, as pyarrow names it);
+        ``dict_values`` (a dictionary page's entry count, else 0 -- ``num_values`` stays 0 there: a dictionary page holds no
+        row) and, for v2 data pages, ``def_bytes`` / ``rep_bytes`` (the level bytes that lie uncompressed in front of the
+        values), ``num_nulls`` and ``is_compressed`` (0 / 0 / 0 / 1 for every other page).  Cached: a few numbers per page."""
         if g in self._page_tables:
             return self._page_tables[g]
         from . import parquet_splice as PS
@@ -321,7 +348,7 @@ class SceneRowGroups:
         if len(chunk) != size:
             raise ValueError("visindex: the values chunk ends beyond the file")
         self._mark("file_read")
-        rows, p = [], 0
+        rows, more, p = [], [], 0
         while p < size:
             r = PS._Reader(chunk, p)
             h = r.struct()
@@ -330,13 +357,17 @@ class SceneRowGroups:
             comp = PS._get(h, 3)
             rows.append((r.p, comp, PS._get(h, 2), PS._get(body, 1, 0) if (v1 or v2) else 0, PS._get(h, 1),
                          PS._get(body, 4 if v2 else 2, -1) if body else -1, PS._get(v1, 3, -1) if v1 else -1))
+            more.append((PS._get(dic, 1, 0) if dic else 0, PS._get(v2, 5, 0) if v2 else 0, PS._get(v2, 6, 0) if v2 else 0,
+                         PS._get(v2, 2, 0) if v2 else 0, int(bool(PS._get(v2, 7, True))) if v2 else 1))
             p = r.p + comp
         if p != size:
             raise ValueError("visindex: the page headers do not add up to the values chunk")
         t = np.array(rows, dtype=np.int64).reshape(-1, 7)
+        m = np.array(more, dtype=np.int64).reshape(-1, 5)
         table = {"start": int(start), "bytes": int(size), "codec": str(col.compression), "pos": t[:, 0], "compressed": t[:, 1],
                  "uncompressed": t[:, 2], "num_values": t[:, 3], "type": t[:, 4], "encoding": t[:, 5], "levels": t[:, 6],
-                 "first_row": np.concatenate([[0], np.cumsum(t[:, 3])]), "chunk": None}
+                 "first_row": np.concatenate([[0], np.cumsum(t[:, 3])]), "dict_values": m[:, 0], "def_bytes": m[:, 1], "rep_bytes": m[:, 2],
+                 "num_nulls": m[:, 3], "is_compressed": m[:, 4], "chunk": None}
         self._page_tables[g] = table
         self._mark("header_walk")
         table = dict(table, chunk=chunk)                      # the bytes go to this caller only: the cache keeps numbers
@@ -373,7 +404,7 @@ class SceneRowGroups:
         """(page table of group ``g`` with its chunk's bytes, page index of every row of ``rows``, reason) -- ``reason`` is None
         when the device path takes every page these rows lie in: v1 DATA_PAGE, PLAIN, codec SNAPPY or none, RLE definition
         levels; otherwise it says what is in the way (a dictionary page in front does not matter by itself, dictionary-encoded
-        data pages do)."""
+        data pages do).  With ``page_kinds = "any"`` dictionary-coded and v2 pages are taken too (``_any_reason``)."""
         table = self.values_pages(g)
         if table["chunk"] is None:
             with open(self._path, "rb") as f:
@@ -387,6 +418,10 @@ class SceneRowGroups:
         if page is None or bool((rows >= table["first_row"][-1]).any()):
             return table, page, "rows beyond the chunk's pages"
         used = np.unique(page)
+        if self.page_kinds != "plain":
+            if self.page_kinds != "any":
+                raise ValueError(f"visindex: page_kinds {self.page_kinds!r}: expected 'plain' or 'any'")
+            return table, page, self._any_reason(table, used)
         if table["codec"] not in self._CODECS:
             reason = f"codec {table['codec']}"
         elif bool((table["type"][used] != self._DATA_PAGE).any()):
@@ -398,6 +433,42 @@ class SceneRowGroups:
         elif int(table["uncompressed"][used].max()) > 0x7fffffff or int(table["compressed"][used].max()) > 0x7fffffff:
             reason = "a page of 2 GiB"
         return table, page, reason
+
+    def _dictionary_page(self, table: dict) -> int:
+        """The chunk's dictionary page (a chunk has at most one, in front of its data pages), or -1."""
+        at = np.nonzero(table["type"] == self._DICTIONARY_PAGE)[0]
+        return int(at[0]) if len(at) else -1
+
+    def _any_reason(self, table: dict, used) -> Optional[str]:
+        """``needed_pages``' verdict with ``page_kinds = "any"``: None when the data pages ``used`` are PLAIN or dictionary-coded
+        (then behind a PLAIN dictionary page), v1 or v2, Snappy or uncompressed, without nulls and repetition levels."""
+        kind, enc = table["type"][used], table["encoding"][used]
+        if table["codec"] not in self._CODECS:
+            return f"codec {table['codec']}"
+        coded = (enc == self._RLE_DICTIONARY) | (enc == self._PLAIN_DICTIONARY)
+        if bool(((enc != self._PLAIN) & ~coded).any()):
+            return f"a data page with encoding {int(enc[(enc != self._PLAIN) & ~coded][0])}"
+        sizes = used
+        if bool(coded.any()):
+            d = self._dictionary_page(table)
+            if d < 0 or d > int(used[coded].min()) or int(table["encoding"][d]) not in (self._PLAIN, self._PLAIN_DICTIONARY):
+                return "dictionary-coded pages without a PLAIN dictionary page in front"
+            sizes = np.append(used, d)
+        v1, v2 = used[kind == self._DATA_PAGE], used[kind == self._DATA_PAGE_V2]
+        if self._has_levels and bool((table["levels"][v1] != self._RLE).any()):
+            return "definition levels that are not RLE"
+        if bool((table["num_nulls"][v2] != 0).any()):
+            return "a v2 page with nulls"
+        if bool((table["rep_bytes"][v2] != 0).any()):
+            return "a v2 page with repetition levels"
+        for k in v2:                       # the level bytes lie uncompressed in front of the values: one run of ones, no length prefix
+            pos, n, nv = int(table["pos"][k]), int(table["def_bytes"][k]), int(table["num_values"][k])
+            want = _uleb128(nv << 1) + b"\x01" if self._has_levels else b""
+            if n > int(table["compressed"][k]) or bytes(table["chunk"][pos:pos + n]) != want:
+                return "a v2 page whose definition levels are not one run of ones"
+        if int(table["uncompressed"][sizes].max()) > 0x7fffffff or int(table["compressed"][sizes].max()) > 0x7fffffff:
+            return "a page of 2 GiB"
+        return None
 
     def _mark(self, stage: str):
         """The stage clock of tools/visindex_decode_bench.py: off unless ``stage_times`` is a dict, then every stage ends with a
@@ -429,20 +500,38 @@ class SceneRowGroups:
 
     def _plan_pages(self, distinct: List[tuple]):
         """``scene_bits`` step 1, on the host alone: the wanted (row group, row), ascending -> (the ``_Page``s that hold them, in
-        that order, None), or (None, why the device path does not take them)."""
-        pages, upload = [], 0
+        that order, None), or (None, why the device path does not take them).  With ``page_kinds = "any"`` the dictionary
+        pages of the dictionary-coded pages follow, once each, behind every data page."""
+        pages, upload, dictionaries = [], 0, {}
         for g in sorted({g for g, _ in distinct}):
             rows = np.array([r for gg, r in distinct if gg == g], dtype=np.int64)
             table, page, reason = self.needed_pages(g, rows)
             if reason is not None:
                 return None, f"row group {g}: {reason}"
             chunk = memoryview(table["chunk"])
+            snappy = self._CODECS[table["codec"]] == 1
             for pg in np.unique(page):
                 pos, comp = int(table["pos"][pg]), int(table["compressed"][pg])
-                pages.append(_Page(g, int(pg), np.frombuffer(chunk[pos:pos + comp], dtype=np.uint8), upload, comp,
-                                   int(table["uncompressed"][pg]), int(table["num_values"][pg]), self._CODECS[table["codec"]] == 1,
-                                   rows[page == pg] - int(table["first_row"][pg])))
-                upload += comp
+                kind = _PLAIN_PAGE if int(table["encoding"][pg]) == self._PLAIN else _DICT_CODED
+                lev = int(table["def_bytes"][pg]) + int(table["rep_bytes"][pg])          # 0 but for v2 pages
+                if kind == _DICT_CODED and g not in dictionaries:
+                    d = self._dictionary_page(table)
+                    at, n = int(table["pos"][d]), int(table["compressed"][d])
+                    dictionaries[g] = _Page(g, d, np.frombuffer(chunk[at:at + n], dtype=np.uint8), 0, n, int(table["uncompressed"][d]),
+                                            int(table["dict_values"][d]), snappy, np.zeros(0, np.int64), _DICTIONARY)
+                pages.append(_Page(g, int(pg), np.frombuffer(chunk[pos + lev:pos + comp], dtype=np.uint8), upload, comp - lev,
+                                   int(table["uncompressed"][pg]) - lev, int(table["num_values"][pg]),
+                                   snappy and bool(table["is_compressed"][pg]), rows[page == pg] - int(table["first_row"][pg]), kind,
+                                   g if kind == _DICT_CODED else -1, int(table["type"][pg]) == self._DATA_PAGE_V2))
+                upload += comp - lev
+        # the dictionary pages stand behind every data page, so that the data pages keep their places in the tables
+        n_data = len(pages)
+        for g, d in dictionaries.items():
+            pages[:n_data] = [p._replace(dictionary=len(pages)) if p.kind == _DICT_CODED and p.group == g else p for p in pages[:n_data]]
+            pages.append(d._replace(src=upload))
+            upload += d.compressed
+        if self._has_levels and len({p.v2 for p in pages[:n_data]}) == 2:
+            return None, "v1 pages with levels and v2 pages in one scene"
         if sum(p.uncompressed for p in pages) > 0x7fffffff:
             return None, "2 GiB of pages or more"
         return pages, None
@@ -482,6 +571,48 @@ class SceneRowGroups:
             at += p.uncompressed
         return payloads, status, route
 
+    def _mixed_rows_to_bits(self, payloads, pages: List[_Page], tab, n_points, has_levels: bool, device):
+        """``scene_bits`` step 4 for a plan with dictionary-coded pages: the dictionary pages' entries -> a span table
+        (``engine.parquet_plain_spans_device`` without levels, every entry a row); the dictionary-coded pages' rows -> spans
+        through it (``engine.parquet_dict_spans_device``); the PLAIN pages' rows -> spans as ever; both merged into the one
+        row-ordered span table ``engine.index_spans_to_bits`` takes.  Returns its dict; ``page_status`` holds every call's pages."""
+        import torch
+        from . import engine
+
+        def tables(kind, rows_of):
+            """(which pages, device tensors: payload offsets, sizes, values, row_begin, row_index) of the pages of ``kind``."""
+            which = [k for k, p in enumerate(pages) if p.kind == kind]
+            rows = [rows_of(pages[k]) for k in which]
+            row_begin = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+            row_index = np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64)
+            host = [tab[_PAYLOAD, which], tab[_UNCOMPRESSED, which], tab[_VALUES, which], row_begin, row_index]
+            return which, [torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device) for a in host]
+
+        def slots(which):                                              # the rows of these pages in the scene's row table
+            return torch.from_numpy(np.concatenate([np.arange(tab[_ROW_BEGIN, k], tab[_ROW_BEGIN, k + 1]) for k in which]).astype(np.int64)).to(device)
+
+        n_rows = int(tab[_ROW_BEGIN, -1])
+        start, length = (torch.zeros((n_rows,), dtype=torch.int64, device=device) for _ in range(2))
+        status = []
+        dictionaries, t = tables(_DICTIONARY, lambda p: np.arange(p.num_values))
+        dict_start, dict_length, st = engine.parquet_plain_spans_device(payloads, *t, has_levels=False)
+        status.append(st)
+        dict_begin = dict(zip(dictionaries, np.concatenate([[0], np.cumsum(tab[_VALUES, dictionaries])])[:-1]))
+        coded, t = tables(_DICT_CODED, lambda p: p.rows)
+        begin = torch.tensor([int(dict_begin[pages[k].dictionary]) for k in coded], dtype=torch.int64, device=device)
+        count = torch.tensor([pages[pages[k].dictionary].num_values for k in coded], dtype=torch.int64, device=device)
+        _, a, n, st, _code = engine.parquet_dict_spans_device(payloads, *t, begin, count, dict_start, dict_length, has_levels=has_levels)
+        at = slots(coded)
+        start[at], length[at] = a, n
+        status.append(st)
+        plain, t = tables(_PLAIN_PAGE, lambda p: p.rows)
+        if plain:
+            a, n, st = engine.parquet_plain_spans_device(payloads, *t, has_levels=has_levels)
+            at = slots(plain)
+            start[at], length[at] = a, n
+            status.append(st)
+        return engine.index_spans_to_bits(payloads, start, length, n_points, torch.cat(status))
+
     def _repair_rows(self, got: dict, payloads, n_points):
         """``scene_bits`` step 5: the rows the device declined get their text back from the device's pages and take the host path --
         ``json.loads``, ``pack_index_lists`` -- into ``got["bits"]`` (widened where ``n_points`` is None and they say so)."""
@@ -518,7 +649,10 @@ class SceneRowGroups:
         kernel for a page that is not cut that way), finds the rows, parses the lists and sets the bits
         (``engine.index_rows_to_bits``).  Whatever the device path does not take -- a page that is not v1 / PLAIN / Snappy or
         uncompressed, a stream or a page it declines, a row that is not an ascending list inside ``n_points`` -- goes through
-        ``json.loads`` and ``pack_index_lists``, so the result is the host path's for every input.  ``decode_stats`` counts scenes,
+        ``json.loads`` and ``pack_index_lists``, so the result is the host path's for every input.  With ``page_kinds = "any"``
+        dictionary-coded data pages (their dictionary page uploaded and decompressed with them, the rows' indices walked by
+        ``engine.parquet_dict_spans_device``) and v2 data pages (level bytes checked here, the values part uploaded) are
+        taken as well; ``decode_stats["dict_pages"]`` / ``["v2_pages"]`` count them.  ``decode_stats`` counts scenes,
         declined scenes, rows, declined rows, uploaded bytes, ``blocks`` (64 KiB blocks decoded in parallel) and ``serial_streams``
         (Snappy pages the one-wave kernel took); ``last_decline`` says why the last scene was declined."""
         import torch
@@ -567,9 +701,15 @@ class SceneRowGroups:
             return host("an uncompressed page whose sizes differ")
         payloads, stream_status, route = self._decompress_pages(src, pages, tab_dev)
         self._mark("decompress")
-        got = engine.index_rows_to_bits(payloads, tab_dev[_PAYLOAD, :n_pages].contiguous(), tab_dev[_UNCOMPRESSED, :n_pages].contiguous(),
-                                        tab_dev[_VALUES, :n_pages].contiguous(), tab_dev[_ROW_BEGIN].contiguous(),
-                                        torch.from_numpy(row_index).to(device), n_points=n_points, has_levels=self._has_levels)
+        # the data pages open the tables (``_plan_pages``); dictionary pages, if any, stand behind them and hold no row
+        n_data = sum(1 for p in pages if p.kind != _DICTIONARY)
+        has_levels = self._has_levels and not any(p.v2 for p in pages)      # a v2 page's levels stayed on the host, checked
+        if all(p.kind == _PLAIN_PAGE for p in pages):
+            got = engine.index_rows_to_bits(payloads, tab_dev[_PAYLOAD, :n_data].contiguous(), tab_dev[_UNCOMPRESSED, :n_data].contiguous(),
+                                            tab_dev[_VALUES, :n_data].contiguous(), tab_dev[_ROW_BEGIN, :n_data + 1].contiguous(),
+                                            torch.from_numpy(row_index).to(device), n_points=n_points, has_levels=has_levels)
+        else:
+            got = self._mixed_rows_to_bits(payloads, pages, tab, n_points, has_levels, device)
         if (stream_status is not None and bool((stream_status != 0).any().item())) or bool(got["page_status"].any()):
             return host("the device declined a page")
         self._mark("rows_to_bits")
@@ -578,6 +718,8 @@ class SceneRowGroups:
             self.decode_stats["blocks"] += int(routes.sum())
             self.decode_stats["serial_streams"] += int((routes == 0).sum())
         self.decode_stats["rows"] += len(distinct)
+        self.decode_stats["dict_pages"] += sum(1 for p in pages if p.kind == _DICT_CODED)
+        self.decode_stats["v2_pages"] += sum(1 for p in pages if p.v2)
         bits = self._repair_rows(got, payloads, n_points)
         slot = {gr: k for k, gr in enumerate(distinct)}
         order = torch.tensor([slot[found[k]] for k in present_pos], dtype=torch.int64, device=bits.device)

@@ -116,6 +116,8 @@ def process_split(split_name, scene_info_path, visibility_parquet_file, output_d
     print(f"Loading visibility dict from {visibility_parquet_file}.")
     index = visindex.SceneRowGroups(visibility_parquet_file)
     on_device = visindex.decode_mode() == "device"           # MSPA_VISINDEX_DECODE; a value that is neither raises here
+    if on_device:
+        index.page_kinds = "any"                              # dictionary-coded and v2 pages too: whoever wrote the file
     costs = [float(max(1, handler.get_num_objects(s)) * max(1, len(handler.get_all_extrinsic_valid_image_ids(s)))) for s in scene_ids]
     results, lines = {}, []
 

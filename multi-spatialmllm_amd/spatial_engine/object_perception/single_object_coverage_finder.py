@@ -137,6 +137,8 @@ def _load_inputs(scene_info_path, visibility_parquet_file, object_visibility_fil
     # MSPA_VISINDEX_DECODE=device: no dict of the whole file -- every scene's rows go from its pages to the GPU (scene_bits)
     index = (visindex.SceneRowGroups(visibility_parquet_file) if visindex.decode_mode() == "device"
              else load_visibility_dict(visibility_parquet_file))
+    if isinstance(index, visindex.SceneRowGroups):
+        index.page_kinds = "any"                              # dictionary-coded and v2 pages too: whoever wrote the file
     return SceneInfoHandler(scene_info_path), index, _load_any(object_visibility_file)
 
 

@@ -16,7 +16,14 @@ path's stages (each ended by a device synchronise, so their sum exceeds the unsp
 for every page (``SceneRowGroups.decode_by_blocks = False``: the paths named ``device_one_wave``) -- both in this process, beside
 the host path.  Then the decode calls alone, between two events on the stream: one scene's pages in one call, and 8 scenes' pages
 in one call, by either route.  Prints one JSON line.  Kernel-by-kernel times (scan, block decode and last pass apart) come from
-a separate ``rocprofv3 --kernel-trace --stats`` run of this tool with ``--device-only --route blocks``."""
+a separate ``rocprofv3 --kernel-trace --stats`` run of this tool with ``--device-only --route blocks``.
+
+``--layout pandas``: the same scenes as ONE table written the reference's way, ``DataFrame.to_parquet(path, index=False)`` --
+pyarrow's defaults: dictionary encoding on, row groups of 1 Mi rows that mix scenes, a dictionary page and one RLE_DICTIONARY
+page in front of the PLAIN pages of every row group.  The device path then runs with ``page_kinds = "plain"`` (dictionary-coded
+pages decline the scene to the host path: the paths named ``device_plain``) and with ``"any"`` (``device_any``); every path
+reports its declined scenes, and each scene's wall of the last pass is listed (``scene_ms_last_pass``) beside the pages it
+needed.  The host path of such a file reads a whole row group for its first scene and keeps it (``scene_dict``)."""
 import argparse
 import json
 import os
@@ -38,6 +45,16 @@ def write_index(path, bits, ids, points, scenes, layout):
     return os.path.getsize(path)
 
 
+def write_pandas_index(path, bits, ids, points, scenes):
+    """All scenes as one DataFrame -> ``to_parquet(index=False)``, as make_visibility_info.py:71 does."""
+    import pyarrow as pa
+    from mspa import visindex
+    csr = visindex.from_bits(bits, ids, points, text=True, indices=False)
+    df = pa.concat_tables([csr.to_arrow(f"scene{k:04d}_00") for k in range(scenes)]).to_pandas()
+    df.to_parquet(path, index=False)
+    return os.path.getsize(path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=320)
@@ -46,7 +63,7 @@ def main():
     ap.add_argument("--passes", type=int, default=6, help="passes per path; the first is the warm-up")
     ap.add_argument("--host-scenes", type=int, default=4, help="scenes of a host-path pass")
     ap.add_argument("--visible", type=float, default=0.12)
-    ap.add_argument("--layout", choices=("host", "device"), default="host")
+    ap.add_argument("--layout", choices=("host", "device", "pandas"), default="host")
     ap.add_argument("--device-only", action="store_true", help="skip the host path and the kernel-alone timings (for a profiler run)")
     ap.add_argument("--route", choices=("both", "blocks", "one-wave"), default="both",
                     help="the device path's Snappy decode: one wave per 64 KiB block, the one-wave kernel for every page, or both in turn")
@@ -60,26 +77,33 @@ def main():
     scene_ids = [f"scene{k:04d}_00" for k in range(a.scenes)]
     tmp = tempfile.mkdtemp(prefix="visindex_decode_bench_")
     path = os.path.join(tmp, "vis.parquet")
-    file_bytes = write_index(path, bits, ids, a.points, a.scenes, a.layout)
+    file_bytes = (write_pandas_index(path, bits, ids, a.points, a.scenes) if a.layout == "pandas"
+                  else write_index(path, bits, ids, a.points, a.scenes, a.layout))
     print(f"index written: {file_bytes} bytes", file=sys.stderr, flush=True)
     out = {"frames": a.frames, "vertices": a.points, "visible_fraction": round(density, 4), "scenes": a.scenes, "layout": a.layout,
            "file_bytes": file_bytes, "warm_passes": a.passes - 1, "statistic": "median of the warm passes, per scene", "paths": {}}
     want = bits.cpu().numpy()
 
-    def run(path_name, scenes, stages, by_blocks=True):
+    def run(path_name, scenes, stages, by_blocks=True, page_kinds="plain"):
         wall, cpu, h2d, st_all = [], [], [], []
         for _ in range(a.passes):
             index = visindex.SceneRowGroups(path)
             index.decode_by_blocks = by_blocks
+            index.page_kinds = page_kinds
+            each = []
             if stages:
                 index.stage_times = {}
             torch.cuda.synchronize()
             c0, t0 = time.process_time(), time.perf_counter()
             for s in scenes:
+                t1 = time.perf_counter()
                 if path_name == "host":
                     present, got = index._scene_bits_host(s, ids, a.points, "cuda")
                 else:
                     present, got = index.scene_bits(s, ids, a.points)
+                if a.layout == "pandas":
+                    torch.cuda.synchronize()
+                    each.append(round(1e3 * (time.perf_counter() - t1), 2))
             torch.cuda.synchronize()
             wall.append((time.perf_counter() - t0) / len(scenes))
             cpu.append((time.process_time() - c0) / len(scenes))
@@ -87,7 +111,8 @@ def main():
             st_all.append({k: round(1e3 * v / len(scenes), 3) for k, v in (index.stage_times or {}).items()})
             assert present == ids and np.array_equal(got.cpu().numpy(), want)
             print(f"{path_name}{' staged' if stages else ''}: pass of {len(scenes)} scenes, {1e3 * wall[-1]:.1f} ms per scene", file=sys.stderr, flush=True)
-            assert path_name == "host" or (index.decode_stats["scenes_declined"] == 0 and index.decode_stats["rows_declined"] == 0)
+            assert path_name == "host" or index.decode_stats["rows_declined"] == 0
+            assert path_name == "host" or a.layout == "pandas" or index.decode_stats["scenes_declined"] == 0
         res = {"scenes_per_pass": len(scenes), "wall_ms": round(1e3 * statistics.median(wall[1:]), 2),
                "process_cpu_ms": round(1e3 * statistics.median(cpu[1:]), 2), "wall_ms_all": [round(1e3 * v, 2) for v in wall],
                "process_cpu_ms_all": [round(1e3 * v, 2) for v in cpu]}
@@ -95,6 +120,10 @@ def main():
             res["h2d_bytes"] = int(statistics.median(h2d[1:]))
             res["blocks_per_scene"] = index.decode_stats["blocks"] // len(scenes)
             res["serial_streams_per_scene"] = index.decode_stats["serial_streams"] // len(scenes)
+            res["scenes_declined"] = index.decode_stats["scenes_declined"]
+            res["dict_pages"], res["v2_pages"] = index.decode_stats["dict_pages"], index.decode_stats["v2_pages"]
+        if a.layout == "pandas":
+            res["scene_ms_last_pass"] = each
         if stages:
             res["stages_ms"] = {k: round(statistics.median([p[k] for p in st_all[1:]]), 3) for k in st_all[-1]}
             res["stages_ms_all"] = st_all
@@ -102,6 +131,20 @@ def main():
 
     if not a.device_only:
         out["paths"]["host"] = run("host", scene_ids[:a.host_scenes], False)
+    if a.layout == "pandas":
+        index = visindex.SceneRowGroups(path)
+        index.page_kinds = "any"
+        out["row_groups"] = index.file.metadata.num_row_groups
+        out["scene_pages"] = []                    # per scene: (kind, compressed, uncompressed, values) of the pages it needs
+        for s in scene_ids:
+            pages, why = index._plan_pages(sorted(set(index.image_rows(s, ids).values())))
+            out["scene_pages"].append(why or [(p.kind, p.compressed, p.uncompressed, p.num_values) for p in pages])
+        if not a.device_only:
+            out["paths"]["device_plain"] = run("device", scene_ids, False)
+        out["paths"]["device_any"] = run("device", scene_ids, False, page_kinds="any")
+        out["paths"]["device_any_staged"] = run("device", scene_ids, True, page_kinds="any")
+        print(json.dumps(out))
+        return
     if a.route != "one-wave":
         out["paths"]["device"] = run("device", scene_ids, False)
         out["paths"]["device_staged"] = run("device", scene_ids, True)
