@@ -717,6 +717,12 @@ int mspa_parquet_string_pages_device(const int32_t *text_offsets_dev, int64_t ro
  *   out_bits_dev [n_rows, n_words] uint64, bit i of word w = vertex 64 w + i (scene.pack_index_lists' layout), rows zeroed
  *   first; n_points <= 64 n_words.  Lists ascend: a value below its predecessor raises 32 in row_status_dev[r] (cleared by the
  *   call), a value outside [0, n_points) 64 -- such a row's bits are unspecified; a duplicate is harmless, an empty list a zero row.
+ * mspa_index_lists_pick_device  the same values_dev / offsets_dev read as LISTS (duplicates count, the order is the text's):
+ *   samples_dev [n_samples, 2] int64 (row, position) -> out_vertex_dev[s] (int32) = values[offsets[row] + position] and
+ *   out_status_dev[s] (int32) = 0; otherwise out_vertex_dev[s] = -1 and the status says why: 1 the row lies outside
+ *   [0, n_rows), 2 the position outside [0, offsets[row + 1] - offsets[row]), 4 the value outside [0, n_points), 8 offsets[row]
+ *   or offsets[row + 1] outside [0, n_values] or descending.  n_points < 2^31; n_samples = 0 enqueues nothing.  A vertex with a
+ *   non-zero status must not reach mspa_project_samples_ex, which indexes xyz with what it is given.
  * All device calls only enqueue on `stream`; a wrong argument (a null pointer included) returns MSPA_EINVAL before anything is
  * enqueued; no kernel uses atomics.
  */
@@ -753,6 +759,9 @@ int mspa_index_rows_gather_device(const uint8_t *pages_dev, int64_t pages_bytes,
                                   const int64_t *inner_prefix_dev, int64_t n_rows, uint8_t *out_text_dev, int64_t text_bytes, void *stream);
 int mspa_index_lists_to_bits_device(const int32_t *values_dev, int64_t n_values, const int64_t *offsets_dev, int64_t n_rows,
                                     int64_t n_points, uint64_t *out_bits_dev, int64_t n_words, int32_t *row_status_dev, void *stream);
+int mspa_index_lists_pick_device(const int32_t *values_dev, int64_t n_values, const int64_t *offsets_dev, int64_t n_rows,
+                                 const int64_t *samples_dev, int64_t n_samples, int64_t n_points, int32_t *out_vertex_dev,
+                                 int32_t *out_status_dev, void *stream);
 
 /*
  * Image resizing ON THE DEVICE (csrc/resize.hip, arithmetic in csrc/resize_core.h): n 8-bit RGB images of one shape resampled

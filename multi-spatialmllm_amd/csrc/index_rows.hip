@@ -15,6 +15,8 @@
 //                the lane whose predecessor lies in another word (or that opens the row) ORs the run and stores the word with a
 //                plain store into the zeroed row.  A value below its predecessor or outside [0, n_points) declines the row
 //                (plain stores of a constant: lanes that race write the same thing); a duplicate is harmless.
+//   pick         one lane per sample (row, position): element `position` of the row's parsed list, for the readers that use a
+//                row as a LIST (len, list[j]: duplicates count, order is the text's) -- they stop in front of lists->bits.
 // No atomics; every load and store is checked against the buffer it goes to.
 #include "mspa_common.h"
 #include "snappy_core.h"
@@ -30,6 +32,11 @@ constexpr int32_t kPageIndex = 4;        // dictionary-coded pages: an index >= 
 constexpr int32_t kRowBrackets = 1;      // a row's text is not [ ... ]
 constexpr int32_t kRowOrder = 32;        // lists->bits: a value below its predecessor     (K11's parser owns bits 2 .. 16)
 constexpr int32_t kRowRange = 64;        // lists->bits: a value outside [0, n_points)
+constexpr int32_t kPickRow = 1;          // pick: the sample's row lies outside [0, n_rows)
+constexpr int32_t kPickPosition = 2;     // pick: its position lies outside the row's list
+constexpr int32_t kPickRange = 4;        // pick: the element lies outside [0, n_points)
+constexpr int32_t kPickOffsets = 8;      // pick: the row's offsets descend or leave [0, n_values]
+constexpr int kPickBlock = 256;
 
 __device__ __forceinline__ bool json_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
 
@@ -208,6 +215,36 @@ __global__ __launch_bounds__(256) void lists_to_bits_kernel(const int32_t *__res
     bits[lo * n_words + (v >> 6)] = w;                           // v < n_points <= 64 n_words
 }
 
+// One lane per sample (row, position): the row's list read as a list -- element `position` of it, duplicates and order as the
+// text has them.  A sample that names no element, or an element that is no vertex of the scene, gives -1 and says why.
+__global__ __launch_bounds__(kPickBlock) void list_pick_kernel(const int32_t *__restrict__ values, int64_t n_values,
+                                                               const int64_t *__restrict__ offsets, int64_t n_rows,
+                                                               const int64_t *__restrict__ samples, int64_t n_samples, int64_t n_points,
+                                                               int32_t *__restrict__ out_vertex, int32_t *__restrict__ out_status) {
+    const int64_t s = (int64_t)blockIdx.x * kPickBlock + threadIdx.x;
+    if (s >= n_samples) return;
+    const int64_t row = samples[2 * s], position = samples[2 * s + 1];
+    int32_t vertex = -1, status = 0;
+    if (row < 0 || row >= n_rows) {
+        status = kPickRow;
+    } else {
+        const int64_t first = offsets[row], end = offsets[row + 1];
+        if (first < 0 || end < first || end > n_values) {
+            status = kPickOffsets;
+        } else if (position < 0 || position >= end - first) {
+            status = kPickPosition;
+        } else {
+            const int32_t v = values[first + position];          // 0 <= first + position < end <= n_values
+            if (v < 0 || v >= n_points)
+                status = kPickRange;
+            else
+                vertex = v;
+        }
+    }
+    out_vertex[s] = vertex;
+    out_status[s] = status;
+}
+
 }  // namespace index_rows
 }  // namespace mspa
 
@@ -300,4 +337,19 @@ extern "C" int mspa_index_lists_to_bits_device(const int32_t *values_dev, int64_
         hipLaunchKernelGGL(index_rows::lists_to_bits_kernel, dim3((unsigned)((n_values + 255) / 256)), dim3(256), 0, st, values_dev, n_values, offsets_dev,
                            n_rows, n_points, out_bits_dev, n_words, row_status_dev);
     return check_hip(hipGetLastError(), "mspa_index_lists_to_bits_device");
+}
+
+extern "C" int mspa_index_lists_pick_device(const int32_t *values_dev, int64_t n_values, const int64_t *offsets_dev, int64_t n_rows,
+                                            const int64_t *samples_dev, int64_t n_samples, int64_t n_points, int32_t *out_vertex_dev,
+                                            int32_t *out_status_dev, void *stream) {
+    if (n_values < 0 || n_rows < 0 || n_samples < 0 || n_points < 0 || n_points > 0x7fffffffLL ||
+        n_samples > (int64_t)0x7fffffff * index_rows::kPickBlock)
+        return fail(MSPA_EINVAL, "mspa_index_lists_pick_device: bad size (0 <= n_points < 2^31)");
+    if (n_samples == 0) return MSPA_OK;
+    if (!samples_dev || !out_vertex_dev || !out_status_dev || (n_rows > 0 && !offsets_dev) || (n_values > 0 && !values_dev))
+        return fail(MSPA_EINVAL, "mspa_index_lists_pick_device: null pointer");
+    hipLaunchKernelGGL(index_rows::list_pick_kernel, dim3((unsigned)((n_samples + index_rows::kPickBlock - 1) / index_rows::kPickBlock)),
+                       dim3(index_rows::kPickBlock), 0, (hipStream_t)stream, values_dev, n_values, offsets_dev, n_rows, samples_dev, n_samples,
+                       n_points, out_vertex_dev, out_status_dev);
+    return check_hip(hipGetLastError(), "mspa_index_lists_pick_device");
 }

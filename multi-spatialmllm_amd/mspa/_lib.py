@@ -26,6 +26,9 @@ SNAPPY_NOT_BLOCKWISE = -22     # mspa_snappy_block_starts_host alone: a valid st
 SNAPPY_SEGMENT = 2048          # csrc/snappy_decode.hip: kSeg, the compressed bytes one wave of the block-start scan takes
 # csrc/rle_hybrid_core.h: what mspa_rle_hybrid_take_host returns for, and mspa_parquet_dict_spans_device writes as the code of, runs it declines
 RLE_EBITWIDTH, RLE_EHEADER, RLE_EZERORUN, RLE_ETRUNCATED, RLE_ESHORT = -32, -33, -34, -35, -36
+# mspa_index_lists_pick_device's per-sample status (csrc/index_rows.hip: kPick*) and the samples one workgroup takes
+PICK_OK, PICK_EROW, PICK_EPOSITION, PICK_ERANGE, PICK_EOFFSETS = 0, 1, 2, 4, 8
+PICK_BLOCK = 256
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
@@ -173,6 +176,7 @@ _SIGNATURES = {
     "mspa_index_rows_brackets_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mspa_index_rows_gather_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "mspa_index_lists_to_bits_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mspa_index_lists_pick_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "mspa_track_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                         c_double, c_double, c_void_p, c_void_p, c_void_p]),
 }

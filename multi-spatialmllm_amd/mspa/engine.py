@@ -1112,27 +1112,24 @@ def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_siz
     return index_spans_to_bits(pages, start, length, n_points, page_status)
 
 
-def index_spans_to_bits(pages: torch.Tensor, start: torch.Tensor, length: torch.Tensor, n_points: Optional[int] = None,
-                        page_status: Optional[torch.Tensor] = None):
-    """``index_rows_to_bits`` behind the span kernels: row r's text is ``pages[start[r] : start[r] + length[r]]`` (int64, on the
-    device -- from ``parquet_plain_spans_device``, ``parquet_dict_spans_device`` or both merged) -> the same dict;
-    ``page_status`` (int32, device) rides along in the read-back of the rows' status."""
+def _spans_to_lists(pages: torch.Tensor, start: torch.Tensor, length: torch.Tensor, page_status: Optional[torch.Tensor]):
+    """THE pipeline from row spans to parsed lists, enqueued once for ``index_spans_to_lists`` and ``index_spans_to_bits``:
+    brackets -> (prefix sum) -> gather -> flags -> (prefix sum) -> parse.  Returns (values int32 [max(count, 1)], count,
+    offsets int64 [rows + 1], status int32 [2, max(rows, 1)] -- brackets, parser --, page_status, n_pages), all tensors on the
+    device; for no rows ``values`` and ``offsets`` are None.  Two read-backs (the text's and the values' totals)."""
     lib = _lib.load()
     _check("pages", pages, torch.uint8, (None,))
     n_rows = _check("start", start, torch.int64, (None,)).shape[0]
     _check("length", length, torch.int64, (n_rows,))
-    _require(n_points is None or 0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
     if page_status is None:
         page_status = torch.zeros((0,), dtype=torch.int32, device=pages.device)
     n_pages = _check("page_status", page_status, torch.int32, (None,)).shape[0]
     dev, st = pages.device, _stream_ptr()
     i64 = dict(dtype=torch.int64, device=dev)
-    inner_start, inner_len = torch.empty((n_rows,), **i64), torch.empty((n_rows,), **i64)
-    status = torch.zeros((3, max(n_rows, 1)), dtype=torch.int32, device=dev)                 # brackets, parser, bits
+    status = torch.zeros((2, max(n_rows, 1)), dtype=torch.int32, device=dev)                 # brackets, parser
     if n_rows == 0:
-        n_points = int(n_points or 1)
-        return {"bits": torch.zeros((0, (n_points + 63) // 64), **i64), "n_points": n_points, "page_status": np.zeros(n_pages, np.int32),
-                "row_status": np.zeros(0, np.int32), "start": start, "length": length}
+        return None, 0, None, status, page_status, n_pages
+    inner_start, inner_len = torch.empty((n_rows,), **i64), torch.empty((n_rows,), **i64)
     pages_ptr = _ptr(pages) if pages.numel() else None
     _lib.check(lib.mspa_index_rows_brackets_device(pages_ptr, pages.numel(), _ptr(start), _ptr(length), n_rows, _ptr(inner_start),
                                                    _ptr(inner_len), _ptr(status[0]), st))
@@ -1153,15 +1150,81 @@ def index_spans_to_bits(pages: torch.Tensor, start: torch.Tensor, length: torch.
     offsets = torch.empty((n_rows + 1,), **i64)
     _lib.check(lib.mspa_parse_int_list_device(_ptr(text), _ptr(prefix), n_rows, n_bytes, _ptr(T), None, _ptr(values), count, _ptr(offsets),
                                               _ptr(status[1]), st))
-    del T
+    return values, count, offsets, status, page_status, n_pages
+
+
+def index_spans_to_lists(pages: torch.Tensor, start: torch.Tensor, length: torch.Tensor, page_status: Optional[torch.Tensor] = None):
+    """``index_spans_to_bits`` one step short: the rows as LISTS, for the readers that take ``len(row)`` and ``row[j]`` (a
+    duplicate counts, the order is the text's -- neither survives a bitset).  Row r's text is ``pages[start[r] : start[r] +
+    length[r]]``.  Returns a dict: ``values`` int32 [n] and ``offsets`` int64 [rows + 1] on the device (CSR: row r is
+    ``values[offsets[r] : offsets[r + 1]]`` -- what ``index_lists_pick`` takes), ``counts`` (int64 numpy, ``diff(offsets)``),
+    ``row_status`` (int32 numpy: brackets | parser; a declined row has count 0 and belongs to the host path), ``page_status``
+    (int32 numpy), ``n_points`` (1 + the largest parsed value: the width ``index_spans_to_bits`` takes for ``n_points=None``),
+    ``start`` / ``length``.  Synchronises: the pipeline's two totals and ONE read-back of statuses, counts and width."""
+    values, count, offsets, status, page_status, n_pages = _spans_to_lists(pages, start, length, page_status)
+    n_rows = start.shape[0]
+    if n_rows == 0:
+        dev = pages.device
+        return {"values": torch.zeros((0,), dtype=torch.int32, device=dev), "offsets": torch.zeros((1,), dtype=torch.int64, device=dev),
+                "counts": np.zeros(0, np.int64), "row_status": np.zeros(0, np.int32), "page_status": np.zeros(n_pages, np.int32), "n_points": 1,
+                "start": start, "length": length}
+    values = values[:count]
+    top = values.max().to(torch.int64).reshape(1) if count else torch.zeros((1,), dtype=torch.int64, device=pages.device)
+    back = torch.cat([page_status.to(torch.int64), (status[0] | status[1])[:n_rows].to(torch.int64), offsets[1:] - offsets[:-1], top]).cpu().numpy()
+    return {"values": values, "offsets": offsets, "counts": back[n_pages + n_rows:-1].copy(),
+            "row_status": back[n_pages:n_pages + n_rows].astype(np.int32), "page_status": back[:n_pages].astype(np.int32),
+            "n_points": int(back[-1]) + 1, "start": start, "length": length}
+
+
+def index_rows_to_lists(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
+                        row_begin: torch.Tensor, row_index: torch.Tensor, has_levels: bool = True):
+    """``index_rows_to_bits`` for the readers of lists: the same pages and tables -> ``index_spans_to_lists``' dict."""
+    start, length, page_status = parquet_plain_spans_device(pages, page_offsets, page_sizes, page_values, row_begin, row_index, has_levels)
+    return index_spans_to_lists(pages, start, length, page_status)
+
+
+def index_lists_pick(values: torch.Tensor, offsets: torch.Tensor, samples: torch.Tensor, n_points: int):
+    """Element ``position`` of row ``row`` for every sample (mspa_index_lists_pick_device): ``values`` int32 [n] / ``offsets``
+    int64 [rows + 1] as ``index_spans_to_lists`` leaves them, ``samples`` int64 [n_samples, 2] (row, position), all on the device
+    -> (vertex int32 [n_samples], status int32 [n_samples]) on the device.  Status 0: ``vertex = values[offsets[row] +
+    position]``; otherwise vertex -1 and ``_lib.PICK_EROW`` (1, no such row), ``PICK_EPOSITION`` (2, outside the list),
+    ``PICK_ERANGE`` (4, the value is outside [0, n_points)) or ``PICK_EOFFSETS`` (8, the row's offsets leave ``values``).  Only
+    enqueues: the caller reads ``status`` before a vertex goes anywhere that indexes with it (``project_samples``)."""
+    n_values = _check("values", values, torch.int32, (None,)).shape[0]
+    n_rows = _check("offsets", offsets, torch.int64, ((1,),)).shape[0] - 1
+    n = _check("samples", samples, torch.int64, (None, 2)).shape[0]
+    _require(0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
+    vertex = torch.empty((n,), dtype=torch.int32, device=values.device)
+    status = torch.empty((n,), dtype=torch.int32, device=values.device)
+    if n:
+        _lib.check(_lib.load().mspa_index_lists_pick_device(_ptr(values) if n_values else None, n_values, _ptr(offsets), n_rows, _ptr(samples), n,
+                                                            int(n_points), _ptr(vertex), _ptr(status), _stream_ptr()))
+    return vertex, status
+
+
+def index_spans_to_bits(pages: torch.Tensor, start: torch.Tensor, length: torch.Tensor, n_points: Optional[int] = None,
+                        page_status: Optional[torch.Tensor] = None):
+    """``index_rows_to_bits`` behind the span kernels: row r's text is ``pages[start[r] : start[r] + length[r]]`` (int64, on the
+    device -- from ``parquet_plain_spans_device``, ``parquet_dict_spans_device`` or both merged) -> the same dict;
+    ``page_status`` (int32, device) rides along in the read-back of the rows' status.  The lists come from the pipeline
+    ``index_spans_to_lists`` runs; mspa_index_lists_to_bits_device follows."""
+    _require(n_points is None or 0 <= int(n_points) <= 0x7fffffff, "n_points: 0 <= n_points < 2^31")
+    values, count, offsets, status, page_status, n_pages = _spans_to_lists(pages, start, length, page_status)
+    n_rows = start.shape[0]
+    i64 = dict(dtype=torch.int64, device=pages.device)
+    if n_rows == 0:
+        n_points = int(n_points or 1)
+        return {"bits": torch.zeros((0, (n_points + 63) // 64), **i64), "n_points": n_points, "page_status": np.zeros(n_pages, np.int32),
+                "row_status": np.zeros(0, np.int32), "start": start, "length": length}
     if n_points is None:
         n_points = (int(values[:count].max().item()) if count else 0) + 1
     n_points = int(n_points)
     n_words = (n_points + 63) // 64
     bits = torch.empty((n_rows, n_words), **i64)
-    _lib.check(lib.mspa_index_lists_to_bits_device(_ptr(values), count, _ptr(offsets), n_rows, n_points, _ptr(bits) if n_words else None, n_words,
-                                                   _ptr(status[2]), st))
-    row_status = (status[0] | status[1] | status[2])[:n_rows]
+    bits_status = torch.zeros((n_rows,), dtype=torch.int32, device=pages.device)
+    _lib.check(_lib.load().mspa_index_lists_to_bits_device(_ptr(values), count, _ptr(offsets), n_rows, n_points, _ptr(bits) if n_words else None,
+                                                           n_words, _ptr(bits_status), _stream_ptr()))
+    row_status = (status[0] | status[1])[:n_rows] | bits_status
     back = torch.cat([page_status, row_status]).cpu().numpy()
     return {"bits": bits, "n_points": n_points, "page_status": back[:n_pages], "row_status": back[n_pages:], "start": start, "length": length}
 

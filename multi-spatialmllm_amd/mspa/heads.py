@@ -950,6 +950,27 @@ def list_point_numerics(scene, visible_points):
     return fn
 
 
+def index_point_numerics(scene, lists):
+    """``list_point_numerics`` over a scene's ``visindex.IndexLists``: the drawn (image, position) samples are resolved by
+    ``lists.pick`` -- on the device, checked: a position outside its list or a vertex outside the scene's raises there, before
+    K6b indexes ``xyz`` with it -- and stay on the device for the projection; one download."""
+    import torch
+    from . import engine
+
+    def fn(samples):
+        if not samples:
+            return []
+        vert = lists.pick(samples, scene.xyz.shape[0]).to(scene.device)
+        image = torch.tensor([scene.index[i] for i, _ in samples], dtype=torch.int32, device=scene.device)
+        uv, d, ok = engine.project_samples(scene.xyz, scene.cam_mats, scene.depth, scene.image_hw, torch.stack([vert, image], dim=1),
+                                           scene.depth_scale)
+        # one download: an int32 vertex and a 0 / 1 flag are exact in float64
+        back = torch.cat([uv, d[:, None], ok[:, None].to(torch.float64), vert[:, None].to(torch.float64)], dim=1).cpu().numpy()
+        uv = np.ascontiguousarray(back[:, :2])
+        return [(int(back[s, 4]), uv[s] if back[s, 3] else None, float(back[s, 2])) for s in range(len(samples))]
+    return fn
+
+
 def depth_comparison_records_gpu(scene, scene_id: str, image_hw, max_samples: int = -1, templates: T.TemplateSet = None,
                                  rng=_random, on_skip=None) -> List[dict]:
     counts = scene._visibility()["count"].cpu().numpy()

@@ -34,7 +34,8 @@ def decode_mode() -> str:
     """Who turns the index's ``image_to_points`` rows back into bitsets: "host" (the default: pyarrow reads the row group,
     ``json.loads`` and ``scene.pack_index_lists`` on the CPU) or "device" (``MSPA_VISINDEX_DECODE=device``:
     ``SceneRowGroups.scene_bits`` uploads the needed pages as they lie in the file and decompresses, parses and packs them on
-    the GPU).  Read at every call."""
+    the GPU; the depth builders, which use the rows as lists, take ``scene_lists`` then: ``index_reader_route``).  Read at every
+    call."""
     value = os.environ.get("MSPA_VISINDEX_DECODE", "host").strip().lower() or "host"
     if value not in ("host", "device"):
         raise ValueError(f"MSPA_VISINDEX_DECODE={value!r}: expected 'host' or 'device'")
@@ -268,6 +269,125 @@ _PLAIN_PAGE, _DICT_CODED, _DICTIONARY = range(3)
 
 # the rows of the page table ``scene_bits`` sends to the device (one column per page, one more for the running sums' ends)
 _SRC, _COMPRESSED, _UNCOMPRESSED, _PAYLOAD, _VALUES, _ROW_BEGIN = range(6)
+
+
+class _DeviceRows(NamedTuple):
+    """What ``SceneRowGroups._rows_on_device`` hands ``scene_bits`` and ``scene_lists``."""
+    present: list             # the requested ids the file has, in request order
+    order: list               # per present id: its row in ``got``'s tables (the distinct rows in (row group, row) order)
+    payloads: object          # the decompressed pages, on the device (the declined rows' texts are read back from them)
+    got: Optional[dict]       # ``engine.index_spans_to_bits``' or ``index_spans_to_lists``' dict
+
+
+def index_reader_route(visibility_info_path: str) -> str:
+    """Which reader a builder that uses the index's rows as lists (the depth builders) takes: "lists"
+    (``SceneRowGroups.scene_lists``: ``MSPA_VISINDEX_DECODE=device`` and a parquet index) or "handler"
+    (``VisibilityInfoHandler``: the switch unset, or a .pkl index).  A wrong value of the switch raises ``decode_mode``'s
+    ValueError whatever the file is."""
+    return "lists" if decode_mode() == "device" and str(visibility_info_path).endswith(".parquet") else "handler"
+
+
+class IndexLists:
+    """A scene's ``image_to_points`` rows as the LISTS the text holds -- ``len(row)`` and ``row[j]``, duplicates counted, in the
+    text's order -- behind one interface in two forms: the device form (``values`` / ``offsets`` of
+    ``engine.index_spans_to_lists`` stay on the GPU, ``pick`` is ``engine.index_lists_pick``; the rows the device declined
+    are served from their text) and the host form (every row from its text: ``json.loads`` at first use, as
+    ``VisibilityInfoHandler`` does per call).  ``present``: the requested ids the file has, in request order."""
+
+    def __init__(self, scene_id: str, present: list, device, texts: Dict[str, str], values=None, offsets=None, row_of: Optional[Dict[str, int]] = None,
+                 row_counts: Optional[np.ndarray] = None):
+        self.scene_id, self.present, self.device = scene_id, list(present), device
+        self.values, self.offsets = values, offsets
+        self._texts = texts                       # image id -> JSON text of the rows served on the host
+        self._row_of = row_of or {}               # image id -> row of values / offsets, for the others
+        self._row_counts = row_counts
+        self._parsed: Dict[str, object] = {}
+        self._counts: Optional[np.ndarray] = None
+
+    def _key_error(self, image_id):
+        return ValueError(f"Key {self.scene_id}:image_to_points:{image_id} not found in visibility info.")
+
+    def _host_list(self, image_id):
+        if image_id not in self._parsed:
+            self._parsed[image_id] = json.loads(self._texts[image_id])
+        return self._parsed[image_id]
+
+    def count(self, image_id) -> int:
+        """``len`` of the image's list; an id the index lacks raises ``VisibilityInfoHandler``'s ValueError."""
+        if image_id in self._texts:
+            return len(self._host_list(image_id))
+        if image_id not in self._row_of:
+            raise self._key_error(image_id)
+        return int(self._row_counts[self._row_of[image_id]])
+
+    @property
+    def counts(self) -> np.ndarray:
+        """int64, one entry per present id."""
+        if self._counts is None:
+            self._counts = np.array([self.count(i) for i in self.present], dtype=np.int64)
+        return self._counts
+
+    def _range_error(self, image_id, vertex, n_points):
+        return ValueError(f"visindex: scene {self.scene_id}, image {image_id}: vertex {vertex} of the visibility index lies outside "
+                          f"[0, {n_points})")
+
+    def pick(self, samples, n_points: int):
+        """``[int(row(image_id)[position]) for image_id, position in samples]`` as an int32 tensor on ``device``, every vertex
+        inside [0, n_points) -- it may index the scene's vertex table unchecked.  The first sample that is not: an id the
+        index lacks raises ``count``'s ValueError, a position outside the list IndexError (``list[j]``), a vertex outside
+        [0, n_points) ValueError.  Device form: one launch, one read-back of the status."""
+        import torch
+        samples = list(samples)
+        n_points = int(n_points)
+        errors: Dict[int, Exception] = {}
+        on_host, on_device = {}, []
+        for s, (image_id, position) in enumerate(samples):
+            if image_id in self._texts:
+                seen = self._host_list(image_id)
+                if int(position) < 0:
+                    errors[s] = IndexError("list index out of range")
+                    continue
+                try:
+                    vertex = int(seen[position])
+                except IndexError as e:
+                    errors[s] = e
+                    continue
+                if 0 <= vertex < n_points:
+                    on_host[s] = vertex
+                else:
+                    errors[s] = self._range_error(image_id, vertex, n_points)
+            elif image_id in self._row_of:
+                on_device.append(s)
+            else:
+                errors[s] = self._key_error(image_id)
+        if errors and not on_device:
+            raise errors[min(errors)]
+        if not on_device:
+            return torch.tensor([on_host[s] for s in range(len(samples))], dtype=torch.int32).to(self.device)
+        from . import _lib, engine
+        table = torch.tensor([[self._row_of[samples[s][0]], int(samples[s][1])] for s in on_device], dtype=torch.int64).to(self.device)
+        vertex, status = engine.index_lists_pick(self.values, self.offsets, table, n_points)
+        status = status.cpu().numpy()                                          # THE read-back: nothing leaves unchecked
+        for k in np.nonzero(status)[0][:1]:                                    # the first one in sample order
+            s = on_device[int(k)]
+            image_id, position = samples[s]
+            code = int(status[k])
+            if code == _lib.PICK_EPOSITION:
+                errors[s] = IndexError("list index out of range")
+            elif code == _lib.PICK_ERANGE:
+                at = int(self.offsets[self._row_of[image_id]].item()) + int(position)
+                errors[s] = self._range_error(image_id, int(self.values[at].item()), n_points)
+            else:
+                errors[s] = RuntimeError(f"visindex: scene {self.scene_id}, image {image_id}: pick status {code} (the list tables are damaged)")
+        if errors:
+            raise errors[min(errors)]
+        if not on_host:
+            return vertex
+        out = torch.empty((len(samples),), dtype=torch.int32, device=vertex.device)
+        out[torch.tensor(on_device, dtype=torch.int64, device=vertex.device)] = vertex
+        out[torch.tensor(list(on_host), dtype=torch.int64, device=vertex.device)] = torch.tensor(list(on_host.values()), dtype=torch.int32,
+                                                                                               device=vertex.device)
+        return out
 
 
 class SceneRowGroups:
@@ -571,11 +691,12 @@ class SceneRowGroups:
             at += p.uncompressed
         return payloads, status, route
 
-    def _mixed_rows_to_bits(self, payloads, pages: List[_Page], tab, n_points, has_levels: bool, device):
+    def _mixed_row_spans(self, payloads, pages: List[_Page], tab, has_levels: bool, device):
         """``scene_bits`` step 4 for a plan with dictionary-coded pages: the dictionary pages' entries -> a span table
         (``engine.parquet_plain_spans_device`` without levels, every entry a row); the dictionary-coded pages' rows -> spans
         through it (``engine.parquet_dict_spans_device``); the PLAIN pages' rows -> spans as ever; both merged into the one
-        row-ordered span table ``engine.index_spans_to_bits`` takes.  Returns its dict; ``page_status`` holds every call's pages."""
+        row-ordered span table ``engine.index_spans_to_bits`` / ``index_spans_to_lists`` take.  Returns (start, length, page
+        status of every call's pages), on the device."""
         import torch
         from . import engine
 
@@ -611,7 +732,7 @@ class SceneRowGroups:
             at = slots(plain)
             start[at], length[at] = a, n
             status.append(st)
-        return engine.index_spans_to_bits(payloads, start, length, n_points, torch.cat(status))
+        return start, length, torch.cat(status)
 
     def _repair_rows(self, got: dict, payloads, n_points):
         """``scene_bits`` step 5: the rows the device declined get their text back from the device's pages and take the host path --
@@ -659,13 +780,31 @@ class SceneRowGroups:
         from . import engine
         image_ids = list(image_ids)
         self.decode_stats["scenes"] += 1
-
-        def host(why):
-            self._decline(why)
+        rows = self._rows_on_device(scene_id, image_ids, device, "rows_to_bits",
+                                    lambda payloads, start, length, status: engine.index_spans_to_bits(payloads, start, length, n_points, status))
+        if isinstance(rows, str):
+            self._decline(rows)
             return self._scene_bits_host(scene_id, image_ids, n_points, device)
+        if not rows.present:
+            n = 1 if n_points is None else int(n_points)
+            return rows.present, torch.zeros((0, (n + 63) // 64), dtype=torch.int64, device=device)
+        bits = self._repair_rows(rows.got, rows.payloads, n_points)
+        order = torch.tensor(rows.order, dtype=torch.int64, device=bits.device)
+        if len(order) != bits.shape[0] or not bool((order == torch.arange(len(order), device=bits.device)).all().item()):
+            bits = bits.index_select(0, order)
+        return rows.present, bits
 
+    def _rows_on_device(self, scene_id: str, image_ids: list, device, stage: str, spans_to):
+        """``scene_bits``' and ``scene_lists``' steps 1 - 4: the wanted rows (``image_rows``), the pages that hold them
+        (``_plan_pages``), their upload, ``_decompress_pages`` and the rows' spans (PLAIN, or dictionary-coded and PLAIN merged),
+        handed to ``spans_to(payloads, start, length, page_status)`` -- ``engine.index_spans_to_bits`` or ``index_spans_to_lists``
+        -- whose dict comes back as ``got`` of a ``_DeviceRows``; ``stage`` names that call on the stage clock.  A str instead:
+        why the device path does not take this scene (the caller declines it and takes the host path).  No present id: a
+        ``_DeviceRows`` with nothing but the empty ``present``.  Counts everything in ``decode_stats`` but scenes and declines."""
+        import torch
+        from . import engine
         if self._path is None or not self._device_schema:
-            return host("not a file on disk" if self._path is None else "values is not a flat BYTE_ARRAY column")
+            return "not a file on disk" if self._path is None else "values is not a flat BYTE_ARRAY column"
         if self.stage_times is not None:
             import time
             self._stage_start = time.perf_counter()
@@ -674,13 +813,12 @@ class SceneRowGroups:
         present_pos = sorted(found)
         present = [image_ids[k] for k in present_pos]
         if not present:
-            n = 1 if n_points is None else int(n_points)
-            return present, torch.zeros((0, (n + 63) // 64), dtype=torch.int64, device=device)
+            return _DeviceRows(present, [], None, None)
         # the distinct rows, in (row group, row) order: what the device walks; the request refers to them by position
         distinct = sorted(set(found.values()))
         pages, why = self._plan_pages(distinct)
         if pages is None:
-            return host(why)
+            return why
         n_pages, upload = len(pages), sum(p.compressed for p in pages)
         staged = torch.empty((max(upload, 1),), dtype=torch.uint8, pin_memory=True)
         if upload:
@@ -698,21 +836,22 @@ class SceneRowGroups:
         row_index = np.concatenate([p.rows for p in pages]).astype(np.int64)
         tab_dev = torch.from_numpy(tab).to(device)
         if any(not p.snappy and p.compressed != p.uncompressed for p in pages):
-            return host("an uncompressed page whose sizes differ")
+            return "an uncompressed page whose sizes differ"
         payloads, stream_status, route = self._decompress_pages(src, pages, tab_dev)
         self._mark("decompress")
         # the data pages open the tables (``_plan_pages``); dictionary pages, if any, stand behind them and hold no row
         n_data = sum(1 for p in pages if p.kind != _DICTIONARY)
         has_levels = self._has_levels and not any(p.v2 for p in pages)      # a v2 page's levels stayed on the host, checked
         if all(p.kind == _PLAIN_PAGE for p in pages):
-            got = engine.index_rows_to_bits(payloads, tab_dev[_PAYLOAD, :n_data].contiguous(), tab_dev[_UNCOMPRESSED, :n_data].contiguous(),
-                                            tab_dev[_VALUES, :n_data].contiguous(), tab_dev[_ROW_BEGIN, :n_data + 1].contiguous(),
-                                            torch.from_numpy(row_index).to(device), n_points=n_points, has_levels=has_levels)
+            spans = engine.parquet_plain_spans_device(payloads, tab_dev[_PAYLOAD, :n_data].contiguous(), tab_dev[_UNCOMPRESSED, :n_data].contiguous(),
+                                                      tab_dev[_VALUES, :n_data].contiguous(), tab_dev[_ROW_BEGIN, :n_data + 1].contiguous(),
+                                                      torch.from_numpy(row_index).to(device), has_levels=has_levels)
         else:
-            got = self._mixed_rows_to_bits(payloads, pages, tab, n_points, has_levels, device)
+            spans = self._mixed_row_spans(payloads, pages, tab, has_levels, device)
+        got = spans_to(payloads, *spans)
         if (stream_status is not None and bool((stream_status != 0).any().item())) or bool(got["page_status"].any()):
-            return host("the device declined a page")
-        self._mark("rows_to_bits")
+            return "the device declined a page"
+        self._mark(stage)
         if stream_status is not None:
             routes = route.cpu().numpy() if route is not None else np.zeros(len(stream_status), dtype=np.int32)
             self.decode_stats["blocks"] += int(routes.sum())
@@ -720,12 +859,47 @@ class SceneRowGroups:
         self.decode_stats["rows"] += len(distinct)
         self.decode_stats["dict_pages"] += sum(1 for p in pages if p.kind == _DICT_CODED)
         self.decode_stats["v2_pages"] += sum(1 for p in pages if p.v2)
-        bits = self._repair_rows(got, payloads, n_points)
         slot = {gr: k for k, gr in enumerate(distinct)}
-        order = torch.tensor([slot[found[k]] for k in present_pos], dtype=torch.int64, device=bits.device)
-        if len(order) != bits.shape[0] or not bool((order == torch.arange(len(order), device=bits.device)).all().item()):
-            bits = bits.index_select(0, order)
-        return present, bits
+        return _DeviceRows(present, [slot[found[k]] for k in present_pos], payloads, got)
+
+    def _scene_lists_host(self, scene_id: str, image_ids: list, device) -> IndexLists:
+        """The host form: the present rows' texts from ``scene_dict``."""
+        texts = self.scene_dict(scene_id)
+        present = [i for i in image_ids if f"{scene_id}:image_to_points:{i}" in texts]
+        return IndexLists(scene_id, present, device, {i: texts[f"{scene_id}:image_to_points:{i}"] for i in present})
+
+    def scene_lists(self, scene_id: str, image_ids, device="cuda") -> IndexLists:
+        """The requested images' ``image_to_points`` rows as lists (``IndexLists``: ``count(image)``, ``pick([(image, position)],
+        n_points)``) for the readers that take ``len(row)`` and ``row[j]`` -- a bitset answers neither for a row with a
+        duplicate or out of order.  ``scene_bits``' way to the device up to the parsed lists (``_rows_on_device`` with
+        ``engine.index_spans_to_lists``); ``values`` / ``offsets`` stay there.  A row the device declines (a '-', a non-digit,
+        more than 10 digits, a leading zero, no [...]) gets its text back from the device's pages and is served through
+        ``json.loads`` (``decode_stats["rows_declined"]``); a scene it does not take (a codec, a declined page, not a file on
+        disk: ``scenes_declined``, ``last_decline``) comes in the host form, as does every scene with ``device="cpu"``."""
+        image_ids = list(image_ids)
+        self.decode_stats["scenes"] += 1
+        if str(device) == "cpu":
+            return self._scene_lists_host(scene_id, image_ids, "cpu")
+        import torch
+        from . import engine
+        rows = self._rows_on_device(scene_id, image_ids, device, "rows_to_lists", engine.index_spans_to_lists)
+        if isinstance(rows, str):
+            self._decline(rows)
+            return self._scene_lists_host(scene_id, image_ids, device)
+        if not rows.present:
+            return IndexLists(scene_id, [], device, {})
+        got = rows.got
+        row_of = dict(zip(rows.present, rows.order))
+        texts: Dict[str, str] = {}
+        declined = np.nonzero(got["row_status"])[0]
+        if len(declined):                                          # their text back from the device's pages, as ``_repair_rows``
+            self.decode_stats["rows_declined"] += len(declined)
+            which = torch.from_numpy(declined).to(got["start"].device)
+            spans = torch.stack([got["start"], got["length"]])[:, which].cpu().numpy()
+            text_of = {int(r): bytes(rows.payloads[int(a):int(a) + int(n)].cpu().numpy()).decode() for r, a, n in zip(declined, spans[0], spans[1])}
+            texts = {i: text_of[r] for i, r in row_of.items() if r in text_of}
+            row_of = {i: r for i, r in row_of.items() if r not in text_of}
+        return IndexLists(scene_id, rows.present, got["values"].device, texts, got["values"], got["offsets"], row_of, got["counts"])
 
     def _split_group(self, g: int) -> Dict[str, Dict[str, str]]:
         if g not in self._cache:

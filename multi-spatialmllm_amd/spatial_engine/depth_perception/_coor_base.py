@@ -5,7 +5,7 @@ from __future__ import annotations
 import os
 import random
 
-from mspa import heads
+from mspa import heads, visindex
 from spatial_engine.utils.scannet_utils.handler.info_handler import SceneInfoHandler, VisibilityInfoHandler
 from mspa.hostinfo import quietly
 
@@ -20,6 +20,16 @@ class _LazyCounts:
         return len(self._lists(image_id))
 
 
+class _IndexCounts:
+    """The same over a scene's ``visindex.IndexLists``: the lengths came back with the device decode."""
+
+    def __init__(self, lists):
+        self._lists = lists
+
+    def __getitem__(self, image_id):
+        return self._lists.count(image_id)
+
+
 class DepthCoorEngineBase:
     task_name = ""
     TEMPLATE_SET = None
@@ -32,7 +42,15 @@ class DepthCoorEngineBase:
         self.all_max_samples = all_max_samples
         self.max_n_points_per_image = max_n_points_per_image
         self.warning_file = warning_file
-        self.visibility_info = VisibilityInfoHandler(visibility_info_path)
+        # MSPA_VISINDEX_DECODE=device and a parquet index: the rows come from the file's pages as lists on the GPU, scene by scene
+        # (``visindex.SceneRowGroups.scene_lists``) -- the file is never read whole and no handler dict is built
+        self.visibility_info, self.index_lists = None, None
+        if visindex.index_reader_route(visibility_info_path) == "lists":
+            self.index_lists = visindex.SceneRowGroups(visibility_info_path)
+            self.index_lists.page_kinds = "any"                   # dictionary-coded and v2 pages too: whoever wrote the file
+            self._scene_lists_cache = {}                          # scene id -> IndexLists, the two last scenes (~40 MB of values each)
+        else:
+            self.visibility_info = VisibilityInfoHandler(visibility_info_path)
         self.max_samples = -1
         self.templates = self.TEMPLATE_SET
         self.annotator = None          # dot variants: mspa.annotate.default_annotator() unless the caller sets another one
@@ -57,11 +75,31 @@ class DepthCoorEngineBase:
             return cache[image_id]
         return visible_points
 
+    def _lists_of(self, scene_id):
+        """The scene's ``IndexLists`` (device route only), asked once for all its pose-valid images and kept while it is one of
+        the two last scenes: a sharded build makes a scene's draws and, on its owner, its picks at different times."""
+        cache = self._scene_lists_cache
+        if scene_id not in cache:
+            while len(cache) >= 2:
+                del cache[next(iter(cache))]
+            cache[scene_id] = self.index_lists.scene_lists(scene_id, self.scene_info.get_all_extrinsic_valid_image_ids(scene_id))
+        return cache[scene_id]
+
+    def _visible_counts(self, scene_id):
+        """len(visible points) per image, read only for the images that are sampled: an image the index lacks raises at its draw."""
+        if self.index_lists is not None:
+            return _IndexCounts(self._lists_of(scene_id))
+        return _LazyCounts(self._visible_points_of(scene_id))
+
     def _scene_inputs(self, scene_id, scene=None):
-        visible_points = self._visible_points_of(scene_id)
         scene = scene if scene is not None else self.scene_info.scene_on_device(scene_id)
-        return (self.scene_info.get_all_extrinsic_valid_image_ids(scene_id), _LazyCounts(visible_points),
-                heads.list_point_numerics(scene, visible_points), self.scene_info.get_image_shape(scene_id))
+        if self.index_lists is not None:
+            lists = self._lists_of(scene_id)
+            n_visible, numeric_fn = _IndexCounts(lists), heads.index_point_numerics(scene, lists)
+        else:
+            visible_points = self._visible_points_of(scene_id)
+            n_visible, numeric_fn = _LazyCounts(visible_points), heads.list_point_numerics(scene, visible_points)
+        return self.scene_info.get_all_extrinsic_valid_image_ids(scene_id), n_visible, numeric_fn, self.scene_info.get_image_shape(scene_id)
 
     def _annotated_path(self, scene_id, name):
         return os.path.join(self.image_output_dir, scene_id, name)

@@ -10,7 +10,7 @@ import numpy
 
 from mspa import heads
 from mspa import templates as T
-from spatial_engine.depth_perception._coor_base import DepthCoorEngineBase, _LazyCounts, run_cli
+from spatial_engine.depth_perception._coor_base import DepthCoorEngineBase, run_cli
 
 numpy.random.seed(7)
 random.seed(7)
@@ -30,7 +30,7 @@ class DepthComparisonCoorQAEngine(DepthCoorEngineBase):
         """The scene's records, the generator advanced as upstream advances it; ``dry_run``: only the draws of a scene without a
         skipped pair (host side: the visibility index is all they read)."""
         if dry_run:
-            image_ids, n_visible = self.scene_info.get_all_extrinsic_valid_image_ids(scene_id), _LazyCounts(self._visible_points_of(scene_id))
+            image_ids, n_visible = self.scene_info.get_all_extrinsic_valid_image_ids(scene_id), self._visible_counts(scene_id)
             numeric_fn, image_hw = None, self.scene_info.get_image_shape(scene_id)
         else:
             image_ids, n_visible, numeric_fn, image_hw = self._scene_inputs(scene_id, scene)

@@ -9,7 +9,7 @@ import numpy
 from mspa import heads
 from mspa import templates as T
 from mspa.annotate import Mark
-from spatial_engine.depth_perception._coor_base import DepthCoorEngineBase, _LazyCounts, run_cli
+from spatial_engine.depth_perception._coor_base import DepthCoorEngineBase, run_cli
 
 numpy.random.seed(5)
 random.seed(5)
@@ -29,7 +29,7 @@ class DepthEstimationDotQAEngine(DepthCoorEngineBase):
     def _scene_draws(self, scene_id):
         """The scene's random decisions (images, vertex positions, templates, disc colours): they read the visibility index only."""
         return heads.depth_estimation_draws(self.scene_info.get_all_extrinsic_valid_image_ids(scene_id),
-                                            _LazyCounts(self._visible_points_of(scene_id)), self.max_samples, self.templates, random,
+                                            self._visible_counts(scene_id), self.max_samples, self.templates, random,
                                             self.max_n_points_per_image, True)
 
     def _scene_records_on(self, scene, scene_id, draws):

@@ -23,7 +23,12 @@ pyarrow's defaults: dictionary encoding on, row groups of 1 Mi rows that mix sce
 page in front of the PLAIN pages of every row group.  The device path then runs with ``page_kinds = "plain"`` (dictionary-coded
 pages decline the scene to the host path: the paths named ``device_plain``) and with ``"any"`` (``device_any``); every path
 reports its declined scenes, and each scene's wall of the last pass is listed (``scene_ms_last_pass``) beside the pages it
-needed.  The host path of such a file reads a whole row group for its first scene and keeps it (``scene_dict``)."""
+needed.  The host path of such a file reads a whole row group for its first scene and keeps it (``scene_dict``).
+
+``--lists``: the rows as LISTS, the depth builders' route -- ``scene_lists`` and one ``pick`` of one position per image, per scene
+-- twice in turn with ``scene_bits`` (``page_kinds = "any"``) on the same file in this process, and the builders' access with the
+switch unset: ``json.loads`` of each image's text, ``len`` and one element, the texts already in memory.  Reports
+``lists_over_bits`` and ``host_access_over_lists``; nothing else runs."""
 import argparse
 import json
 import os
@@ -67,6 +72,8 @@ def main():
     ap.add_argument("--device-only", action="store_true", help="skip the host path and the kernel-alone timings (for a profiler run)")
     ap.add_argument("--route", choices=("both", "blocks", "one-wave"), default="both",
                     help="the device path's Snappy decode: one wave per 64 KiB block, the one-wave kernel for every page, or both in turn")
+    ap.add_argument("--lists", action="store_true",
+                    help="time scene_lists + one pick per image (the depth builders' route) beside scene_bits and beside the builders' host access")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -129,6 +136,69 @@ def main():
             res["stages_ms_all"] = st_all
         return res
 
+    def run_lists(scenes):
+        """``scene_lists`` and one ``pick`` of one position per image (what a depth builder asks of a scene it draws every image
+        of), per scene; the picks read back."""
+        rng = np.random.default_rng(7)
+        wall, cpu = [], []
+        for _ in range(a.passes):
+            index = visindex.SceneRowGroups(path)
+            index.page_kinds = "any"
+            torch.cuda.synchronize()
+            c0, t0 = time.process_time(), time.perf_counter()
+            for s in scenes:
+                lists = index.scene_lists(s, ids)
+                samples = [(i, int(rng.integers(0, n))) for i, n in zip(lists.present, lists.counts.tolist())]
+                picked = lists.pick(samples, a.points).cpu()
+            wall.append((time.perf_counter() - t0) / len(scenes))
+            cpu.append((time.process_time() - c0) / len(scenes))
+            assert lists.present == ids and index.decode_stats["rows_declined"] == 0 and index.decode_stats["scenes_declined"] == 0
+            assert lists.counts.tolist() == want_counts and picked.tolist() == [want_lists[k][j] for k, (_, j) in enumerate(samples)]
+            print(f"lists: pass of {len(scenes)} scenes, {1e3 * wall[-1]:.1f} ms per scene", file=sys.stderr, flush=True)
+        return {"scenes_per_pass": len(scenes), "wall_ms": round(1e3 * statistics.median(wall[1:]), 2),
+                "process_cpu_ms": round(1e3 * statistics.median(cpu[1:]), 2), "wall_ms_all": [round(1e3 * v, 2) for v in wall],
+                "process_cpu_ms_all": [round(1e3 * v, 2) for v in cpu]}
+
+    def run_host_access(scenes):
+        """The builders' access with the switch unset, per scene: ``json.loads`` of every image's text, its ``len`` and one element.
+        The texts are in memory already (``VisibilityInfoHandler`` holds the whole file as a dict): reading them (``scene_dict``) is
+        timed apart."""
+        rng = np.random.default_rng(7)
+        wall, cpu, read = [], [], []
+        index = visindex.SceneRowGroups(path)
+        for _ in range(a.passes):
+            for s in scenes:
+                t0 = time.perf_counter()
+                texts = index.scene_dict(s)
+                read.append(time.perf_counter() - t0)
+                c0, t0 = time.process_time(), time.perf_counter()
+                got = []
+                for i in ids:
+                    seen = json.loads(texts[f"{s}:image_to_points:{i}"])
+                    got.append((len(seen), int(seen[int(rng.integers(0, len(seen)))])))
+                wall.append(time.perf_counter() - t0)
+                cpu.append(time.process_time() - c0)
+            assert [n for n, _ in got] == want_counts
+            print(f"host access: pass of {len(scenes)} scenes, {1e3 * wall[-1]:.1f} ms per scene", file=sys.stderr, flush=True)
+        warm = len(scenes)                                       # the first pass is the warm-up
+        return {"scenes_per_pass": len(scenes), "wall_ms": round(1e3 * statistics.median(wall[warm:]), 2),
+                "process_cpu_ms": round(1e3 * statistics.median(cpu[warm:]), 2), "scene_dict_read_ms": round(1e3 * statistics.median(read[warm:]), 2),
+                "wall_ms_all": [round(1e3 * v, 2) for v in wall]}
+
+    if a.lists:
+        # the rows as lists (the depth builders' route) beside scene_bits on the same file in this process, and beside the host access
+        want_lists = [np.nonzero(np.unpackbits(row.view(np.uint8), bitorder="little")[:a.points])[0].tolist() for row in want]
+        want_counts = [len(v) for v in want_lists]
+        for turn in ("first", "second"):                         # bits, lists, bits, lists: drift of the box shows between the turns
+            out["paths"][f"scene_bits_{turn}"] = run("device", scene_ids, False, page_kinds="any")
+            out["paths"][f"scene_lists_pick_{turn}"] = run_lists(scene_ids)
+        out["paths"]["host_access"] = run_host_access(scene_ids[:a.host_scenes])
+        bits_ms = statistics.median([out["paths"][f"scene_bits_{t}"]["wall_ms"] for t in ("first", "second")])
+        lists_ms = statistics.median([out["paths"][f"scene_lists_pick_{t}"]["wall_ms"] for t in ("first", "second")])
+        out["lists_over_bits"] = round(lists_ms / bits_ms, 3)
+        out["host_access_over_lists"] = round(out["paths"]["host_access"]["wall_ms"] / lists_ms, 2)
+        print(json.dumps(out))
+        return
     if not a.device_only:
         out["paths"]["host"] = run("host", scene_ids[:a.host_scenes], False)
     if a.layout == "pandas":
