@@ -764,6 +764,75 @@ int mspa_index_lists_pick_device(const int32_t *values_dev, int64_t n_values, co
                                  int32_t *out_status_dev, void *stream);
 
 /*
+ * The pair table sampled ON THE DEVICE (csrc/pair_table.hip; the bin rule in csrc/pair_bins_core.h): the DOUBLE column chunks of
+ * `*_camera_info_D5.parquet` from decompressed pages to float64 columns, `overlap` to one class byte per row and the classes to
+ * lists of ascending file rows -- what mspa/pairtable.py draws its sample from.
+ *
+ * mspa_rle_hybrid_runs_device  a batch of RLE / bit-packed hybrid streams (csrc/rle_hybrid_core.h), ALL values wanted: stream s
+ *   is src_dev[stream_offsets_dev[s], + stream_bytes_dev[s]) with bit width stream_bit_width_dev[s] and stream_values_dev[s]
+ *   values (all int64); its values go to out[out_begin_dev[s] ..] of the expansion (out_begin_dev [n_streams + 1]: the exclusive
+ *   prefix sum of the value counts, the caller's plumbing).  One lane per stream walks the run headers, one step per run, until
+ *   the values are covered.  Always written: run_count_dev[s] (int64), status_dev[s] (int32: 0, or
+ *   mspa_rle_hybrid_take_host's code, MSPA_EINVAL for a table entry outside src) and const_value_dev[s] (int32: the value when
+ *   the stream is ONE RLE run over all its values, else -1).  With run_begin_dev (int64 [n_streams + 1], the exclusive prefix
+ *   sum of a first call's run_count_dev; n_runs its last entry) the run table is written too: run_first_dev[r] (int64, where
+ *   run r's first value goes in the expansion), run_pos_dev[r] (int64, where its bytes lie in src) and run_info_dev[r] (int32:
+ *   bit 0 bit-packed, bit 1 a hole, bits 8.. the bit width).  A declined stream's runs end with one hole over the values it did
+ *   not give (counted in run_count_dev).  run_begin_dev null or n_runs = 0: a counting call.
+ * mspa_rle_hybrid_expand_device  the run table -> out_dev [n_values] int32, one lane per value: mspa_rle_hybrid_take_host's
+ *   values for rows 0 .. n - 1 of every stream, -1 inside a hole.
+ * mspa_parquet_double_layout_device  one lane per decompressed page of a DOUBLE chunk (page p: pages_dev[page_offsets_dev[p], +
+ *   page_bytes_dev[p])): page_flags_dev[p] (int32) bit 0 a v1 page whose payload opens with u32le(L) and L bytes of RLE
+ *   definition levels, bit 1 dictionary-coded values (a byte of bit width, then hybrid indices), bit 2 a v2 page whose level
+ *   bytes the caller has put into rows 0 / 1 of layout_dev.  layout_dev [5, n_pages] int64: level offset, level bytes, value
+ *   offset, value bytes (positions in pages_dev), bit width.  page_status_dev[p] (int32): 0, or 1 when the tables do not
+ *   describe the page or a length runs past it (its layout is then empty).
+ * mspa_parquet_double_column_device  out_dev [n_out] float64, one lane per row: page_first_dev [n_pages] (int64, ascending,
+ *   first entry 0) says where each page's first row goes in out_dev, page_values_dev its rows.  With levels_dev (int32, the
+ *   expansion of the level streams, level_begin_dev[p] where page p's open; level_rank_dev the exclusive running sum of
+ *   levels_dev) a row of level 0 reads as NaN (0x7ff8000000000000) and the others take value k, k = the non-null rows of the
+ *   page in front; levels_dev null: no page has a null.  A PLAIN page gives the 8 bytes at value offset + 8 k; a dictionary-
+ *   coded page entry indices_dev[index_begin_dev[p] + k] of the dictionary at pages_dev[dict_offsets_dev[p], + 8
+ *   dict_count_dev[p]) (a decompressed PLAIN dictionary page).  value_status_dev[p] (int32, cleared by the call): 5 when a
+ *   level, an index or a value lies outside what the page holds; such rows read as NaN.
+ * mspa_pair_bin_codes_host / _device  the sampler's bin rule (mspa/sampling.py: pd.cut(x, edges, include_lowest=True) behind
+ *   the `== 0` split): edges [n_edges] float64, strictly ascending, 2 <= n_edges <= 251.  codes[i] (uint8) = the row's bin,
+ *   254 for x == 0 (-0.0 too) or 255 for a row the sampler drops (NaN, outside the edges).  Host: out_counts [256] int64.
+ *   Device: a wave per tile of mspa_pair_tile_rows() rows; out_tile_counts_dev [n_tiles, 256] int32, n_tiles =
+ *   ceil(n / tile rows); n < 2^31.
+ * mspa_pair_partition_device  codes_dev -> out_order_dev [n] int32: per class the ascending file rows, back to back.
+ *   tile_offsets_dev [n_tiles, 256] int32: where tile t's first row of class c goes -- the exclusive prefix sum of the tile
+ *   counts in (class, tile) order (the caller's plumbing).  Offsets that are not write nothing outside out_order_dev.
+ * All device calls only enqueue on `stream`; a wrong argument returns MSPA_EINVAL before anything is enqueued; no atomics.
+ */
+#define MSPA_PAIR_CLASS_ZERO 254
+#define MSPA_PAIR_CLASS_DROPPED 255
+#define MSPA_PAIR_MAX_BINS 250
+int mspa_rle_hybrid_runs_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *stream_offsets_dev,
+                                const int64_t *stream_bytes_dev, const int64_t *stream_bit_width_dev, const int64_t *stream_values_dev,
+                                const int64_t *out_begin_dev, const int64_t *run_begin_dev, int64_t n_streams, int64_t n_runs,
+                                int64_t *run_count_dev, int32_t *status_dev, int32_t *const_value_dev, int64_t *run_first_dev,
+                                int64_t *run_pos_dev, int32_t *run_info_dev, void *stream);
+int mspa_rle_hybrid_expand_device(const uint8_t *src_dev, int64_t src_bytes, const int64_t *run_first_dev, const int64_t *run_pos_dev,
+                                  const int32_t *run_info_dev, int64_t n_runs, int32_t *out_dev, int64_t n_values, void *stream);
+int mspa_parquet_double_layout_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *page_offsets_dev,
+                                      const int64_t *page_bytes_dev, const int32_t *page_flags_dev, int64_t n_pages, int64_t *layout_dev,
+                                      int32_t *page_status_dev, void *stream);
+int mspa_parquet_double_column_device(const uint8_t *pages_dev, int64_t pages_bytes, const int64_t *layout_dev,
+                                      const int64_t *page_values_dev, const int32_t *page_flags_dev, const int64_t *page_first_dev,
+                                      int64_t n_pages, const int32_t *levels_dev, const int64_t *level_rank_dev,
+                                      const int64_t *level_begin_dev, int64_t n_levels, const int32_t *indices_dev,
+                                      const int64_t *index_begin_dev, int64_t n_indices, const int64_t *dict_offsets_dev,
+                                      const int64_t *dict_count_dev, double *out_dev, int64_t n_out, int32_t *value_status_dev,
+                                      void *stream);
+int32_t mspa_pair_tile_rows(void);
+int mspa_pair_bin_codes_host(const double *x, int64_t n, const double *edges, int32_t n_edges, uint8_t *out_codes, int64_t *out_counts);
+int mspa_pair_bin_codes_device(const double *x_dev, int64_t n, const double *edges_dev, int32_t n_edges, uint8_t *out_codes_dev,
+                               int32_t *out_tile_counts_dev, int64_t n_tiles, void *stream);
+int mspa_pair_partition_device(const uint8_t *codes_dev, int64_t n, const int32_t *tile_offsets_dev, int64_t n_tiles,
+                               int32_t *out_order_dev, void *stream);
+
+/*
  * Image resizing ON THE DEVICE (csrc/resize.hip, arithmetic in csrc/resize_core.h): n 8-bit RGB images of one shape resampled
  * to one target shape, bit-identical to Pillow's `Image.resize((W, H), resample)` for resample = BILINEAR (filter 2) and
  * BICUBIC (filter 3, Pillow's default): float64 weights per axis turned into 22-bit fixed point, a horizontal pass rounded to

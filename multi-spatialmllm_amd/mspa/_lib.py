@@ -29,6 +29,11 @@ RLE_EBITWIDTH, RLE_EHEADER, RLE_EZERORUN, RLE_ETRUNCATED, RLE_ESHORT = -32, -33,
 # mspa_index_lists_pick_device's per-sample status (csrc/index_rows.hip: kPick*) and the samples one workgroup takes
 PICK_OK, PICK_EROW, PICK_EPOSITION, PICK_ERANGE, PICK_EOFFSETS = 0, 1, 2, 4, 8
 PICK_BLOCK = 256
+# csrc/pair_bins_core.h: the class bytes that are no bin, the most bins a table may have and the entries of a class table;
+# csrc/pair_table.hip: the page flags of mspa_parquet_double_layout_device and the rows of its layout table
+PAIR_CLASS_ZERO, PAIR_CLASS_DROPPED, PAIR_MAX_BINS, PAIR_CLASSES = 254, 255, 250, 256
+PAGE_LEVELS_INLINE, PAGE_DICT_CODED, PAGE_LEVELS_GIVEN = 1, 2, 4
+LAYOUT_LEVEL_OFFSET, LAYOUT_LEVEL_BYTES, LAYOUT_VALUE_OFFSET, LAYOUT_VALUE_BYTES, LAYOUT_BIT_WIDTH, LAYOUT_ROWS = range(6)
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
@@ -177,6 +182,17 @@ _SIGNATURES = {
     "mspa_index_rows_gather_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "mspa_index_lists_to_bits_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mspa_index_lists_pick_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mspa_rle_hybrid_runs_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_rle_hybrid_expand_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "mspa_parquet_double_layout_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mspa_parquet_double_column_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                  c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                  c_void_p, c_void_p]),
+    "mspa_pair_tile_rows": (c_int32, []),
+    "mspa_pair_bin_codes_host": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p]),
+    "mspa_pair_bin_codes_device": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_pair_partition_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mspa_track_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                         c_double, c_double, c_void_p, c_void_p, c_void_p]),
 }

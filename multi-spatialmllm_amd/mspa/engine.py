@@ -1092,6 +1092,187 @@ def rle_hybrid_take_host(stream, bit_width: int, n_values: int, rows) -> Tuple[i
     return rc, out
 
 
+def rle_hybrid_runs_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, bit_widths: torch.Tensor, n_values: torch.Tensor):
+    """The run tables of a batch of RLE / bit-packed hybrid streams whose values are ALL wanted (mspa_rle_hybrid_runs_device):
+    stream s is ``src[offsets[s] : + nbytes[s]]`` with ``bit_widths[s]`` bits a value and ``n_values[s]`` values (int64 device
+    tensors, one length).  Returns a dict, everything on the device: ``out_begin`` int64 [n + 1] (where each stream's values go
+    in the expansion), ``total`` (its last entry, an int), ``status`` int32 [n] (0, ``_lib.RLE_E*``, MSPA_EINVAL for a stream
+    outside ``src``), ``const_value`` int32 [n] (the value of a stream that is one RLE run, else -1), ``n_runs`` (an int) and the
+    run table ``run_first`` / ``run_pos`` int64, ``run_info`` int32.  A counting launch, ONE small read-back (the sizes to
+    allocate), a writing launch."""
+    lib = _lib.load()
+    n = _check_streams(offsets, nbytes)
+    _check("src", src, torch.uint8, (None,))
+    _check("bit_widths", bit_widths, torch.int64, (n,))
+    _check("n_values", n_values, torch.int64, (n,))
+    dev = src.device
+    out_begin = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    run_begin = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    run_count = torch.zeros((n,), dtype=torch.int64, device=dev)
+    status = torch.zeros((n,), dtype=torch.int32, device=dev)
+    const_value = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    got = {"out_begin": out_begin, "total": 0, "status": status, "const_value": const_value, "n_runs": 0}
+    for name, dtype in (("run_first", torch.int64), ("run_pos", torch.int64), ("run_info", torch.int32)):
+        got[name] = torch.zeros((0,), dtype=dtype, device=dev)
+    if n == 0:
+        return got
+    torch.cumsum(n_values.clamp(min=0), dim=0, out=out_begin[1:])     # a negative count is the kernel's to refuse (MSPA_EINVAL)
+
+    def launch(begin, n_runs, count, st, const):
+        _lib.check(lib.mspa_rle_hybrid_runs_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(offsets), _ptr(nbytes), _ptr(bit_widths),
+                                                   _ptr(n_values), _ptr(out_begin), _ptr(begin), n, n_runs, _ptr(count), _ptr(st), _ptr(const),
+                                                   _ptr(got["run_first"]) if n_runs else None, _ptr(got["run_pos"]) if n_runs else None,
+                                                   _ptr(got["run_info"]) if n_runs else None, _stream_ptr()))
+
+    launch(None, 0, run_count, status, const_value)
+    torch.cumsum(run_count, dim=0, out=run_begin[1:])
+    head = torch.stack([out_begin[-1], run_begin[-1]]).cpu()
+    got["total"], got["n_runs"] = int(head[0]), int(head[1])
+    if got["n_runs"]:
+        got["run_first"], got["run_pos"] = (torch.zeros((got["n_runs"],), dtype=torch.int64, device=dev) for _ in range(2))
+        got["run_info"] = torch.full((got["n_runs"],), 2, dtype=torch.int32, device=dev)          # a slot nothing writes is a hole
+        launch(run_begin, got["n_runs"], torch.empty_like(run_count), torch.empty_like(status), torch.empty_like(const_value))
+    return got
+
+
+def rle_hybrid_expand_device(src: torch.Tensor, runs: dict) -> torch.Tensor:
+    """``rle_hybrid_runs_device``'s run tables -> every stream's values back to back, int32 [``runs["total"]``] on the device:
+    what ``rle_hybrid_take_host`` gives for rows 0 .. n - 1 of each stream, -1 for the values a declined stream did not give.
+    One lane per value; only enqueues."""
+    _check("src", src, torch.uint8, (None,))
+    n_runs, total = int(runs["n_runs"]), int(runs["total"])
+    _check("run_first", runs["run_first"], torch.int64, (n_runs,))
+    _check("run_pos", runs["run_pos"], torch.int64, (n_runs,))
+    _check("run_info", runs["run_info"], torch.int32, (n_runs,))
+    _require(total >= 0 and (n_runs > 0 or total == 0), "values need runs")
+    out = torch.empty((total,), dtype=torch.int32, device=src.device)
+    if total:
+        _lib.check(_lib.load().mspa_rle_hybrid_expand_device(_ptr(src) if src.numel() else None, src.numel(), _ptr(runs["run_first"]),
+                                                             _ptr(runs["run_pos"]), _ptr(runs["run_info"]), n_runs, _ptr(out), total,
+                                                             _stream_ptr()))
+    return out
+
+
+def parquet_double_columns_device(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
+                                  page_flags: torch.Tensor, page_first: torch.Tensor, n_out: int, level_offsets: torch.Tensor,
+                                  level_sizes: torch.Tensor, dict_offsets: torch.Tensor, dict_count: torch.Tensor):
+    """Decompressed data pages of DOUBLE column chunks -> float64 [``n_out``] on the device, nulls as NaN.  Page p is
+    ``pages[page_offsets[p] : + page_sizes[p]]`` with ``page_values[p]`` rows that go to ``out[page_first[p] ..]`` (``page_first``
+    ascends from 0 and the pages cover ``n_out``: several chunks are laid out one behind the other by the caller).
+    ``page_flags[p]`` (int32): ``_lib.PAGE_LEVELS_INLINE`` (a v1 page: u32 length + RLE definition levels in front),
+    ``_lib.PAGE_LEVELS_GIVEN`` (a v2 page: its level bytes are ``pages[level_offsets[p] : + level_sizes[p]]``),
+    ``_lib.PAGE_DICT_CODED`` (a byte of bit width and hybrid indices into the PLAIN dictionary ``pages[dict_offsets[p] : + 8 *
+    dict_count[p]]``); without the last the values are PLAIN.  All tables int64 but the flags.  Returns (out, status): status a
+    dict of int32 device tensors [pages] -- ``layout`` (1: a length runs past the page), ``levels`` / ``indices`` (the hybrid
+    streams' codes, ``_lib.RLE_E*``), ``values`` (5: a level, index or value the page does not hold) -- all zero for a column
+    that was taken, plus ``null_pages`` (an int: pages whose levels are not one run of ones).  Two small read-backs."""
+    lib = _lib.load()
+    n_pages = _check_streams(page_offsets, page_sizes)
+    _check("pages", pages, torch.uint8, (None,))
+    for name, t in (("page_values", page_values), ("page_first", page_first), ("level_offsets", level_offsets), ("level_sizes", level_sizes),
+                    ("dict_offsets", dict_offsets), ("dict_count", dict_count)):
+        _check(name, t, torch.int64, (n_pages,))
+    _check("page_flags", page_flags, torch.int32, (n_pages,))
+    n_out = int(n_out)
+    _require(n_out >= 0 and (n_pages > 0 or n_out == 0), "rows need pages")
+    dev = pages.device
+    out = torch.empty((n_out,), dtype=torch.float64, device=dev)
+    zeros = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    status = {"layout": zeros, "levels": zeros, "indices": zeros, "values": zeros, "null_pages": 0}
+    if n_out == 0:
+        return out, status
+    src = _ptr(pages) if pages.numel() else None
+    layout = torch.zeros((_lib.LAYOUT_ROWS, n_pages), dtype=torch.int64, device=dev)
+    layout[_lib.LAYOUT_LEVEL_OFFSET], layout[_lib.LAYOUT_LEVEL_BYTES] = level_offsets, level_sizes
+    status["layout"] = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_parquet_double_layout_device(src, pages.numel(), _ptr(page_offsets), _ptr(page_sizes), _ptr(page_flags), n_pages,
+                                                     _ptr(layout), _ptr(status["layout"]), _stream_ptr()))
+    # the level streams (bit width 1) and the index streams of every page, as one batch of hybrid streams
+    has_levels = (page_flags & (_lib.PAGE_LEVELS_INLINE | _lib.PAGE_LEVELS_GIVEN)) != 0
+    coded = (page_flags & _lib.PAGE_DICT_CODED) != 0
+    ok = status["layout"] == 0
+    level_values, index_values = page_values * (has_levels & ok), page_values * (coded & ok)
+    head = torch.stack([level_values.sum(), index_values.sum()]).cpu()
+    levels = rank = indices = None
+    level_begin = index_begin = torch.zeros((n_pages,), dtype=torch.int64, device=dev)
+    n_levels = n_indices = 0
+    if int(head[0]):
+        runs = rle_hybrid_runs_device(pages, layout[_lib.LAYOUT_LEVEL_OFFSET].contiguous(), layout[_lib.LAYOUT_LEVEL_BYTES].contiguous(),
+                                      torch.ones((n_pages,), dtype=torch.int64, device=dev), level_values)
+        status["levels"] = runs["status"]
+        nulls = has_levels & ok & (runs["const_value"] != 1)
+        status["null_pages"] = int(nulls.sum().item())
+        if status["null_pages"]:                                 # otherwise every level is 1 and row r takes value r
+            levels = rle_hybrid_expand_device(pages, runs)
+            rank = torch.cumsum(levels, dim=0, dtype=torch.int64) - levels
+            level_begin, n_levels = runs["out_begin"][:-1].contiguous(), runs["total"]
+    if int(head[1]):
+        runs = rle_hybrid_runs_device(pages, layout[_lib.LAYOUT_VALUE_OFFSET].contiguous(), layout[_lib.LAYOUT_VALUE_BYTES].contiguous(),
+                                      layout[_lib.LAYOUT_BIT_WIDTH].contiguous(), index_values)
+        # the indices of a page with nulls are fewer than its rows: its stream may end early, and the rows that need one say so
+        status["indices"] = torch.where(runs["status"] == _lib.RLE_ESHORT, torch.zeros_like(runs["status"]), runs["status"])
+        indices = rle_hybrid_expand_device(pages, runs)
+        index_begin, n_indices = runs["out_begin"][:-1].contiguous(), runs["total"]
+    status["values"] = torch.zeros((n_pages,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_parquet_double_column_device(src, pages.numel(), _ptr(layout), _ptr(page_values), _ptr(page_flags), _ptr(page_first),
+                                                     n_pages, _ptr(levels), _ptr(rank), _ptr(level_begin), n_levels, _ptr(indices),
+                                                     _ptr(index_begin), n_indices, _ptr(dict_offsets), _ptr(dict_count), _ptr(out), n_out,
+                                                     _ptr(status["values"]), _stream_ptr()))
+    return out, status
+
+
+def pair_tiles(n: int) -> int:
+    """Tiles (one wave's share of rows) of an ``n``-row pair table in ``pair_bin_codes`` / ``pair_partition``."""
+    rows = int(_lib.load().mspa_pair_tile_rows())
+    return (int(n) + rows - 1) // rows
+
+
+def pair_bin_codes_host(overlap, edges) -> Tuple[np.ndarray, np.ndarray]:
+    """mspa_pair_bin_codes_host: the sampler's bin rule on the host -> (codes uint8 [n], counts int64 [256])."""
+    x = np.ascontiguousarray(overlap, dtype=np.float64)
+    e = np.ascontiguousarray(edges, dtype=np.float64)
+    _require(x.ndim == 1 and e.ndim == 1, "overlap, edges: one dimension")
+    codes, counts = np.empty(len(x), dtype=np.uint8), np.zeros(_lib.PAIR_CLASSES, dtype=np.int64)
+    _lib.check(_lib.load().mspa_pair_bin_codes_host(x.ctypes.data if len(x) else None, len(x), e.ctypes.data, len(e),
+                                                    codes.ctypes.data if len(x) else None, counts.ctypes.data))
+    return codes, counts
+
+
+def pair_bin_codes(overlap: torch.Tensor, edges: torch.Tensor):
+    """The sampler's class of every row of ``overlap`` (float64 [n], n < 2^31) for the bin ``edges`` (float64 [2 .. 251], strictly
+    ascending: the caller's to see to) -> (codes uint8 [n]: the bin, ``_lib.PAIR_CLASS_ZERO`` or ``_lib.PAIR_CLASS_DROPPED``;
+    tile_counts int32 [tiles, 256]: rows per class in each tile of ``pair_tiles``), on the device.  Only enqueues."""
+    n = _check("overlap", overlap, torch.float64, (None,)).shape[0]
+    n_edges = _check("edges", edges, torch.float64, (None,)).shape[0]
+    _require(2 <= n_edges <= _lib.PAIR_MAX_BINS + 1 and n <= 0x7fffffff, "2 <= edges <= 251, fewer than 2^31 rows")
+    n_tiles = pair_tiles(n)
+    codes = torch.empty((n,), dtype=torch.uint8, device=overlap.device)
+    tile_counts = torch.zeros((n_tiles, _lib.PAIR_CLASSES), dtype=torch.int32, device=overlap.device)
+    if n:
+        _lib.check(_lib.load().mspa_pair_bin_codes_device(_ptr(overlap), n, _ptr(edges), n_edges, _ptr(codes), _ptr(tile_counts), n_tiles,
+                                                          _stream_ptr()))
+    return codes, tile_counts
+
+
+def pair_partition(codes: torch.Tensor, tile_counts: torch.Tensor):
+    """``pair_bin_codes``' results -> (order int32 [n], begin int64 [257]) on the device: ``order[begin[c] : begin[c + 1]]`` are
+    the file rows of class c, ascending.  The scan over (class, tile) is torch's (plumbing); the scatter is the kernel's.  Only
+    enqueues."""
+    n = _check("codes", codes, torch.uint8, (None,)).shape[0]
+    n_tiles = pair_tiles(n)
+    _check("tile_counts", tile_counts, torch.int32, (n_tiles, _lib.PAIR_CLASSES))
+    dev = codes.device
+    begin = torch.zeros((_lib.PAIR_CLASSES + 1,), dtype=torch.int64, device=dev)
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return order, begin
+    torch.cumsum(tile_counts.sum(dim=0, dtype=torch.int64), dim=0, out=begin[1:])
+    in_class = torch.cumsum(tile_counts, dim=0, dtype=torch.int64) - tile_counts          # rows of the class in the tiles in front
+    tile_offsets = (in_class + begin[:-1]).to(torch.int32).contiguous()
+    _lib.check(_lib.load().mspa_pair_partition_device(_ptr(codes), n, _ptr(tile_offsets), n_tiles, _ptr(order), _stream_ptr()))
+    return order, begin
+
+
 def index_rows_to_bits(pages: torch.Tensor, page_offsets: torch.Tensor, page_sizes: torch.Tensor, page_values: torch.Tensor,
                        row_begin: torch.Tensor, row_index: torch.Tensor, n_points: Optional[int] = None, has_levels: bool = True):
     """Rows of the visibility index straight from their pages to bitset rows, on the device.  ``pages`` (uint8) holds the

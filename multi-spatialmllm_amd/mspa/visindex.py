@@ -279,6 +279,60 @@ class _DeviceRows(NamedTuple):
     got: Optional[dict]       # ``engine.index_spans_to_bits``' or ``index_spans_to_lists``' dict
 
 
+def column_chunk_pages(path: str, col, who: str = "parquet", chunk_name: str = "column chunk", mark=None, file=None) -> tuple:
+    """THE walk of one column chunk's thrift page headers (``parquet_splice._Reader``), for any column: ``col`` is pyarrow's
+    ``ColumnChunkMetaData`` of a chunk of the parquet file at ``path`` (``file``: that file, already open for reading).  Returns
+    (table, the chunk's bytes as they lie in the file).  The table: ``start`` (the chunk's position in the file), ``bytes`` (its
+    compressed size), ``codec`` (the chunk's, as pyarrow names it) and, per page in file order, int64 arrays ``pos`` (the
+    payload's position inside the chunk), ``compressed``, ``uncompressed``, ``num_values``, ``type``, ``encoding`` (-1 where
+    the page has none), ``levels`` (a v1 data page's definition-level encoding, else -1) and ``first_row`` (rows of the group
+    in front of it; ``n_pages + 1`` entries); ``dict_values`` (a dictionary page's entry count, else 0 -- ``num_values`` stays
+    0 there: a dictionary page holds no row) and, for v2 data pages, ``def_bytes`` / ``rep_bytes`` (the level bytes that lie
+    uncompressed in front of the values), ``num_nulls`` and ``is_compressed`` (0 / 0 / 0 / 1 for every other page); ``chunk``
+    None (the bytes are the caller's to keep or drop).  ``mark(stage)``: a stage clock, called after the read ("file_read") and
+    after the walk ("header_walk").  A chunk that ends beyond the file, or headers that do not add up to it, raise ValueError
+    (``who`` and ``chunk_name`` word the message)."""
+    from . import parquet_splice as PS
+    start = col.data_page_offset
+    if col.has_dictionary_page and col.dictionary_page_offset:
+        start = min(start, col.dictionary_page_offset)
+    size = col.total_compressed_size
+    if file is None:
+        with open(path, "rb") as f:
+            f.seek(start)
+            chunk = f.read(size)
+    else:
+        file.seek(start)
+        chunk = file.read(size)
+    if len(chunk) != size:
+        raise ValueError(f"{who}: the {chunk_name} ends beyond the file")
+    if mark is not None:
+        mark("file_read")
+    rows, more, p = [], [], 0
+    while p < size:
+        r = PS._Reader(chunk, p)
+        h = r.struct()
+        v1, v2, dic = PS._get(h, 5), PS._get(h, 8), PS._get(h, 7)
+        body = v1 or v2 or dic or []
+        comp = PS._get(h, 3)
+        rows.append((r.p, comp, PS._get(h, 2), PS._get(body, 1, 0) if (v1 or v2) else 0, PS._get(h, 1),
+                     PS._get(body, 4 if v2 else 2, -1) if body else -1, PS._get(v1, 3, -1) if v1 else -1))
+        more.append((PS._get(dic, 1, 0) if dic else 0, PS._get(v2, 5, 0) if v2 else 0, PS._get(v2, 6, 0) if v2 else 0,
+                     PS._get(v2, 2, 0) if v2 else 0, int(bool(PS._get(v2, 7, True))) if v2 else 1))
+        p = r.p + comp
+    if p != size:
+        raise ValueError(f"{who}: the page headers do not add up to the {chunk_name}")
+    t = np.array(rows, dtype=np.int64).reshape(-1, 7)
+    m = np.array(more, dtype=np.int64).reshape(-1, 5)
+    table = {"start": int(start), "bytes": int(size), "codec": str(col.compression), "pos": t[:, 0], "compressed": t[:, 1],
+             "uncompressed": t[:, 2], "num_values": t[:, 3], "type": t[:, 4], "encoding": t[:, 5], "levels": t[:, 6],
+             "first_row": np.concatenate([[0], np.cumsum(t[:, 3])]), "dict_values": m[:, 0], "def_bytes": m[:, 1], "rep_bytes": m[:, 2],
+             "num_nulls": m[:, 3], "is_compressed": m[:, 4], "chunk": None}
+    if mark is not None:
+        mark("header_walk")
+    return table, chunk
+
+
 def index_reader_route(visibility_info_path: str) -> str:
     """Which reader a builder that uses the index's rows as lists (the depth builders) takes: "lists"
     (``SceneRowGroups.scene_lists``: ``MSPA_VISINDEX_DECODE=device`` and a parquet index) or "handler"
@@ -444,52 +498,15 @@ class SceneRowGroups:
     page_kinds = "plain"
 
     def values_pages(self, g: int) -> dict:
-        """The page table of row group ``g``'s ``values`` column chunk, from the thrift page headers (``parquet_splice._Reader``):
-        ``start`` (the chunk's position in the file), ``bytes`` (its compressed size) and, per page in file order, int64 arrays
-        ``pos`` (the payload's position inside the chunk), ``compressed``, ``uncompressed``, ``num_values``, ``type``,
-        ``encoding`` (-1 where the page has none), ``levels`` (a v1 data page's definition-level encoding, else -1) and
-        ``first_row`` (rows of the group in front of it; ``n_pages + 1`` entries), ``codec`` (the chunk's, as pyarrow names it);
-        ``dict_values`` (a dictionary page's entry count, else 0 -- ``num_values`` stays 0 there: a dictionary page holds no
-        row) and, for v2 data pages, ``def_bytes`` / ``rep_bytes`` (the level bytes that lie uncompressed in front of the
-        values), ``num_nulls`` and ``is_compressed`` (0 / 0 / 0 / 1 for every other page).  Cached: a few numbers per page."""
+        """The page table of row group ``g``'s ``values`` column chunk: ``column_chunk_pages``' table (which see), with the
+        chunk's bytes under ``chunk`` at the call that walks the headers.  Cached: a few numbers per page, not the bytes."""
         if g in self._page_tables:
             return self._page_tables[g]
-        from . import parquet_splice as PS
         if self._path is None:
             raise ValueError("visindex: the page table needs the index as a file on disk")
-        col = self.file.metadata.row_group(g).column(self._values_col)
-        start = col.data_page_offset
-        if col.has_dictionary_page and col.dictionary_page_offset:
-            start = min(start, col.dictionary_page_offset)
-        size = col.total_compressed_size
-        with open(self._path, "rb") as f:
-            f.seek(start)
-            chunk = f.read(size)
-        if len(chunk) != size:
-            raise ValueError("visindex: the values chunk ends beyond the file")
-        self._mark("file_read")
-        rows, more, p = [], [], 0
-        while p < size:
-            r = PS._Reader(chunk, p)
-            h = r.struct()
-            v1, v2, dic = PS._get(h, 5), PS._get(h, 8), PS._get(h, 7)
-            body = v1 or v2 or dic or []
-            comp = PS._get(h, 3)
-            rows.append((r.p, comp, PS._get(h, 2), PS._get(body, 1, 0) if (v1 or v2) else 0, PS._get(h, 1),
-                         PS._get(body, 4 if v2 else 2, -1) if body else -1, PS._get(v1, 3, -1) if v1 else -1))
-            more.append((PS._get(dic, 1, 0) if dic else 0, PS._get(v2, 5, 0) if v2 else 0, PS._get(v2, 6, 0) if v2 else 0,
-                         PS._get(v2, 2, 0) if v2 else 0, int(bool(PS._get(v2, 7, True))) if v2 else 1))
-            p = r.p + comp
-        if p != size:
-            raise ValueError("visindex: the page headers do not add up to the values chunk")
-        t = np.array(rows, dtype=np.int64).reshape(-1, 7)
-        m = np.array(more, dtype=np.int64).reshape(-1, 5)
-        table = {"start": int(start), "bytes": int(size), "codec": str(col.compression), "pos": t[:, 0], "compressed": t[:, 1],
-                 "uncompressed": t[:, 2], "num_values": t[:, 3], "type": t[:, 4], "encoding": t[:, 5], "levels": t[:, 6],
-                 "first_row": np.concatenate([[0], np.cumsum(t[:, 3])]), "dict_values": m[:, 0], "def_bytes": m[:, 1], "rep_bytes": m[:, 2],
-                 "num_nulls": m[:, 3], "is_compressed": m[:, 4], "chunk": None}
+        table, chunk = column_chunk_pages(self._path, self.file.metadata.row_group(g).column(self._values_col), "visindex", "values chunk",
+                                          self._mark)
         self._page_tables[g] = table
-        self._mark("header_walk")
         table = dict(table, chunk=chunk)                      # the bytes go to this caller only: the cache keeps numbers
         return table
 

@@ -43,14 +43,15 @@ def _build_samples(parquet_path, scene_infos, qtype, desired_count, overlap_min,
     launcher) every rank samples the same rows (seeded) and makes every row's draws, formats its own slice of the records
     and rank 0 receives the finished lines (``heads.camera_movement_dataset``); upstream builds them in one loop
     (CME:295-299)."""
-    import pandas as pd
-    from mspa import shard
+    from mspa import pairtable, shard
     ctx = shard.context_from_env()
-    df = pd.read_parquet(parquet_path)
-    print(f"[{tag}: {qtype}] Loaded DF with {len(df)} rows from {parquet_path}")
-    print(f"[{tag}: {qtype}] sampling {desired_count} samples in overlap=[{overlap_min}..{overlap_max}]")
-    df_sampled = sample_dataframe(df, all_overlap_samples=desired_count, non_overlap_samples=0, overlap_min=overlap_min,
-                                  overlap_max=overlap_max, interval=interval)
+
+    def loaded(n_rows):
+        print(f"[{tag}: {qtype}] Loaded DF with {n_rows} rows from {parquet_path}")
+        print(f"[{tag}: {qtype}] sampling {desired_count} samples in overlap=[{overlap_min}..{overlap_max}]")
+    # pd.read_parquet + sample_dataframe, or with MSPA_PAIRTABLE=device the same rows chosen on the GPU
+    df_sampled = pairtable.sampled_rows(parquet_path, desired_count, 0, overlap_min, overlap_max, interval, on_loaded=loaded,
+                                        device=ctx.device if ctx is not None else "cuda")
     print(f"[{tag}: {qtype}] got {len(df_sampled)} sampled rows")
     rows = df_sampled.to_dict("records")          # plain dicts in row order (a pandas Series per row costs ~10 us: 30 s per 3 M rows)
     # one K4 launch for the relative poses of the rows a rank formats, then the records in row order

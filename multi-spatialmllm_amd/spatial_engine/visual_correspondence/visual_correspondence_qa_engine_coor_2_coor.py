@@ -117,14 +117,15 @@ def _build_samples(parquet_path, scene_infos, desired_count, overlap_min, overla
     """(records in row order -- rows without one dropped --, how many there are on every rank, communicator or None).  In a job
     with one process per GPU the scenes of the sampled rows are dealt over the ranks: each reads and uploads only its own
     (``heads.visual_correspondence_dataset``); upstream loops over the rows in one process (VC_C:424-429)."""
-    import pandas as pd
-    from mspa import shard
+    from mspa import pairtable, shard
     ctx = shard.context_from_env()
-    df = pd.read_parquet(parquet_path)
-    print(f"[{tag}] Loaded DataFrame with {len(df)} rows from {parquet_path}")
-    print(f"[{tag}] Sampling {desired_count} samples with overlap in [{overlap_min}, {overlap_max}]")
-    df_sampled = sample_dataframe(df, all_overlap_samples=desired_count, non_overlap_samples=0, overlap_min=overlap_min,
-                                  overlap_max=overlap_max, interval=interval)
+
+    def loaded(n_rows):
+        print(f"[{tag}] Loaded DataFrame with {n_rows} rows from {parquet_path}")
+        print(f"[{tag}] Sampling {desired_count} samples with overlap in [{overlap_min}, {overlap_max}]")
+    # pd.read_parquet + sample_dataframe, or with MSPA_PAIRTABLE=device the same rows chosen on the GPU
+    df_sampled = pairtable.sampled_rows(parquet_path, desired_count, 0, overlap_min, overlap_max, interval, on_loaded=loaded,
+                                        device=ctx.device if ctx is not None else "cuda")
     print(f"[{tag}] Got {len(df_sampled)} sampled rows")
     resident = _ResidentScenes(scene_infos, _load_visibility(visibility_info_path))
 

@@ -88,15 +88,16 @@ def _build(parquet_path, output_dir, scene_infos, desired_count, overlap_min, ov
     with one process per GPU the scenes of the sampled rows are dealt over the ranks (``heads.visual_correspondence_dot_dataset``):
     each rank reads and uploads its own scenes and draws the two annotated JPEGs of its own records -- the expensive part of
     this head; upstream loops over the rows in one process (VC_D:455-466)."""
-    import pandas as pd
     import torch
-    from mspa import shard
+    from mspa import pairtable, shard
     ctx = shard.context_from_env()
-    df = pd.read_parquet(parquet_path)
-    print(f"[{tag}] Loaded DataFrame with {len(df)} rows from {parquet_path}")
-    print(f"[{tag}] Sampling {desired_count} samples with overlap in [{overlap_min}, {overlap_max}]")
-    df_sampled = sample_dataframe(df, all_overlap_samples=desired_count, non_overlap_samples=0, overlap_min=overlap_min,
-                                  overlap_max=overlap_max, interval=interval)
+
+    def loaded(n_rows):
+        print(f"[{tag}] Loaded DataFrame with {n_rows} rows from {parquet_path}")
+        print(f"[{tag}] Sampling {desired_count} samples with overlap in [{overlap_min}, {overlap_max}]")
+    # pd.read_parquet + sample_dataframe, or with MSPA_PAIRTABLE=device the same rows chosen on the GPU
+    df_sampled = pairtable.sampled_rows(parquet_path, desired_count, 0, overlap_min, overlap_max, interval, on_loaded=loaded,
+                                        device=ctx.device if ctx is not None else "cuda")
     print(f"[{tag}] Got {len(df_sampled)} sampled rows")
     image_output_dir = os.path.join(output_dir, "images")
     os.makedirs(image_output_dir, exist_ok=True)
