@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 230            /* 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 240            /* 0.14.0: handler ops on the device: grey decode and Laplacian moments (mspa_jpeg_decode_luma_device, mspa_laplacian_moments_device), exact k-nearest mean distance (mspa_knn_*); 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -1001,6 +1001,47 @@ int mspa_project_samples_ex(const double *xyz, int64_t n_points, int64_t point_s
                             const double *cam_mats, int32_t n_images, const uint16_t *depth, int32_t dh,
                             int32_t dw, int32_t H, int32_t W, double depth_value_scale, const int32_t *samples, int64_t n,
                             double *out_uv, double *out_depth, uint8_t *out_visible, mspa_stream_t stream);
+
+/*
+ * Frame sharpness (the reference's calculate_image_sharpness, OPS:22-34) -- csrc/image_ops.hip.
+ *
+ * mspa_jpeg_decode_luma_device   arguments, workspace (mspa_jpeg_workspace_bytes) and status codes of mspa_jpeg_decode_device,
+ *                                but out_dev[k] is [h, w] uint8: component 0 after the IDCT at the image's size -- libjpeg's
+ *                                JCS_GRAYSCALE output, what cv2.imread(IMREAD_GRAYSCALE) and Pillow's draft("L") return for a
+ *                                baseline greyscale or YCbCr file.
+ * mspa_laplacian_blocks          the number of row blocks B of one [h, w] image (-1: bad size).
+ * mspa_laplacian_moments_device  luma_dev [n, h, w] uint8 -> partials_dev [n, B, 2] int64: per image and row block the sum and
+ *                                the sum of squares of L = I(y-1,x) + I(y+1,x) + I(y,x-1) + I(y,x+1) - 4 I(y,x), borders
+ *                                reflect-101 (cv2.Laplacian(img, CV_64F) with its defaults).  Exact integers, no atomics.
+ */
+int mspa_jpeg_decode_luma_device(const void *src_dev, const int64_t *src_offsets_dev, const int64_t *src_bytes_dev, int64_t src_capacity,
+                                 const void *desc_dev, int64_t n_images, int32_t h, int32_t w, uint8_t *out_dev, int32_t *status_dev,
+                                 void *workspace, int64_t workspace_bytes, mspa_stream_t stream);
+int32_t mspa_laplacian_blocks(int32_t h, int32_t w);
+int mspa_laplacian_moments_device(const uint8_t *luma_dev, int64_t n, int32_t h, int32_t w, int64_t *partials_dev, mspa_stream_t stream);
+
+/*
+ * Exact k-nearest mean distance (the quantity behind Open3D's remove_statistical_outlier, OPS:138-160) -- csrc/cloud_ops.hip,
+ * rule in csrc/knn_grid_core.h.  mean[i] = the mean of the Euclidean distances from point i to its min(k, n) nearest points,
+ * point i itself included at distance 0, summed in ascending order in float64.  1 <= k <= MSPA_KNN_MAX_K, n <= 2^30, finite
+ * coordinates.  The ordering of the points by cell is the caller's sort, so the device form is three calls:
+ *   mspa_knn_grid_host             box lo[3] <= hi[3] (per-axis order statistics of the cloud), n, k -> grid record
+ *                                  (MSPA_KNN_GRID_BYTES, host memory); points outside the box fall into its border cells.
+ *   mspa_knn_cells_device          xyz_dev [n, 3] f64 -> cells_dev [n] int32.  The caller sorts them STABLY and passes the
+ *                                  permutation on as order_dev [n] int64.
+ *   mspa_knn_mean_distance_device  -> mean_dev [n] f64 and, when evals_dev is not null, the distances evaluated per point
+ *                                  [n] int32.  An order_dev that is no such permutation gives wrong means, never an access
+ *                                  outside the buffers.  workspace: mspa_knn_workspace_bytes(n, k), 16-byte aligned.
+ *   mspa_knn_mean_distance_host    the same search on the CPU through the same header (box: ranks n / 100 and n - 1 - n / 100).
+ */
+#define MSPA_KNN_GRID_BYTES 112
+#define MSPA_KNN_MAX_K 64
+int mspa_knn_grid_host(const double *lo, const double *hi, int64_t n, int32_t k, void *grid_out);
+int64_t mspa_knn_workspace_bytes(int64_t n, int32_t k);
+int mspa_knn_cells_device(const double *xyz_dev, int64_t n, const void *grid_host, int32_t *cells_dev, mspa_stream_t stream);
+int mspa_knn_mean_distance_device(const double *xyz_dev, int64_t n, int32_t k, const void *grid_host, const int64_t *order_dev,
+                                  double *mean_dev, int32_t *evals_dev, void *workspace, int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_knn_mean_distance_host(const double *xyz_host, int64_t n, int32_t k, double *mean_host, int32_t *evals_host);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ PAIR_STREAM = 2
 PAIR_WORD_STRIPES = 0x200      # retired: accepted and ignored (the word-stripe kernel it selected was removed)
 CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
 JPEG_DESC_BYTES = 4224
+KNN_GRID_BYTES, KNN_MAX_K = 112, 64      # csrc/knn_grid_core.h: sizeof(Grid), kMaxK
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
@@ -195,6 +196,15 @@ _SIGNATURES = {
     "mspa_pair_partition_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "mspa_track_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                         c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "mspa_jpeg_decode_luma_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                             c_void_p, c_int64, c_void_p]),
+    "mspa_laplacian_blocks": (c_int32, [c_int32, c_int32]),
+    "mspa_laplacian_moments_device": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "mspa_knn_grid_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "mspa_knn_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "mspa_knn_cells_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mspa_knn_mean_distance_device": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_knn_mean_distance_host": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
 }
 
 

@@ -311,6 +311,25 @@ def jpeg_desc_fields(desc: np.ndarray) -> Dict[str, np.ndarray]:
             "qt": d[:, 192:576].view(np.uint16).reshape(-1, 3, 64).copy()}
 
 
+def _jpeg_decode(entry: str, tail: tuple, src, offsets, nbytes, descriptors, hw, out, status):
+    """The two device decodes' shared front: checks, allocation of ``out`` ([n, H, W, *tail]) and ``status``, workspace, the call."""
+    H, W = int(hw[0]), int(hw[1])
+    _require(H > 0 and W > 0, f"hw: a positive (H, W), got {(H, W)}")
+    _check("src", src, torch.uint8, (None,))
+    _require(src.numel() % 4 == 0, f"src: a multiple of 4 bytes long, got {src.numel()}")
+    n = _check_streams(offsets, nbytes)
+    _check("descriptors", descriptors, torch.uint8, (n, _lib.JPEG_DESC_BYTES))
+    out = torch.empty((n, H, W) + tail, dtype=torch.uint8, device=src.device) if out is None else _check("out", out, torch.uint8, ((n,), H, W) + tail)
+    status = torch.empty((n,), dtype=torch.int32, device=src.device) if status is None else _check("status", status, torch.int32, ((n,),))
+    if n == 0:
+        return out, status
+    lib = _lib.load()
+    work = _workspace(int(lib.mspa_jpeg_workspace_bytes(n, H, W)), src.device)
+    _lib.check(getattr(lib, entry)(_ptr(src), _ptr(offsets), _ptr(nbytes), int(src.numel()), _ptr(descriptors), n, H, W,
+                                   _ptr(out), _ptr(status), _ptr(work), int(work.numel()), _stream_ptr()))
+    return out, status
+
+
 def jpeg_decode_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, descriptors: torch.Tensor, hw: Tuple[int, int],
                        out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
     """``len(offsets)`` JPEG payloads resident on the device -- payload k = ``src[offsets[k] : offsets[k] + nbytes[k]]`` (uint8,
@@ -318,21 +337,88 @@ def jpeg_decode_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.T
     uint8) decoded into ``out[k]`` = [H, W, 3] uint8 RGB (mspa_jpeg_decode_device; replaces the per-frame cv2.imread /
     Pillow decode of the colour frames).  Returns (out, status): status 0 = bit-identical to libjpeg-turbo's decode;
     anything else = decode that frame on the host.  Only enqueues; read ``status`` after a synchronisation."""
-    H, W = int(hw[0]), int(hw[1])
-    _require(H > 0 and W > 0, f"hw: a positive (H, W), got {(H, W)}")
-    _check("src", src, torch.uint8, (None,))
-    _require(src.numel() % 4 == 0, f"src: a multiple of 4 bytes long, got {src.numel()}")
-    n = _check_streams(offsets, nbytes)
-    _check("descriptors", descriptors, torch.uint8, (n, _lib.JPEG_DESC_BYTES))
-    out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=src.device) if out is None else _check("out", out, torch.uint8, ((n,), H, W, 3))
-    status = torch.empty((n,), dtype=torch.int32, device=src.device) if status is None else _check("status", status, torch.int32, ((n,),))
-    if n == 0:
-        return out, status
+    return _jpeg_decode("mspa_jpeg_decode_device", (3,), src, offsets, nbytes, descriptors, hw, out, status)
+
+
+def jpeg_decode_luma_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torch.Tensor, descriptors: torch.Tensor, hw: Tuple[int, int],
+                            out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+    """``jpeg_decode_device`` for the grey image alone: ``out[k]`` = [H, W] uint8, component 0 after the IDCT
+    (mspa_jpeg_decode_luma_device) -- what ``cv2.imread(path, IMREAD_GRAYSCALE)`` and Pillow's ``draft("L")`` return for a
+    baseline JPEG.  Same arguments, same (out, status) contract; only enqueues."""
+    return _jpeg_decode("mspa_jpeg_decode_luma_device", (), src, offsets, nbytes, descriptors, hw, out, status)
+
+
+def laplacian_moments(luma: torch.Tensor) -> torch.Tensor:
+    """[n, H, W] uint8 grey images -> [n, B, 2] int64: per image and block of rows (B = mspa_laplacian_blocks) the sum and the
+    sum of squares of the 4-neighbour Laplacian with reflect-101 borders (mspa_laplacian_moments_device): exact integers,
+    deterministic.  ``laplacian_variance`` turns them into ``cv2.Laplacian(img, cv2.CV_64F).var()``.  Only enqueues."""
+    n, H, W = _check("luma", luma, torch.uint8, (None, None, None)).shape
+    _require(H > 0 and W > 0 and n <= 65535, f"luma: at most 65 535 non-empty images, got {list(luma.shape)}")
     lib = _lib.load()
-    work = _workspace(int(lib.mspa_jpeg_workspace_bytes(n, H, W)), src.device)
-    _lib.check(lib.mspa_jpeg_decode_device(_ptr(src), _ptr(offsets), _ptr(nbytes), int(src.numel()), _ptr(descriptors), n, H, W,
-                                           _ptr(out), _ptr(status), _ptr(work), int(work.numel()), _stream_ptr()))
-    return out, status
+    partials = torch.empty((n, int(lib.mspa_laplacian_blocks(H, W)), 2), dtype=torch.int64, device=luma.device)
+    if n:
+        _lib.check(lib.mspa_laplacian_moments_device(_ptr(luma), n, H, W, _ptr(partials), _stream_ptr()))
+    return partials
+
+
+def laplacian_variance(partials, n_pixels: int) -> np.ndarray:
+    """``laplacian_moments``' output (device tensor or array) for images of ``n_pixels`` pixels -> [n] float64: the exact
+    population variance (N S2 - S1^2) / N^2 from Python integers, rounded once."""
+    p = partials.cpu().numpy() if isinstance(partials, torch.Tensor) else np.asarray(partials)
+    N = int(n_pixels)
+    out = np.empty((p.shape[0],), dtype=np.float64)
+    for i, blocks in enumerate(p.tolist()):
+        s1, s2 = sum(b[0] for b in blocks), sum(b[1] for b in blocks)
+        out[i] = (N * s2 - s1 * s1) / (N * N)
+    return out
+
+
+def _knn_check(xyz_shape, k: int) -> int:
+    k = int(k)
+    _require(1 <= k <= _lib.KNN_MAX_K, f"k: between 1 and {_lib.KNN_MAX_K}, got {k}")
+    _require(xyz_shape[0] <= 1 << 30, f"xyz: at most 2^30 points, got {xyz_shape[0]}")
+    return k
+
+
+def knn_mean_distance(xyz: torch.Tensor, k: int, want_evals: bool = False):
+    """[N, 3] float64 finite points -> [N] float64: the mean Euclidean distance from each point to its min(k, N) nearest points,
+    itself included at distance 0, summed in ascending order (what Open3D's ``SearchKNN`` on the cloud's own tree returns);
+    exact search over a uniform grid (csrc/knn_grid_core.h, mspa_knn_mean_distance_device).  With ``want_evals`` also [N]
+    int32, the distances each point evaluated.  The grid's box is the per-axis order statistics of rank N // 100 and
+    N - 1 - N // 100, read back from a device sort: synchronises once."""
+    N = _check("xyz", xyz, torch.float64, (None, 3)).shape[0]
+    k = _knn_check(xyz.shape, k)
+    mean = torch.empty((N,), dtype=torch.float64, device=xyz.device)
+    evals = torch.empty((N,), dtype=torch.int32, device=xyz.device) if want_evals else None
+    if N:
+        lib = _lib.load()
+        r = N // 100
+        box = torch.sort(xyz, dim=0).values[[r, N - 1 - r]].cpu().numpy()
+        _require(bool(np.isfinite(box).all()), "xyz: finite coordinates")
+        box = np.ascontiguousarray(box, dtype=np.float64)
+        grid = np.zeros((_lib.KNN_GRID_BYTES,), dtype=np.uint8)
+        _lib.check(lib.mspa_knn_grid_host(box[0].ctypes.data, box[1].ctypes.data, N, k, grid.ctypes.data))
+        cells = torch.empty((N,), dtype=torch.int32, device=xyz.device)
+        _lib.check(lib.mspa_knn_cells_device(_ptr(xyz), N, grid.ctypes.data, _ptr(cells), _stream_ptr()))
+        order = torch.sort(cells, stable=True).indices
+        work = _workspace(int(lib.mspa_knn_workspace_bytes(N, k)), xyz.device)
+        _lib.check(lib.mspa_knn_mean_distance_device(_ptr(xyz), N, k, grid.ctypes.data, _ptr(order), _ptr(mean), _ptr(evals),
+                                                     _ptr(work), int(work.numel()), _stream_ptr()))
+    return (mean, evals) if want_evals else mean
+
+
+def knn_mean_distance_host(xyz, k: int, want_evals: bool = False):
+    """``knn_mean_distance`` on the CPU for a NumPy [N, 3] cloud: the same grid walk through the same header
+    (mspa_knn_mean_distance_host).  The device's twin for tests on a machine without a GPU, not a fallback."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"mspa.engine: xyz: expected [N, 3], got {list(xyz.shape)}")
+    k = _knn_check(xyz.shape, k)
+    mean = np.empty((xyz.shape[0],), dtype=np.float64)
+    evals = np.empty((xyz.shape[0],), dtype=np.int32) if want_evals else None
+    _lib.check(_lib.load().mspa_knn_mean_distance_host(xyz.ctypes.data, xyz.shape[0], k, mean.ctypes.data,
+                                                       evals.ctypes.data if want_evals else None))
+    return (mean, evals) if want_evals else mean
 
 
 JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}

@@ -341,3 +341,90 @@ def read_color_frames_device(paths: Sequence[str], device="cuda", n_threads: int
         return decode_jpegs_device(stage, offsets, sizes, device, lambda k: reader(paths[k]))
     finally:
         PINNED_POOL.give(stage)
+
+
+def _pillow_grey(source) -> np.ndarray:
+    """[H, W] uint8 of a file (path or bytes) on the host.  A JPEG is decoded with ``draft("L")``: libjpeg's own greyscale
+    output, component 0, which is what ``cv2.imread(path, IMREAD_GRAYSCALE)`` returns.  Any other format goes through
+    ``Image.convert("L")`` -- Pillow's grey rule (ITU-R 601-2 luma, its own rounding), not cv2's."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(source) if isinstance(source, (bytes, bytearray, memoryview)) else source) as im:
+        if im.format == "JPEG":
+            im.draft("L", im.size)
+        return np.ascontiguousarray(np.asarray(im.convert("L")))
+
+
+def image_sharpness(paths: Sequence[str], device="cuda", n_threads: int = 8, max_batch: int = 1024) -> np.ndarray:
+    """[F] float64: the variance of the Laplacian of each file's grey image -- ``cv2.Laplacian(cv2.imread(path,
+    IMREAD_GRAYSCALE), CV_64F).var()``, the reference's ``calculate_image_sharpness`` -- batched.  The headers are parsed on
+    the host and the files grouped by shape; per shape (``max_batch`` files at a time) one H2D copy carries the compressed
+    bytes, one call decodes the grey planes on the device (mspa_jpeg_decode_luma_device) and one takes the Laplacian's
+    moments (mspa_laplacian_moments_device: exact integers); the variance is the exact (N S2 - S1^2) / N^2, rounded once.  A
+    JPEG the parser or the device declines (progressive, damaged) is decoded by Pillow's ``draft("L")`` on the host and scored
+    by the same kernel; a file that is no JPEG goes through ``Image.convert("L")`` (Pillow's grey rule, not cv2's).  A file
+    that cannot be read raises ``ValueError("Unable to read image from: ...")`` as upstream."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from . import engine
+    paths = list(paths)
+    F = len(paths)
+    scores = np.zeros((F,), dtype=np.float64)
+    if F == 0:
+        return scores
+    dev = torch.device(device)
+
+    def load(p):
+        try:
+            with open(p, "rb") as f:
+                return f.read()
+        except (OSError, TypeError):
+            raise ValueError(f"Unable to read image from: {p}") from None
+    with ThreadPoolExecutor(max_workers=max(1, int(n_threads))) as pool:
+        payloads = list(pool.map(load, paths))
+    desc, st = engine.jpeg_parse_host(payloads)
+    fields = engine.jpeg_desc_fields(desc)
+    host: dict = {}                                   # shape -> [(file, grey image)]: what the device does not decode
+
+    def decode_on_host(k):
+        try:
+            img = _pillow_grey(payloads[k])
+        except Exception:
+            raise ValueError(f"Unable to read image from: {paths[k]}") from None
+        host.setdefault(img.shape, []).append((k, img))
+
+    def score(luma, files):
+        scores[files] = engine.laplacian_variance(engine.laplacian_moments(luma), luma.shape[1] * luma.shape[2])
+
+    groups: dict = {}
+    for k in range(F):
+        if st[k] == 0:
+            groups.setdefault((int(fields["h"][k]), int(fields["w"][k])), []).append(k)
+        else:
+            decode_on_host(k)
+    for (H, W), members in groups.items():
+        for b in range(0, len(members), max(1, int(max_batch))):
+            files = np.array(members[b:b + max(1, int(max_batch))], dtype=np.int64)
+            sizes = np.array([len(payloads[k]) for k in files], dtype=np.int64)
+            offsets = np.zeros(len(files), dtype=np.int64)
+            offsets[1:] = np.cumsum((sizes[:-1] + 15) // 16 * 16)
+            stage = np.zeros((int(offsets[-1] + (sizes[-1] + 15) // 16 * 16),), dtype=np.uint8)
+            for o, k in zip(offsets, files):
+                stage[int(o):int(o) + len(payloads[k])] = np.frombuffer(payloads[k], dtype=np.uint8)
+            luma, status = engine.jpeg_decode_luma_device(torch.from_numpy(stage).to(dev), torch.from_numpy(offsets).to(dev),
+                                                          torch.from_numpy(sizes).to(dev), torch.from_numpy(desc[files]).to(dev), (H, W))
+            ok = status.cpu().numpy() == 0
+            if ok.all():
+                score(luma, files)
+            else:
+                if ok.any():
+                    score(luma[torch.from_numpy(ok).to(dev)].contiguous(), files[ok])
+                for k in files[~ok]:
+                    decode_on_host(int(k))
+    for shape, members in host.items():
+        if len(shape) != 2 or shape[0] == 0 or shape[1] == 0:
+            raise ValueError(f"Unable to read image from: {paths[members[0][0]]}")
+        for b in range(0, len(members), max(1, int(max_batch))):
+            part = members[b:b + max(1, int(max_batch))]
+            score(torch.from_numpy(np.stack([img for _k, img in part])).to(dev), np.array([k for k, _img in part], dtype=np.int64))
+    return scores

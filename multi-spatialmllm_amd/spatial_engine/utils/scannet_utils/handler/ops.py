@@ -1,12 +1,158 @@
-"""Mirror of the reference's handler/ops.py for the one function on the hot path."""
+"""Mirror of the reference's handler/ops.py: the object-cloud tool chain mask -> cloud (``project_mask_to_3d``, kernel K3) ->
+cleaned cloud (``remove_statistical_outliers``: exact k-nearest search on the device; ``remove_truncated_outliers``) -> box
+(``calculate_aabb``, ``convert_to_corners``) -> IoU (``calculate_iou_3d``, ``calculate_iou_2d``), and the frame filter
+(``filter_images_laplacian``, ``calculate_image_sharpness``: grey decode and Laplacian moments on the device).  NumPy in gives
+NumPy out; a device tensor in gives a device tensor out."""
 from __future__ import annotations
+
+from typing import List
 
 import numpy as np
 import torch
 
-from mspa import engine
+from mspa import engine, ingest
 
 from ._images import read_color_rgb, read_depth
+
+__all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
+           "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
+
+
+def _same_device(a, b):
+    """Two arguments of which at least one is a tensor, both as tensors where the device tensor lives."""
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    dev = a.device if a.is_cuda else b.device
+    return a.to(dev), b.to(dev)
+
+
+def filter_images_laplacian(image_paths, threshold=100):
+    """The paths whose sharpness score is at least ``threshold``, in their order (OPS:14-19); one batched call scores them all."""
+    image_paths = list(image_paths)
+    scores = ingest.image_sharpness(image_paths)
+    return [p for p, s in zip(image_paths, scores) if s >= threshold]
+
+
+def calculate_image_sharpness(image_path):
+    """Variance of the Laplacian of the file's grey image (OPS:22-34): ``mspa.ingest.image_sharpness`` of one file.  The value
+    is the exact population variance rounded once; upstream's ``laplacian.var()`` is within a few ulps of it.  An unreadable
+    file raises ``ValueError("Unable to read image from: ...")``."""
+    return np.float64(ingest.image_sharpness([image_path])[0])
+
+
+def convert_to_corners(bounding_boxes) -> List[np.ndarray]:
+    """Per box [cx, cy, cz, dx, dy, dz, ...] its eight corners, [8, 3] float32 (OPS:37-94): corner j takes +d/2 on x where bit 0 of
+    j is set, on y where bit 1 is, on z where bit 2 is, and -d/2 elsewhere.  Each coordinate is formed in the box's own
+    precision and then narrowed, as upstream's array literal does.  Device boxes give device corners."""
+    corners = []
+    for bbox in bounding_boxes:
+        if isinstance(bbox, torch.Tensor):
+            sign = torch.tensor([[1 if j >> a & 1 else -1 for a in range(3)] for j in range(8)], dtype=bbox.dtype, device=bbox.device)
+            half = bbox[3:6] / 2
+            plus, minus = bbox[:3] + half, bbox[:3] - half
+            corners.append(torch.where(sign > 0, plus[None, :], minus[None, :]).to(torch.float32))
+        else:
+            rows = [[bbox[a] + bbox[3 + a] / 2 if j >> a & 1 else bbox[a] - bbox[3 + a] / 2 for a in range(3)] for j in range(8)]
+            corners.append(np.array(rows, dtype=np.float32))
+    return corners
+
+
+def calculate_iou_2d(mask1, mask2):
+    """Intersection over union of two binary masks (OPS:97-111); 0.0 when the union is empty."""
+    if isinstance(mask1, torch.Tensor) or isinstance(mask2, torch.Tensor):
+        a, b = _same_device(mask1, mask2)
+        union = (a.bool() | b.bool()).sum()
+        return torch.where(union != 0, (a.bool() & b.bool()).sum() / union.clamp(min=1), torch.zeros_like(union, dtype=torch.float32))
+    union = np.sum(np.logical_or(mask1, mask2))
+    if union == 0:
+        return 0.0
+    return np.sum(np.logical_and(mask1, mask2)) / union
+
+
+def calculate_iou_3d(box1, box2):
+    """Intersection over union of two axis-aligned boxes [x, y, z, dx, dy, dz] (OPS:114-135); the intersection counts only
+    when it is positive along every axis."""
+    if isinstance(box1, torch.Tensor) or isinstance(box2, torch.Tensor):
+        box1, box2 = _same_device(box1, box2)
+        dim = torch.minimum(box1[:3] + box1[3:] / 2, box2[:3] + box2[3:] / 2) - torch.maximum(box1[:3] - box1[3:] / 2, box2[:3] - box2[3:] / 2)
+        inter = torch.where((dim > 0).all(), dim.prod(), torch.zeros((), dtype=dim.dtype, device=dim.device))
+        return inter / (box1[3:].prod() + box2[3:].prod() - inter)
+    dim = np.minimum(box1[:3] + box1[3:] / 2, box2[:3] + box2[3:] / 2) - np.maximum(box1[:3] - box1[3:] / 2, box2[:3] - box2[3:] / 2)
+    inter = np.prod(dim) if np.all(dim > 0) else 0
+    return inter / (np.prod(box1[3:]) + np.prod(box2[3:]) - inter)
+
+
+def remove_statistical_outliers(point_cloud_data, nb_neighbors=20, std_ratio=1.0):
+    """[N, C >= 3] cloud -> the rows Open3D's ``remove_statistical_outlier(nb_neighbors, std_ratio)`` keeps, all columns, the
+    input's dtype, ascending row order (OPS:138-160).  The rule, as restated here (Open3D is not a dependency):
+      avg[i] = mean distance from point i to its min(nb_neighbors, N) nearest points, itself included (exact search on the
+               device, ``mspa.engine.knn_mean_distance``);
+      mean = (sum of the positive avg) / N;  sd = sqrt(sum over the positive avg of (avg - mean)^2 / (N - 1));
+      row i stays iff 0 < avg[i] < mean + std_ratio * sd.
+    N = 0 and N = 1 (a 0 / 0 threshold) give an empty result.  ``nb_neighbors < 1`` or ``std_ratio <= 0`` raises RuntimeError,
+    as Open3D does.  Deviations: non-finite coordinates raise ValueError, and ``nb_neighbors > 64`` raises
+    NotImplementedError (the kernel keeps at most 64 candidates per point)."""
+    if nb_neighbors < 1 or std_ratio <= 0:
+        raise RuntimeError("remove_statistical_outliers: nb_neighbors must be at least 1 and std_ratio positive "
+                           f"(got {nb_neighbors}, {std_ratio})")
+    if nb_neighbors > engine._lib.KNN_MAX_K:
+        raise NotImplementedError(f"remove_statistical_outliers: nb_neighbors is limited to {engine._lib.KNN_MAX_K} "
+                                  f"(got {nb_neighbors})")
+    is_tensor = isinstance(point_cloud_data, torch.Tensor)
+    data = point_cloud_data if is_tensor else np.asarray(point_cloud_data)
+    n = int(data.shape[0])
+    if n == 0:
+        return data[:0, :]
+    xyz = (data[:, :3] if is_tensor else torch.from_numpy(np.ascontiguousarray(data[:, :3]))).to("cuda", torch.float64).contiguous()
+    if not bool(torch.isfinite(xyz).all()):
+        raise ValueError("remove_statistical_outliers: the cloud has non-finite coordinates")
+    avg = engine.knn_mean_distance(xyz, int(nb_neighbors))
+    pos = avg > 0
+    zero = torch.zeros((), dtype=torch.float64, device=avg.device)
+    mean = torch.where(pos, avg, zero).sum() / n
+    dev = avg - mean
+    sd = torch.sqrt(torch.where(pos, dev * dev, zero).sum() / (n - 1))             # n = 1: 0 / 0, nothing passes
+    ind = torch.nonzero(pos & (avg < mean + std_ratio * sd)).flatten()
+    from .info_handler import _like                 # (info_handler imports this module: not at the top)
+    ind = _like(ind, point_cloud_data)
+    return data[ind.to(data.device) if is_tensor else ind, :]
+
+
+def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
+    """Drop, per axis, the ``int(t * N)`` rows with the smallest and the largest coordinate, and keep the rows that survive on
+    all three axes, in ascending row order (OPS:163-208).  Which of several equal coordinates goes is ``np.argsort``'s
+    choice, so NumPy input is ranked by NumPy itself and the result is upstream's by construction; a device tensor is ranked
+    by ``torch.argsort(stable=True)``.  Upstream's quirks stay: all-zero ratios return the input itself, and a zero count on
+    one axis next to a non-zero ratio elsewhere selects ``[0:-0]``, nothing."""
+    assert tx < 0.5 and ty < 0.5 and tz < 0.5, "tx, ty, tz must be less than 0.5."
+    n = len(point_cloud_data)
+    if tx == 0 and ty == 0 and tz == 0:
+        return point_cloud_data
+    if isinstance(point_cloud_data, torch.Tensor):
+        keep = torch.ones((n,), dtype=torch.bool, device=point_cloud_data.device)
+        for axis, t in enumerate((tx, ty, tz)):
+            cut = int(t * n)
+            ranked = torch.argsort(point_cloud_data[:, axis], stable=True)
+            inside = torch.zeros_like(keep)
+            if 2 * cut < n:
+                inside[ranked[cut:-cut]] = True
+            keep &= inside
+        return point_cloud_data[keep]
+    valid = None
+    for axis, t in enumerate((tx, ty, tz)):
+        cut = int(t * n)
+        ranked = np.argsort(point_cloud_data[:, axis])
+        inside = ranked[cut:-cut] if 2 * cut < n else np.array([])
+        valid = inside if valid is None else np.intersect1d(valid, inside)
+    return point_cloud_data[valid]
+
+
+def calculate_aabb(point_cloud_data):
+    """[N, C >= 3] cloud -> [cx, cy, cz, dx, dy, dz]: centre and size of its axis-aligned bounding box (OPS:211-232)."""
+    if isinstance(point_cloud_data, torch.Tensor):
+        lo, hi = point_cloud_data[:, :3].min(dim=0).values, point_cloud_data[:, :3].max(dim=0).values
+        return torch.cat([(hi + lo) / 2, hi - lo])
+    lo, hi = np.min(point_cloud_data[:, :3], axis=0), np.max(point_cloud_data[:, :3], axis=0)
+    return np.concatenate([(hi + lo) / 2, hi - lo])
 
 
 def project_mask_to_3d(depth_image, intrinsic_matrix, extrinsic_matrix, mask=None,
