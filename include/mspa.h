@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 240            /* 0.14.0: handler ops on the device: grey decode and Laplacian moments (mspa_jpeg_decode_luma_device, mspa_laplacian_moments_device), exact k-nearest mean distance (mspa_knn_*); 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 250            /* 0.15.0: pair mining of the object-movement head on the device (mspa_track_pair_stats / _bin_counts / _sort / _order / _resolve); 0.14.0: handler ops on the device: grey decode and Laplacian moments (mspa_jpeg_decode_luma_device, mspa_laplacian_moments_device), exact k-nearest mean distance (mspa_knn_*); 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -922,6 +922,53 @@ int mspa_track_displacement(const double *world, const double *w2c, const double
 int mspa_track_pair_distances(const double *world, int32_t T, int32_t P, const int32_t *points,
                               const int32_t *frame_offsets, const int32_t *frames, int32_t n_selected,
                               int32_t n_frames_max, const int64_t *out_offsets, double *out, mspa_stream_t stream);
+
+/*
+ * K5d -- the pair mining itself (OM_C:465-567) on the device: csrc/track_mining.hip, rule in csrc/track_mining_core.h.  The
+ * draws stay on the host (mspa/heads.py: plan_track_draws); the device counts, orders and resolves.  For a point, `frames` is
+ * the ascending list of the frames it is visible in (V of them) and its pairs are (i, j), i < j, in row-major order, with K5c's
+ * distance d.  A pair is dropped when (double)frames[i] > d + future_frame_windows (OM_C:505-507 as written), else static when
+ * d < object_not_moving_threshold, else moving.  T <= 65535 throughout.
+ *
+ *   mspa_track_pair_stats       world [T, P, 3] f64, visibility [T, P] u8, points [n_points] i32 -> out_frames [n_points, T] i32
+ *                               and out_positions [n_points, T, 3] f64 (the first V entries of a row), out_stats
+ *                               [n_points, MSPA_TRACK_STAT_WORDS] i64: V, static pairs, moving pairs, the bit patterns of the
+ *                               smallest and the largest moving distance, flags (1: a moving distance is not finite, 2: the point
+ *                               lies outside the track).  The three outputs are what the calls below read.
+ *   mspa_track_pair_bin_counts  edges [n_points, 11] f64 -> out_bin_counts [n_points, 10] i32 of the moving pairs, bin =
+ *                               min(#{e : e <= d} - 1, 9) (np.digitize, then min(.., 9)).
+ *   mspa_track_pair_sort        the segmented sort on its own: segment s is [seg_offsets[s], seg_offsets[s+1]) of keys
+ *                               [2, n_total] u64 and payload [2, n_total] u32 (row 0 holds the data and the result, row 1 is the
+ *                               other half of the ping-pong), each segment shorter than 2^31, sorted by (key, payload).
+ *                               payload_ordered != 0: every segment ascends in its payload already, so only the key is sorted.
+ *   mspa_track_pair_order       rows [n_selected] i32 (rows of the statistics), seg_offsets [n_selected + 1] i64 with segment
+ *                               lengths = the rows' moving counts -> every selected point's moving pairs in keys / payload as
+ *                               above: key = the bits of d, payload = (i << 16) | j, sorted by (key, payload).
+ *   mspa_track_pair_resolve     picks [n_picks, 3] i32 (selected point, class, rank; class 0..9 a bin, 10 the static pairs) ->
+ *                               out_frame_pairs [n_picks, 2] i32 (frames[i], frames[j]).  A bin pick is entry (bin start + rank) of
+ *                               the point's sorted segment, a static pick the rank-th static pair in row-major order.  picks_host
+ *                               is the same table in host memory and class_counts_host [n_selected, 11] i32 the classes' sizes:
+ *                               a pick outside them is MSPA_EINVAL, and nothing is launched.
+ */
+#define MSPA_TRACK_STAT_WORDS 6
+#define MSPA_TRACK_CLASS_STATIC 10
+int mspa_track_pair_stats(const double *world, const uint8_t *visibility, int32_t T, int32_t P, const int32_t *points,
+                          int32_t n_points, double object_not_moving_threshold, double future_frame_windows,
+                          int32_t *out_frames, double *out_positions, int64_t *out_stats, mspa_stream_t stream);
+int mspa_track_pair_bin_counts(const int32_t *frames, const double *positions, const int64_t *stats, int32_t T, int32_t n_points,
+                               const double *edges, double object_not_moving_threshold, double future_frame_windows,
+                               int32_t *out_bin_counts, mspa_stream_t stream);
+int mspa_track_pair_sort(uint64_t *keys, uint32_t *payload, const int64_t *seg_offsets, int64_t n_segments, int64_t n_total,
+                         int32_t payload_ordered, mspa_stream_t stream);
+int mspa_track_pair_order(const int32_t *frames, const double *positions, const int64_t *stats, int32_t T, int32_t n_points,
+                          const int32_t *rows, const int64_t *seg_offsets, int32_t n_selected, int64_t n_total,
+                          double object_not_moving_threshold, double future_frame_windows, uint64_t *keys, uint32_t *payload,
+                          mspa_stream_t stream);
+int mspa_track_pair_resolve(const int32_t *frames, const double *positions, const int64_t *stats, const int32_t *bin_counts, int32_t T,
+                            int32_t n_points, const int32_t *rows, const int64_t *seg_offsets, int32_t n_selected,
+                            const uint32_t *payload, int64_t n_total, const int32_t *picks_host, const int32_t *class_counts_host,
+                            const int32_t *picks, int64_t n_picks, double object_not_moving_threshold, double future_frame_windows,
+                            int32_t *out_frame_pairs, mspa_stream_t stream);
 
 /*
  * K7 -- the accumulation inside rigid_body_segmentation (OM_C:49-92): cumulative_loss[i, j] = sum over

@@ -36,6 +36,10 @@ PAIR_CLASS_ZERO, PAIR_CLASS_DROPPED, PAIR_MAX_BINS, PAIR_CLASSES = 254, 255, 250
 PAGE_LEVELS_INLINE, PAGE_DICT_CODED, PAGE_LEVELS_GIVEN = 1, 2, 4
 LAYOUT_LEVEL_OFFSET, LAYOUT_LEVEL_BYTES, LAYOUT_VALUE_OFFSET, LAYOUT_VALUE_BYTES, LAYOUT_BIT_WIDTH, LAYOUT_ROWS = range(6)
 LINKAGE_OK, LINKAGE_NONFINITE, LINKAGE_ITERATION_CAP = 0, 1, 2
+# csrc/track_mining_core.h: a point's statistics record, its flags, the classes of a pick and the longest track
+TRACK_STAT_V, TRACK_STAT_STATIC, TRACK_STAT_MOVING, TRACK_STAT_MIN_BITS, TRACK_STAT_MAX_BITS, TRACK_STAT_FLAGS, TRACK_STAT_WORDS = range(7)
+TRACK_FLAG_NONFINITE, TRACK_FLAG_BAD_POINT = 1, 2
+TRACK_BINS, TRACK_CLASS_STATIC, TRACK_CLASSES, TRACK_MAX_FRAMES = 10, 10, 11, 65535
 KERNEL_NONE, KERNEL_PAIR_EXACT, KERNEL_PAIR_FAST, KERNEL_PAIR_FAST_LINEAR, KERNEL_PAIR_FAST_TIGHT, KERNEL_PAIR_FAST_SCALED, KERNEL_PAIR_FAST_RECT = range(7)   # KERNEL_PAIR_FAST_SCALED (5): retired id, never reported
 
 
@@ -147,6 +151,15 @@ _SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "mspa_track_pair_distances": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                           c_void_p, c_void_p, c_void_p]),
+    "mspa_track_pair_stats": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_double, c_double, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "mspa_track_pair_bin_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_double, c_double, c_void_p,
+                                           c_void_p]),
+    "mspa_track_pair_sort": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+    "mspa_track_pair_order": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64, c_double,
+                                      c_double, c_void_p, c_void_p, c_void_p]),
+    "mspa_track_pair_resolve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
     "mspa_track_rigidity_loss": (c_int, [c_void_p, c_int32, c_int32, c_double, c_void_p, c_void_p]),
     "mspa_track_rigidity_loss_batch": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p]),
     "mspa_track_linkage_workspace_bytes": (c_int64, [c_int64, c_int32]),

@@ -1750,6 +1750,115 @@ def track_pair_distances(world: torch.Tensor, points: Sequence[int], visible_fra
     return [host[o_off[s]:o_off[s + 1]] for s in range(S)]
 
 
+# ---- K5d: the pair mining of the object-movement head (csrc/track_mining.hip) -----------------------------------------------------------
+
+TRACK_MINING_BUDGET_BYTES = 1 << 30      # (key, payload) ping-pong of the selected points ordered in one launch: 24 B per moving pair
+TRACK_MINING_PAIR_BYTES = 24
+
+
+def track_mining_backend() -> str:
+    """Where ``heads.object_movement_mine_pairs`` classifies, orders and picks a scene's frame pairs: "host" (default: K5c's
+    distances downloaded, NumPy on them) or "device" (``MSPA_TRACK_MINING=device``: K5d, the same pairs and draws).  Read at
+    every call."""
+    value = os.environ.get("MSPA_TRACK_MINING", "host").strip().lower() or "host"
+    if value not in ("host", "device"):
+        raise ValueError(f"MSPA_TRACK_MINING={value!r}: expected 'host' or 'device'")
+    return value
+
+
+def track_pair_stats(world: torch.Tensor, visibility: torch.Tensor, points: torch.Tensor, object_not_moving_threshold: float = 0.01,
+                     future_frame_windows: float = 1e8) -> Dict[str, torch.Tensor]:
+    """Enqueue K5d's statistics.  world [T,P,3] f64 (K5a), visibility [T,P] u8, points [n] i32 -> the state the other three calls
+    read: ``frames`` [n,T] i32 and ``positions`` [n,T,3] f64 (a point's visible frames and its positions there: the first V of a
+    row) and ``stats`` [n,6] i64 (``_lib.TRACK_STAT_*``: V, static and moving pairs, the bits of the smallest and the largest
+    moving distance, flags)."""
+    T, P = _check_tracks("world", world)
+    _require(T <= _lib.TRACK_MAX_FRAMES, f"world: at most {_lib.TRACK_MAX_FRAMES} frames, got {T}")
+    _check("visibility", visibility, torch.uint8, (T, P))
+    n = _check("points", points, torch.int32, (None,)).shape[0]
+    dev = world.device
+    state = {"frames": torch.empty((n, T), dtype=torch.int32, device=dev), "positions": torch.empty((n, T, 3), dtype=torch.float64, device=dev),
+             "stats": torch.empty((n, _lib.TRACK_STAT_WORDS), dtype=torch.int64, device=dev)}
+    _lib.check(_lib.load().mspa_track_pair_stats(_ptr(world), _ptr(visibility), T, P, _ptr(points), n, float(object_not_moving_threshold),
+                                                 float(future_frame_windows), _ptr(state["frames"]), _ptr(state["positions"]),
+                                                 _ptr(state["stats"]), _stream_ptr()))
+    return state
+
+
+def _check_track_state(state) -> Tuple[int, int]:
+    """What ``track_pair_stats`` returned -> (n, T)."""
+    _require(isinstance(state, dict) and {"frames", "positions", "stats"} <= set(state), "state: the dict track_pair_stats returned")
+    n, T = _check("state[frames]", state["frames"], torch.int32, (None, None)).shape
+    _check("state[positions]", state["positions"], torch.float64, (n, T, 3))
+    _check("state[stats]", state["stats"], torch.int64, (n, _lib.TRACK_STAT_WORDS))
+    return n, T
+
+
+def track_pair_bin_counts(state: Dict[str, torch.Tensor], edges: torch.Tensor, object_not_moving_threshold: float = 0.01,
+                          future_frame_windows: float = 1e8) -> torch.Tensor:
+    """Enqueue K5d's second pass: edges [n,11] f64 (``np.histogram_bin_edges`` of each point's smallest and largest moving distance)
+    -> [n,10] i32, the moving pairs per bin (``np.digitize``, then ``min(.., 9)``)."""
+    n, T = _check_track_state(state)
+    _check("edges", edges, torch.float64, (n, _lib.TRACK_BINS + 1))
+    out = torch.empty((n, _lib.TRACK_BINS), dtype=torch.int32, device=edges.device)
+    _lib.check(_lib.load().mspa_track_pair_bin_counts(_ptr(state["frames"]), _ptr(state["positions"]), _ptr(state["stats"]), T, n, _ptr(edges),
+                                                      float(object_not_moving_threshold), float(future_frame_windows), _ptr(out), _stream_ptr()))
+    return out
+
+
+def track_pair_sort(keys: torch.Tensor, payload: torch.Tensor, seg_offsets: torch.Tensor, payload_ordered: bool = False) -> None:
+    """Enqueue K5d's segmented sort on its own, in place: keys [2,N] i64 (bit patterns, compared UNSIGNED) and payload [2,N] i32
+    (likewise); row 0 holds the data and the result, row 1 is scratch.  Segment s is [seg_offsets[s], seg_offsets[s+1]) (i64, on
+    the device), ordered by (key, payload).  ``payload_ordered``: every segment ascends in its payload already."""
+    N = _check("keys", keys, torch.int64, (2, None)).shape[1]
+    _check("payload", payload, torch.int32, (2, N))
+    n_seg = _check("seg_offsets", seg_offsets, torch.int64, ((1,),)).shape[0] - 1
+    _lib.check(_lib.load().mspa_track_pair_sort(_ptr(keys), _ptr(payload), _ptr(seg_offsets), n_seg, N, int(bool(payload_ordered)), _stream_ptr()))
+
+
+def track_pair_order(state: Dict[str, torch.Tensor], rows: torch.Tensor, seg_offsets: torch.Tensor, n_total: int,
+                     object_not_moving_threshold: float = 0.01, future_frame_windows: float = 1e8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Enqueue K5d's order: rows [s] i32 (rows of the state: the selected points), seg_offsets [s+1] i64 (running sum of their
+    moving counts, ``n_total`` its last entry) -> (keys [2,n_total] i64, payload [2,n_total] i32); row 0 holds every selected point's
+    moving pairs as (bits of d, (i << 16) | j) in ascending order, row 1 is the sort's scratch."""
+    n, T = _check_track_state(state)
+    s = _check("rows", rows, torch.int32, (None,)).shape[0]
+    _check("seg_offsets", seg_offsets, torch.int64, (s + 1,))
+    n_total = int(n_total)
+    _require(n_total >= 0, f"n_total: not negative, got {n_total}")
+    keys = torch.empty((2, n_total), dtype=torch.int64, device=rows.device)
+    payload = torch.empty((2, n_total), dtype=torch.int32, device=rows.device)
+    _lib.check(_lib.load().mspa_track_pair_order(_ptr(state["frames"]), _ptr(state["positions"]), _ptr(state["stats"]), T, n, _ptr(rows),
+                                                 _ptr(seg_offsets), s, n_total, float(object_not_moving_threshold), float(future_frame_windows),
+                                                 _ptr(keys), _ptr(payload), _stream_ptr()))
+    return keys, payload
+
+
+def track_pair_resolve(state: Dict[str, torch.Tensor], bin_counts: torch.Tensor, rows: torch.Tensor, seg_offsets: torch.Tensor,
+                       payload: torch.Tensor, picks: np.ndarray, class_counts: np.ndarray, object_not_moving_threshold: float = 0.01,
+                       future_frame_windows: float = 1e8) -> torch.Tensor:
+    """Enqueue K5d's resolve: picks [k,3] i32 ON THE HOST (selected point, class 0..9 a bin / 10 static, rank) and class_counts
+    [s,11] i32 on the host (the classes' sizes: a rank outside them is refused before any launch) -> [k,2] i32 (frame1, frame2) on
+    the device.  ``payload`` is ``track_pair_order``'s."""
+    n, T = _check_track_state(state)
+    _check("bin_counts", bin_counts, torch.int32, (n, _lib.TRACK_BINS))
+    s = _check("rows", rows, torch.int32, (None,)).shape[0]
+    _check("seg_offsets", seg_offsets, torch.int64, (s + 1,))
+    n_total = _check("payload", payload, torch.int32, (2, None)).shape[1]
+    picks = np.ascontiguousarray(picks, dtype=np.int32)
+    class_counts = np.ascontiguousarray(class_counts, dtype=np.int32)
+    _require(picks.ndim == 2 and picks.shape[1] == 3, f"picks: a host array [k, 3], got {list(picks.shape)}")
+    _require(class_counts.shape == (s, _lib.TRACK_CLASSES), f"class_counts: a host array [{s}, {_lib.TRACK_CLASSES}], got {list(class_counts.shape)}")
+    k = picks.shape[0]
+    out = torch.empty((k, 2), dtype=torch.int32, device=rows.device)
+    picks_dev = torch.from_numpy(picks).to(rows.device)                    # named: alive until the launch is enqueued
+    _lib.check(_lib.load().mspa_track_pair_resolve(_ptr(state["frames"]), _ptr(state["positions"]), _ptr(state["stats"]), _ptr(bin_counts), T, n,
+                                                   _ptr(rows), _ptr(seg_offsets), s, _ptr(payload), n_total, picks.ctypes.data,
+                                                   class_counts.ctypes.data, _ptr(picks_dev), k, float(object_not_moving_threshold),
+                                                   float(future_frame_windows), _ptr(out), _stream_ptr()))
+    return out
+
+
 # ---- K11: ScanNet instance data from raw scans (csrc/scene_prep.hip) -----------------------------------------------------------------
 
 def _ragged_offsets(counts: Sequence[int]) -> np.ndarray:

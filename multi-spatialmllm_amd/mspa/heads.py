@@ -1121,10 +1121,129 @@ def object_perception_records(dim_info: Dict[str, Dict], dimension_name: str, va
     return by_k
 
 
+TRACK_BINS, TRACK_CLASS_STATIC = 10, 10          # a pick's class: a distance bin 0..9, or the static pairs (csrc/track_mining_core.h)
+TRACK_MAX_FRAMES = 65535
+LAST_TRACK_MINING: Dict[str, str] = {}           # {"path": "host" | "device", "reason": why the host line ran} of the last call
+TRACK_MINING_BACKEND = None                      # the four K5d calls: mspa.engine unless a test puts a stand-in here
+
+
+def _track_mining_backend() -> str:
+    from . import engine
+    return engine.track_mining_backend()
+
+
+def plan_track_draws(groups: Sequence[Sequence[int]], stats: Dict[int, tuple], npoints_per_group: int = 5, npairs_per_bin=1e8,
+                     augment: bool = True, augment_ratio: float = 1.0, rng=_random):
+    """Every draw of ``object_movement_mine_pairs``, made from counts alone, in upstream's order (OM_C:465-567).
+
+    ``stats[point] = (V, n_static, bin_counts)``: the frames the point is visible in, its static pairs and its moving pairs per
+    distance bin (ten counts).  Shuffles ``groups`` in place like the host line and returns ``(picks, swaps)``: picks
+    ``(point, class, rank)`` in output order -- class ``TRACK_CLASS_STATIC`` with the rank among the point's static pairs in
+    row-major order, or a bin 0..9 with the rank inside the bin in (distance, row-major) order -- and the positions of the picks
+    the swap augmentation appends reversed."""
+    picks: List[tuple] = []
+    for group in groups:
+        rng.shuffle(group)                                                   # in place, as upstream (OM_C:468)
+        for point_idx in group[:npoints_per_group]:
+            V, n_static, bin_counts = stats[point_idx]
+            if V < 2:
+                continue
+            if n_static:
+                picks.append((point_idx, TRACK_CLASS_STATIC, int(rng.choice(range(n_static)))))
+            if sum(bin_counts):
+                npairs_per_bin = max(min(int(bin_counts[4]), npairs_per_bin), 1)   # carried over to later points (OM_C:535-537)
+                for b in range(TRACK_BINS):
+                    count = int(bin_counts[b])
+                    ranks = sample_indices(count, int(npairs_per_bin), rng) if count > npairs_per_bin else range(count)
+                    picks.extend((point_idx, b, int(r)) for r in ranks)
+    swaps = sample_indices(len(picks), int(len(picks) * augment_ratio), rng) if augment else []
+    return picks, swaps
+
+
+def _mine_pairs_device(visibility, groups, world, npoints_per_group, npairs_per_bin, augment, augment_ratio, rng,
+                       object_not_moving_threshold, future_frame_windows):
+    """The device line of ``object_movement_mine_pairs``: statistics of every grouped point (two small downloads), the draws on
+    the host, then order + resolve of the selected points (one download).  Returns the list, or -- before any draw -- the reason
+    it declines as a string."""
+    B = TRACK_MINING_BACKEND
+    if B is None:
+        from . import engine as B
+    on_host = isinstance(world, np.ndarray)                                  # a stand-in's world: nothing to upload
+
+    def up(a):
+        if on_host:
+            return a
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to(world.device)
+
+    def down(t):
+        return t if isinstance(t, np.ndarray) else t.cpu().numpy()
+
+    visibility = np.asarray(visibility)
+    T, P = visibility.shape
+    thr, window = float(object_not_moving_threshold), float(future_frame_windows)
+    if T > TRACK_MAX_FRAMES:
+        return f"T = {T} > {TRACK_MAX_FRAMES}"
+    members = sorted({int(p) for g in groups for p in g})
+    if not members:
+        return "empty groups"
+    if members[0] < 0 or members[-1] >= P:
+        return "a point outside the track"
+    row_of = {p: r for r, p in enumerate(members)}
+    # phase 1: every grouped point -- which ones get selected depends on draws, and those on counts
+    state = B.track_pair_stats(world, up((visibility != 0).astype(np.uint8)), up(np.asarray(members, dtype=np.int32)), thr, window)
+    stats = down(state["stats"])
+    V, n_static, n_moving, flags = stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 5]
+    if (flags != 0).any():
+        return "a non-finite distance"                                       # upstream's histogram_bin_edges raises: the host line does
+    if (n_moving * B.TRACK_MINING_PAIR_BYTES > B.TRACK_MINING_BUDGET_BYTES).any():
+        return "a point's segment exceeds the byte budget"
+    lo, hi = stats[:, 3].copy().view(np.float64), stats[:, 4].copy().view(np.float64)
+    edges = np.zeros((len(members), TRACK_BINS + 1))
+    for r in np.nonzero(n_moving)[0]:
+        edges[r] = np.histogram_bin_edges(np.array([lo[r], hi[r]]), bins=TRACK_BINS)   # NumPy's edges read min and max only
+    bin_counts_dev = B.track_pair_bin_counts(state, up(edges), thr, window)
+    bin_counts = down(bin_counts_dev)
+    if not np.array_equal(bin_counts.sum(axis=1), n_moving):
+        raise RuntimeError("track mining: the bin counts do not add up to the moving pairs")
+    # phase 2: the draws
+    per_point = {p: (int(V[r]), int(n_static[r]), bin_counts[r].tolist()) for p, r in row_of.items()}
+    picks, swaps = plan_track_draws(groups, per_point, npoints_per_group, npairs_per_bin, augment, augment_ratio, rng)
+    # phase 3: the distinct picked points, in chunks under the byte budget
+    resolved = np.zeros((len(picks), 2), dtype=np.int64)
+    by_point: Dict[int, List[int]] = {}
+    for k, (p, _c, _r) in enumerate(picks):
+        by_point.setdefault(p, []).append(k)
+    todo = list(by_point)
+    while todo:
+        chunk, pairs = [], 0
+        while todo and (not chunk or (pairs + int(n_moving[row_of[todo[0]]])) * B.TRACK_MINING_PAIR_BYTES <= B.TRACK_MINING_BUDGET_BYTES):
+            pairs += int(n_moving[row_of[todo[0]]])
+            chunk.append(todo.pop(0))
+        rows = np.asarray([row_of[p] for p in chunk], dtype=np.int32)
+        seg = np.zeros(len(chunk) + 1, dtype=np.int64)
+        np.cumsum(n_moving[rows], out=seg[1:])
+        where = [k for p in chunk for k in by_point[p]]
+        local = {p: s for s, p in enumerate(chunk)}
+        table = np.asarray([(local[picks[k][0]], picks[k][1], picks[k][2]) for k in where], dtype=np.int32)
+        classes = np.concatenate([bin_counts[rows], n_static[rows, None]], axis=1).astype(np.int32)
+        rows_dev, seg_dev = up(rows), up(seg)
+        _keys, payload = B.track_pair_order(state, rows_dev, seg_dev, int(seg[-1]), thr, window)
+        out = B.track_pair_resolve(state, bin_counts_dev, rows_dev, seg_dev, payload, table, classes, thr, window)
+        resolved[where] = down(out)
+    if (resolved < 0).any():
+        raise RuntimeError("track mining: a pick was not resolved")
+    sample_pairs = [{"point_index": p, "frame1": f[0], "frame2": f[1]} for (p, _c, _r), f in zip(picks, resolved)]
+    for m in swaps:
+        s = sample_pairs[m]
+        sample_pairs.append({"point_index": s["point_index"], "frame1": s["frame2"], "frame2": s["frame1"]})
+    return sample_pairs
+
+
 def object_movement_mine_pairs(visibility: np.ndarray, groups: Sequence[Sequence[int]], distance_fn,
                                npoints_per_group: int = 5, npairs_per_bin=1e8, augment: bool = True,
                                augment_ratio: float = 1.0, rng=_random, object_not_moving_threshold: float = 0.01,
-                               future_frame_windows: float = 1e8) -> List[dict]:
+                               future_frame_windows: float = 1e8, world=None) -> List[dict]:
     """Frame-pair mining of OM_C.generate_qa_training_single_scene (OM_C:465-567): per rigid group a few points,
     per point one static pair plus distance-binned moving pairs, then the swap augmentation.
 
@@ -1133,7 +1252,22 @@ def object_movement_mine_pairs(visibility: np.ndarray, groups: Sequence[Sequence
     Draw order, stable sort, bin edges and the carried-over ``npairs_per_bin`` follow upstream; so does its frame
     window test, which compares the *distance* and the first frame index (OM_C:505-507) and therefore never fires
     with the default window.
+
+    ``world`` (K5a's [T, P, 3] float64 device tensor) with ``MSPA_TRACK_MINING=device`` runs the mining on the device instead
+    (``_mine_pairs_device``): the same list, the same ``rng`` state and the same shuffled ``groups``, or -- where it declines,
+    before any draw -- the code below.  ``LAST_TRACK_MINING`` says which, and why.
     """
+    LAST_TRACK_MINING.clear()
+    if _track_mining_backend() != "device":
+        LAST_TRACK_MINING.update(path="host", reason="MSPA_TRACK_MINING is not 'device'")
+    else:
+        mined = "no device world" if world is None else _mine_pairs_device(
+            visibility, groups, world, npoints_per_group, npairs_per_bin, augment, augment_ratio, rng, object_not_moving_threshold,
+            future_frame_windows)
+        if not isinstance(mined, str):
+            LAST_TRACK_MINING.update(path="device", reason="")
+            return mined
+        LAST_TRACK_MINING.update(path="host", reason=mined)
     sample_pairs: List[dict] = []
     for group in groups:
         rng.shuffle(group)                                                   # in place, as upstream (OM_C:468)

@@ -472,8 +472,9 @@ def run(scenes: Sequence, out_dir: str, ctx: Optional[shard.DistContext] = None,
             world_xyz = E.track_to_world(dev_tracks, c2w, tr.fx_fy_cx_cy, tr.image_hw, ("world",))["world"]       # K5a
             for qt in T.OBJECT_MOVEMENT_TYPES:
                 rng = random.Random(f"{seed}:om:{qt}:{k}")
-                pairs_k = heads.object_movement_mine_pairs(                                           # K5c
-                    tr.visibility, groups, lambda p, f: E.track_pair_distances(world_xyz, p, f), 5, 3, True, 0.05, rng)
+                pairs_k = heads.object_movement_mine_pairs(                                           # K5c, or K5d
+                    tr.visibility, groups, lambda p, f: E.track_pair_distances(world_xyz, p, f), 5, 3, True, 0.05, rng,
+                    world=world_xyz)
                 merge(outputs, f"object_movement_{qt}",
                       heads.object_movement_records(tr.scene_id, xyz, tr.extrinsics_w2c, tr.fx_fy_cx_cy, tr.image_hw,
                                                     pairs_k, qt, T.OBJECT_MOVEMENT, rng, device))        # K5a + K5b

@@ -138,7 +138,8 @@ class TwoFrameVideoQAEngine:
         groups = filter_large_groups(rigid_body_segmentation(tracks_xyz), min_size=5)
         sample_pairs = heads.object_movement_mine_pairs(
             visibility, groups, lambda pts, frames: engine.track_pair_distances(world, pts, frames), npoints_per_group,
-            npairs_per_bin, augment, augment_ratio, random, self.object_not_moving_threshold, self.future_frame_windows)
+            npairs_per_bin, augment, augment_ratio, random, self.object_not_moving_threshold, self.future_frame_windows,
+            world=world)
         return self.format_training_samples(sample_pairs, intrinsics=intrinsics, scene_id=scene_id,
                                             points_pos_world=None, points_pos_cam=tracks_xyz, image_height=image_height,
                                             image_width=image_width, extrinsics_w2c=extrinsics_w2c)
