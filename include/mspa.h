@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MSPA_VERSION 250            /* 0.15.0: pair mining of the object-movement head on the device (mspa_track_pair_stats / _bin_counts / _sort / _order / _resolve); 0.14.0: handler ops on the device: grey decode and Laplacian moments (mspa_jpeg_decode_luma_device, mspa_laplacian_moments_device), exact k-nearest mean distance (mspa_knn_*); 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
+#define MSPA_VERSION 260            /* 0.16.0: per-object clouds from instance masks on the device: 8-bit greyscale PNG decode (mspa_png_pack_idat8_host, mspa_png_unfilter8_device / _host) and the stable split by label (mspa_instance_split_count / _scatter); 0.15.0: pair mining of the object-movement head on the device (mspa_track_pair_stats / _bin_counts / _sort / _order / _resolve); 0.14.0: handler ops on the device: grey decode and Laplacian moments (mspa_jpeg_decode_luma_device, mspa_laplacian_moments_device), exact k-nearest mean distance (mspa_knn_*); 0.13.0: parquet data pages of the visibility index on the device (mspa_snappy_*, mspa_parquet_*); 0.12.0: rigid-body track grouping on the device (mspa_track_linkage, mspa_track_rigidity_loss_batch); 0.11.0: image resizing on the device (mspa_resize_coeffs_host, mspa_resize_rgb_device); 0.10.0: ScanNet instance data from raw scans (mspa_prep_labels / _align / _objects, mspa_parse_int_list_*); 0.9.0: depth-PNG writes on the device (mspa_png_encode_device); 0.8.0: annotated-image writes on the device (mspa_jpeg_encode_device, mspa_draw_spans_device,
                                        mspa_blend_masks_device); 0.7.0: colour-frame (baseline JPEG) decode on the device (mspa_jpeg_parse_host, mspa_jpeg_decode_device);
                                        0.6.0: depth-frame decode on the device (mspa_inflate_blocks_device, mspa_png_unfilter_device); 0.5.0: host-side depth-PNG ingest (mspa_read_depth_png_host); 0.4.0: frame records carry
                                        guard-bound coefficients (slot MSPA_MAT_BOUNDS, MSPA_FRAME_MATS 7 -> 8) */
@@ -1089,6 +1089,61 @@ int mspa_knn_cells_device(const double *xyz_dev, int64_t n, const void *grid_hos
 int mspa_knn_mean_distance_device(const double *xyz_dev, int64_t n, int32_t k, const void *grid_host, const int64_t *order_dev,
                                   double *mean_dev, int32_t *evals_dev, void *workspace, int64_t workspace_bytes, mspa_stream_t stream);
 int mspa_knn_mean_distance_host(const double *xyz_host, int64_t n, int32_t k, double *mean_host, int32_t *evals_host);
+
+/*
+ * Instance-mask decode ON THE DEVICE (csrc/mask_ingest.hip, rule in csrc/png_unfilter8_core.h): the 8-bit twin of the depth-frame
+ * decode above, for ScanNet's `instance-filt/<image>.png` label images (`cv2.imread(path, -1)` per (image, object) in the
+ * reference's get_instance_mask).  The inflate in front of the un-filter is mspa_inflate_blocks_device with block_bytes = h * (w + 1).
+ *
+ * mspa_png_pack_idat8_host    mspa_png_pack_idat_host for 8-bit greyscale (bit depth 8, colour type 0), non-interlaced h x w PNG
+ *   files: the same two-call contract, offsets and status codes (0 packed; 1 unreadable; 2 another pixel format or size; 3 corrupt
+ *   chunk structure).
+ * mspa_png_unfilter8_device   n_images inflated scanline blocks (h rows of 1 filter byte + w sample bytes, image k at raw_dev + k *
+ *   raw_pitch) -> out_dev[k, h, w] uint8: the five PNG row filters undone with bytes-per-pixel 1.  Images whose status_dev[k] is
+ *   non-zero on entry are skipped; an image with a filter byte > 4 gets status 3 and is not written.  raw_pitch >= h * (w + 1) and a
+ *   multiple of 4, raw_dev 4-byte aligned (MSPA_EINVAL otherwise).  Every well-formed image is decoded: nothing is declined.
+ * mspa_png_unfilter8_host     the same rule from the same header on the CPU (no alignment requirement).
+ */
+int mspa_png_pack_idat8_host(const char *const *paths_host, int64_t n_files, int32_t h, int32_t w, void *dst_host,
+                             int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
+                             int64_t *capacity_needed, int32_t n_threads);
+int mspa_png_unfilter8_device(const void *raw_dev, int64_t raw_pitch, int64_t n_images, int32_t h, int32_t w, uint8_t *out_dev,
+                              int32_t *status_dev, mspa_stream_t stream);
+int mspa_png_unfilter8_host(const void *raw_host, int64_t raw_pitch, int64_t n_images, int32_t h, int32_t w, uint8_t *out_host,
+                            int32_t *status_host);
+
+/*
+ * Stable split of a batch of frames' valid pixels by instance label (csrc/instance_split.hip, rule and decomposition in
+ * csrc/instance_split_core.h): the per-object clouds of `project_image_to_3d_with_mask(get_instance_mask(...))` for EVERY object
+ * of every frame from one K3 exact pass per frame.  labels [F, P] uint8 (P = H * W colour pixels, row-major; 0 = nothing, object
+ * `target_id` is label `target_id + 1`), valid = K3 exact's valid_u8 [F, P], xyz_f64 = its [F, P, 3], rgb optionally [F, H, W, 3]
+ * uint8.  A pixel is selected when label != 0 and valid != 0.  F <= 65535, P < 2^31.  All buffers are the caller's:
+ *   mspa_instance_split_workspace_bytes   the workspace of both calls (4-byte aligned); -1 for sizes out of range.
+ *   mspa_instance_split_count             out_counts [F, 256] int32: selected pixels per (frame, label); the workspace receives
+ *                                         what the second call needs (per-tile positions).
+ *   mspa_instance_split_scatter           offsets [F * 256 + 1] int64 = the exclusive prefix of out_counts in (frame, label) order
+ *                                         (the caller's scan), workspace as the first call left it.  Writes out_xyz [total, 3] f64,
+ *                                         out_rgb [total, 3] u8 (rgb and out_rgb both given or both null) and out_pixel [total]
+ *                                         int32 (the pixel index my * W + mx).  THE ORDER IS THE CONTRACT: segment (f, v) occupies
+ *                                         rows offsets[f * 256 + v] .. and holds its pixels in ascending pixel index (np.where(mask)
+ *                                         order), whatever order the hardware runs the workgroups in.  out_lo / out_hi [F, 256, 3]
+ *                                         f64: the segment's per-axis minimum / maximum, +inf / -inf where it is empty (the sign of
+ *                                         a zero extremum is unspecified when both zeros occur).
+ *   mspa_instance_split_host              the same decomposition on the CPU through the same header (tests; the arrays are host
+ *                                         memory).  Fills out_counts, out_offsets [F * 256 + 1] and, unless out_xyz is null (the
+ *                                         size-only first call), everything the scatter writes.  workspace: the same size, int32.
+ *                                         reversed != 0 walks tiles and waves in the opposite order: the output does not change.
+ */
+int64_t mspa_instance_split_workspace_bytes(int64_t F, int64_t P);
+int mspa_instance_split_count(const uint8_t *labels, const uint8_t *valid, int64_t F, int64_t P, int32_t *out_counts, void *workspace,
+                              int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_instance_split_scatter(const uint8_t *labels, const uint8_t *valid, const double *xyz_f64, const uint8_t *rgb_or_null,
+                                int64_t F, int64_t P, int32_t H, int32_t W, const int64_t *offsets, const void *workspace,
+                                double *out_xyz, uint8_t *out_rgb, int32_t *out_pixel, double *out_lo, double *out_hi,
+                                mspa_stream_t stream);
+int mspa_instance_split_host(const uint8_t *labels, const uint8_t *valid, const double *xyz_f64, const uint8_t *rgb_or_null, int64_t F,
+                             int64_t P, int32_t *out_counts, int64_t *out_offsets, int32_t *workspace, double *out_xyz,
+                             uint8_t *out_rgb, int32_t *out_pixel, double *out_lo, double *out_hi, int32_t reversed);
 
 #ifdef __cplusplus
 }

@@ -221,14 +221,16 @@ extern "C" int mspa_read_depth_png_host(const char *const *paths_host, int64_t n
 }
 
 
-// The host half of the on-device decode (csrc/device_ingest.hip): file bytes -> the scanlines' zlib stream, packed for ONE H2D copy.
-extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_files, int32_t h, int32_t w, void *dst_host,
-                                       int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
-                                       int64_t *capacity_needed, int32_t n_threads) {
+// The host half of the on-device decode (csrc/device_ingest.hip, csrc/mask_ingest.hip): file bytes -> the scanlines' zlib stream,
+// packed for ONE H2D copy.  Behind mspa_png_pack_idat_host (bit_depth 16) and mspa_png_pack_idat8_host (bit_depth 8): greyscale,
+// non-interlaced files of that depth and exactly h x w are packed, every other file gets status 2.
+int mspa::png_pack_idat_files(const char *who, int bit_depth, const char *const *paths_host, int64_t n_files, int32_t h, int32_t w,
+                              void *dst_host, int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
+                              int64_t *capacity_needed, int32_t n_threads) {
     if (n_files < 0 || h <= 0 || w <= 0 || (n_files > 0 && (!paths_host || !offsets_host || !bytes_host || !status_host)))
-        return fail(MSPA_EINVAL, "mspa_png_pack_idat_host: bad argument");
+        return fail(MSPA_EINVAL, std::string(who) + ": bad argument");
     for (int64_t k = 0; k < n_files; ++k)
-        if (!paths_host[k]) return fail(MSPA_EINVAL, "mspa_png_pack_idat_host: null path");
+        if (!paths_host[k]) return fail(MSPA_EINVAL, std::string(who) + ": null path");
     // slot k = the file's size rounded up to 16 bytes (+ 16: the device reader may touch the 8-byte unit a stream ends in); the
     // file is read INTO its slot and the IDAT payloads are then moved to the slot's front, so nothing is copied twice
     int64_t need = 0;
@@ -245,7 +247,7 @@ extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_
     }
     if (capacity_needed) *capacity_needed = need;
     if (!dst_host) return MSPA_OK;
-    if (dst_capacity < need) return fail(MSPA_EINVAL, "mspa_png_pack_idat_host: destination smaller than capacity_needed");
+    if (dst_capacity < need) return fail(MSPA_EINVAL, std::string(who) + ": destination smaller than capacity_needed");
     if (n_files == 0) return MSPA_OK;
     const int64_t nt = n_threads < 1 ? 1 : (n_threads > n_files ? n_files : (int64_t)n_threads);
     std::atomic<int64_t> next{0};
@@ -265,7 +267,7 @@ extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_
                     if (got) {
                         PngHeader hd;
                         if (parse_header(slot, (size_t)sz, hd)) st = 3;
-                        else if (hd.bit_depth != 16 || hd.color_type != 0 || hd.interlace != 0 || hd.w != (uint32_t)w || hd.h != (uint32_t)h) st = 2;
+                        else if (hd.bit_depth != bit_depth || hd.color_type != 0 || hd.interlace != 0 || hd.w != (uint32_t)w || hd.h != (uint32_t)h) st = 2;
                         else {
                             size_t pos = 33, out = 0;
                             bool bad = false, any = false;
@@ -296,6 +298,13 @@ extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_
     };
     HostPool::get().parallel((int)nt, work);
     return MSPA_OK;
+}
+
+extern "C" int mspa_png_pack_idat_host(const char *const *paths_host, int64_t n_files, int32_t h, int32_t w, void *dst_host,
+                                       int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
+                                       int64_t *capacity_needed, int32_t n_threads) {
+    return png_pack_idat_files("mspa_png_pack_idat_host", 16, paths_host, n_files, h, w, dst_host, dst_capacity, offsets_host, bytes_host,
+                               status_host, capacity_needed, n_threads);
 }
 
 

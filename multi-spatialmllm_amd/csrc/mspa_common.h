@@ -19,6 +19,11 @@ std::string &last_error();
 int fail(int code, const std::string &what);
 int check_hip(hipError_t e, const char *what);
 int xcd_count();               // XCDs a 1-D grid's workgroups are dealt over: 8 (MI355X, SPX mode) or 1
+// PNG files -> their scanline zlib streams packed for one H2D copy (csrc/host_ingest.hip): the body of mspa_png_pack_idat_host (bit depth 16)
+// and mspa_png_pack_idat8_host (bit depth 8), whose contract it keeps; `who` names the entry point in error texts.
+int png_pack_idat_files(const char *who, int bit_depth, const char *const *paths_host, int64_t n_files, int32_t h, int32_t w,
+                        void *dst_host, int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
+                        int64_t *capacity_needed, int32_t n_threads);
 
 // Lanes of one wave exchange data through LDS (every lane stores its slot, then loads another lane's).  The hardware executes a
 // wave's LDS operations in order, so no instruction is needed -- but the compiler must not move the loads above the stores

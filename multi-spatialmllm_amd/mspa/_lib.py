@@ -218,6 +218,16 @@ _SIGNATURES = {
     "mspa_knn_cells_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mspa_knn_mean_distance_device": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mspa_knn_mean_distance_host": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "mspa_png_pack_idat8_host": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         POINTER(c_int64), c_int32]),
+    "mspa_png_unfilter8_device": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mspa_png_unfilter8_host": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "mspa_instance_split_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "mspa_instance_split_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_instance_split_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_instance_split_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
 }
 
 

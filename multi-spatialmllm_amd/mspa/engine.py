@@ -278,7 +278,87 @@ def png_unfilter_device(raw: torch.Tensor, h: int, w: int, status: torch.Tensor,
     return out
 
 
-JPEG_STATUS = {0: "decoded", 1: "not a JPEG / malformed header", 2: "outside the accepted subset", 3: "another size",
+def png_unfilter8_device(raw: torch.Tensor, h: int, w: int, status: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``raw[k, : h * (w + 1)]`` -- the inflated scanlines of n 8-bit greyscale PNG images (instance masks) -- to ``out[k, h, w]``
+    uint8: the five PNG row filters undone on the device with bytes-per-pixel 1 (mspa_png_unfilter8_device).  Images with
+    ``status[k] != 0`` are skipped; a filter byte > 4 sets status 3.  ``raw`` starts 4-byte aligned and its pitch is a multiple of
+    4 (MspaError otherwise, as from the C ABI)."""
+    n = _check("raw", raw, torch.uint8, (None, (h * (w + 1),))).shape[0]
+    if _ptr(raw) % 4 or int(raw.shape[1]) % 4:
+        raise _lib.MspaError(_lib.MSPA_EINVAL, "png_unfilter8_device: raw must start 4-byte aligned, with a pitch that is a multiple of 4")
+    _check("status", status, torch.int32, ((n,),))
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=raw.device) if out is None else _check("out", out, torch.uint8, ((n,), h, w))
+    _lib.check(_lib.load().mspa_png_unfilter8_device(_ptr(raw), int(raw.shape[1]), n, int(h), int(w), _ptr(out), _ptr(status),
+                                                     _stream_ptr()))
+    return out
+
+
+SPLIT_LABELS = 256
+
+
+def instance_split(labels: torch.Tensor, valid: torch.Tensor, xyz: torch.Tensor, rgb: Optional[torch.Tensor] = None):
+    """The stable split of F frames' valid pixels by instance label (mspa_instance_split_count / _scatter): ``labels`` [F, H, W]
+    uint8 (0 = nothing), ``valid`` [F, P] uint8 and ``xyz`` [F, P, 3] float64 as K3 exact wrote them (P = H * W), ``rgb`` optionally
+    [F, H, W, 3] uint8.  Returns (counts [F, 256] int32, offsets [F * 256 + 1] int64, xyz [total, 3] float64, rgb [total, 3] uint8 or
+    None, pixel [total] int32, lo [F, 256, 3], hi [F, 256, 3] float64): segment (f, v) is rows ``offsets[f * 256 + v] :
+    offsets[f * 256 + v + 1]``, the selected pixels of frame f with label v in ascending pixel index; lo / hi are its extents
+    (+inf / -inf where it is empty).  ``counts`` and ``offsets`` come back on the HOST (NumPy): reading the counts is the call's
+    one synchronisation, and every accessor indexes with them."""
+    F, H, W = _check("labels", labels, torch.uint8, (None, None, None)).shape
+    P = H * W
+    _check("valid", valid, torch.uint8, (F, P))
+    _check("xyz", xyz, torch.float64, (F, P, 3))
+    if rgb is not None:
+        _check("rgb", rgb, torch.uint8, (F, H, W, 3))
+    _require(F <= 65535 and P < 2 ** 31, f"at most 65535 frames of fewer than 2^31 pixels per launch, got {F} x {P}")
+    lib, dev = _lib.load(), labels.device
+    counts_d = torch.empty((F, SPLIT_LABELS), dtype=torch.int32, device=dev)
+    nbytes = int(lib.mspa_instance_split_workspace_bytes(F, P))
+    work = _workspace(nbytes, dev)
+    _lib.check(lib.mspa_instance_split_count(_ptr(labels), _ptr(valid), F, P, _ptr(counts_d), _ptr(work), nbytes, _stream_ptr()))
+    counts = counts_d.cpu().numpy()                                         # the one synchronisation
+    offsets = np.zeros(F * SPLIT_LABELS + 1, dtype=np.int64)
+    np.cumsum(counts.reshape(-1), out=offsets[1:])
+    total = int(offsets[-1])
+    out_xyz = torch.empty((max(total, 1), 3), dtype=torch.float64, device=dev)   # (never a null pointer: an empty tensor has none)
+    out_rgb = torch.empty((max(total, 1), 3), dtype=torch.uint8, device=dev) if rgb is not None else None
+    out_pixel = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
+    lo = torch.empty((F, SPLIT_LABELS, 3), dtype=torch.float64, device=dev)
+    hi = torch.empty((F, SPLIT_LABELS, 3), dtype=torch.float64, device=dev)
+    offsets_d = torch.from_numpy(offsets).to(dev)
+    if F:
+        _lib.check(lib.mspa_instance_split_scatter(_ptr(labels), _ptr(valid), _ptr(xyz), _ptr(rgb), F, P, H, W, _ptr(offsets_d), _ptr(work),
+                                                   _ptr(out_xyz), _ptr(out_rgb), _ptr(out_pixel), _ptr(lo), _ptr(hi), _stream_ptr()))
+    return counts, offsets, out_xyz[:total], None if out_rgb is None else out_rgb[:total], out_pixel[:total], lo, hi
+
+
+def instance_split_host(labels: np.ndarray, valid: np.ndarray, xyz: np.ndarray, rgb: Optional[np.ndarray] = None, reversed_order: bool = False):
+    """``instance_split`` on the CPU through the same header (mspa_instance_split_host): NumPy in, NumPy out, no GPU.  For the
+    tests: ``reversed_order`` walks tiles and waves in the opposite order, which must not change a byte."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint8)
+    F = labels.shape[0]
+    P = int(np.prod(labels.shape[1:]))
+    valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(F, P)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(F, P, 3)
+    rgb = None if rgb is None else np.ascontiguousarray(rgb, dtype=np.uint8).reshape(F, P, 3)
+    lib = _lib.load()
+    counts = np.zeros((F, SPLIT_LABELS), dtype=np.int32)
+    offsets = np.zeros(F * SPLIT_LABELS + 1, dtype=np.int64)
+    work = np.zeros(max(int(lib.mspa_instance_split_workspace_bytes(F, P)) // 4, 4), dtype=np.int32)
+    head = (labels.ctypes.data, valid.ctypes.data, xyz.ctypes.data, None if rgb is None else rgb.ctypes.data, F, P, counts.ctypes.data,
+            offsets.ctypes.data, work.ctypes.data)
+    _lib.check(lib.mspa_instance_split_host(*head, None, None, None, None, None, 0))
+    total = int(offsets[-1])
+    out_xyz = np.zeros((max(total, 1), 3), dtype=np.float64)
+    out_rgb = None if rgb is None else np.zeros((max(total, 1), 3), dtype=np.uint8)
+    out_pixel = np.zeros(max(total, 1), dtype=np.int32)
+    lo, hi = np.zeros((F, SPLIT_LABELS, 3)), np.zeros((F, SPLIT_LABELS, 3))
+    _lib.check(lib.mspa_instance_split_host(*head, out_xyz.ctypes.data, None if out_rgb is None else out_rgb.ctypes.data,
+                                            out_pixel.ctypes.data, lo.ctypes.data, hi.ctypes.data, int(bool(reversed_order))))
+    return counts, offsets, out_xyz[:total], None if out_rgb is None else out_rgb[:total], out_pixel[:total], lo, hi
+
+
+JPEG_STATUS ={0: "decoded", 1: "not a JPEG / malformed header", 2: "outside the accepted subset", 3: "another size",
                4: "bad entropy-coded data", 5: "restart marker missing or out of sequence", 6: "no EOI after the last MCU",
                7: "block out of range"}
 

@@ -268,6 +268,77 @@ def read_depth_frames_device(paths: Sequence[str], device="cuda", n_threads: int
     return frames[:F]
 
 
+def pack_mask_pngs(paths: Sequence[str], h: int, w: int, n_threads: int = 8, out=None):
+    """``pack_depth_pngs`` for 8-bit greyscale ``h x w`` PNG files (instance masks; mspa_png_pack_idat8_host): the same return
+    value, (buffer, offsets int64 [F], nbytes int64 [F], status int32 [F], capacity).  A file of another pixel format gets
+    status 2."""
+    paths = list(paths)
+    F = len(paths)
+    enc = [p.encode() for p in paths]
+    arr = (ctypes.c_char_p * max(F, 1))(*enc)
+    offsets, nbytes = np.zeros(F, dtype=np.int64), np.zeros(F, dtype=np.int64)
+    status = np.zeros(F, dtype=np.int32)
+    need = ctypes.c_int64(0)
+    lib = _lib.load()
+    _lib.check(lib.mspa_png_pack_idat8_host(arr, F, int(h), int(w), None, 0, offsets.ctypes.data, nbytes.ctypes.data,
+                                            status.ctypes.data, ctypes.byref(need), int(n_threads)))
+    cap = int(need.value)
+    if out is None or out.nbytes < cap:
+        out = np.empty(max(cap, 16), dtype=np.uint8)
+    _lib.check(lib.mspa_png_pack_idat8_host(arr, F, int(h), int(w), out.ctypes.data, int(out.nbytes), offsets.ctypes.data,
+                                            nbytes.ctypes.data, status.ctypes.data, ctypes.byref(need), int(max(1, n_threads))))
+    return out, offsets, nbytes, status, cap
+
+
+def _pillow_any(path: str) -> np.ndarray:
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im)
+
+
+def read_label_frames_device(paths: Sequence[str], device="cuda", n_threads: int = 8,
+                             general_reader: Optional[Callable[[str], np.ndarray]] = None):
+    """[F, h, w] uint8 device tensor: the label images (instance masks) at ``paths`` DECODED ON THE DEVICE, built like
+    ``read_depth_frames_device`` -- the host packs the 8-bit greyscale PNGs' scanline streams (``pack_mask_pngs``), one H2D copy
+    carries them, one wave per image inflates (mspa_inflate_blocks_device, block = h * (w + 1) bytes) and one un-filters
+    (mspa_png_unfilter8_device); one synchronisation reads the status.  A file the device declines -- another pixel format
+    (16-bit labels, palette, RGB), a damaged stream -- is read by ``general_reader(path)`` (default: Pillow) and uploaded on its
+    own.  (h, w) is the first file's.  Labels above 255 from that reader, or an image of another size or with channels, raise
+    ValueError: the label block is uint8 by contract.  A file that cannot be read raises FileNotFoundError."""
+    import torch
+    from . import engine
+    paths = list(paths)
+    F = len(paths)
+    if F == 0:
+        return torch.zeros((0, 0, 0), dtype=torch.uint8, device=device)
+    reader = general_reader or _pillow_any
+    try:
+        h, w = png_header(paths[0])[:2]
+    except _lib.MspaError:
+        try:
+            first = np.asarray(reader(paths[0]))
+        except (OSError, TypeError):
+            raise FileNotFoundError(paths[0]) from None
+        h, w = first.shape[:2]
+    buf, offsets, nbytes, st_host, cap = pack_mask_pngs(paths, h, w, n_threads)
+    src = torch.from_numpy(buf[:max(cap, 16)]).to(device, non_blocking=False)
+    off_d = torch.from_numpy(offsets).to(device)
+    nb_d = torch.from_numpy(np.where(st_host == 0, nbytes, 0)).to(device)          # a file the packer declined: an empty stream
+    raw, status = engine.inflate_blocks_device(src, off_d, nb_d, h * (w + 1))
+    frames = engine.png_unfilter8_device(raw, h, w, status)
+    for k in np.nonzero(status.cpu().numpy())[0]:
+        k = int(k)
+        if st_host[k] == 1:
+            raise FileNotFoundError(paths[k])
+        a = np.asarray(reader(paths[k]))
+        if a.shape != (h, w):
+            raise ValueError(f"{paths[k]}: label image of shape {a.shape}, the batch is {(h, w)}")
+        if a.dtype != np.uint8 and (a.min() < 0 or a.max() > 255):
+            raise ValueError(f"{paths[k]}: labels above 255 do not fit the device path's uint8 label block")
+        frames[k] = torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(device)
+    return frames
+
+
 def _pillow_rgb(path: str) -> np.ndarray:
     from PIL import Image
     with Image.open(path) as im:

@@ -1,0 +1,232 @@
+"""Per-object point clouds of a scene's frames from their instance masks, batched on the device.
+
+The reference builds an object's cloud per (image, object): ``get_instance_mask`` reads ``instance-filt/<image>.png`` and compares
+it with ``target_id + 1``, ``project_image_to_3d_with_mask`` reads the depth frame (and the colour frame) again and back-projects
+the mask's pixels.  A frame with 30 objects decodes the same files 30 times and runs K3 30 times over the same pixels.  ``build``
+does: one decode of the depth frames, the label images and (when asked) the colour frames on the device, then per chunk of frames
+ONE ``engine.pair_reproject`` exact launch with pairs (f, f) and one ``engine.instance_split``.  What comes back, ``InstanceClouds``, holds
+the rows of every (image, label) segment back to back on the device -- value for value what the composition returns per object, in
+its order -- and hands out views.  ``LAST_INSTANCE_CLOUDS`` says which path the last call took, and why.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import engine, ingest
+
+LAST_INSTANCE_CLOUDS: Dict[str, str] = {}        # {"path": "device" | "host", "reason": why the per-object host composition ran}
+
+
+class InstanceClouds:
+    """The clouds of every (image, object) of one call.  ``rows`` [total, 3 or 6] float64 (device): xyz, then -- with colour --
+    the RGB columns converted to float64, as ``np.hstack((xyz, rgb))`` does; segment (frame k, label v) is
+    ``rows[offsets[k * L + v] : offsets[k * L + v + 1]]`` in ascending pixel index; ``counts`` [F, L] and ``offsets`` are host
+    arrays (L = 256 on the device path); ``pixel`` [total] int32 the rows' pixel indices my * W + mx; ``lo`` / ``hi`` [F, L, 3]
+    the segments' extents (+inf / -inf where empty).  Object ``target_id`` is label ``target_id + 1``, as upstream."""
+
+    def __init__(self, image_ids: Sequence, counts: np.ndarray, rows: torch.Tensor, pixel: Optional[torch.Tensor], lo: torch.Tensor,
+                 hi: torch.Tensor, rgb: Optional[torch.Tensor] = None):
+        self.image_ids = list(image_ids)
+        self._frame = {self._key(i): k for k, i in enumerate(self.image_ids)}
+        self.counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self.n_labels = int(self.counts.shape[1])
+        self.offsets = np.zeros(self.counts.size + 1, dtype=np.int64)
+        np.cumsum(self.counts.reshape(-1), out=self.offsets[1:])
+        self.rows, self.pixel, self.lo, self.hi, self.rgb = rows, pixel, lo, hi, rgb
+        self.with_color = rows.shape[1] == 6
+
+    @staticmethod
+    def _key(image_id):
+        try:
+            return int(image_id)
+        except (TypeError, ValueError):
+            return image_id
+
+    def _segment(self, image_id, target_id):
+        k, v = self._frame[self._key(image_id)], int(target_id) + 1
+        if v <= 0 or v >= self.n_labels:
+            return k, v, 0, 0
+        s = k * self.n_labels + v
+        return k, v, int(self.offsets[s]), int(self.offsets[s + 1])
+
+    def cloud(self, image_id, target_id) -> torch.Tensor:
+        """[M, 3] or [M, 6] float64 device tensor, a view: ``project_image_to_3d_with_mask(scene, image, get_instance_mask(scene,
+        image, target_id), with_color)`` value for value; [0, C] for an object the image does not show."""
+        _k, _v, a, b = self._segment(image_id, target_id)
+        return self.rows[a:b]
+
+    def count(self, image_id, target_id) -> int:
+        _k, _v, a, b = self._segment(image_id, target_id)
+        return b - a
+
+    def present(self, image_id) -> List[int]:
+        """The target ids with at least one selected pixel in the image, ascending."""
+        k = self._frame[self._key(image_id)]
+        return [int(v) - 1 for v in np.nonzero(self.counts[k])[0] if v > 0]
+
+    def aabb(self, image_id, target_id) -> torch.Tensor:
+        """[cx, cy, cz, dx, dy, dz] of the object's cloud in the image: ``calculate_aabb(cloud(...))`` from the extents the split
+        took.  An empty cloud has no box (ValueError, as NumPy's reduction over no rows)."""
+        k, v, a, b = self._segment(image_id, target_id)
+        if a == b:
+            raise ValueError(f"aabb: object {target_id} has no point in image {image_id}")
+        lo, hi = self.lo[k, v], self.hi[k, v]
+        return torch.cat([(hi + lo) / 2, hi - lo])
+
+    def object_cloud(self, target_id) -> torch.Tensor:
+        """The object's rows over all images, in ``image_ids`` order: one device concatenation."""
+        return torch.cat([self.cloud(i, target_id) for i in self.image_ids] or [self.rows[:0]])
+
+
+def _mask_path(handler, scene_id, image_id) -> str:
+    return os.path.join(handler.mask_image_root, scene_id, "instance-filt", f"{int(image_id)}.png")
+
+
+def _rows(xyz: torch.Tensor, rgb: Optional[torch.Tensor]) -> torch.Tensor:
+    return xyz if rgb is None else torch.cat([xyz, rgb.to(torch.float64)], dim=1)
+
+
+DECODE_GROUP = 256          # frames decoded in one batch: the decode kernels take one wave per frame, so their time is a frame's, not the batch's
+
+
+def _decode_group(handler, scene_id, ids, mask_paths, with_color, device, num_workers, images, color_hw):
+    """(depth [f, h, w] int16, labels [f, H, W] uint8, rgb [f, H, W, 3] uint8 or None) of a group of posed frames, each decoded once on
+    the device.  Raises ValueError where the device path declines."""
+    depth_paths = [handler.get_depth_image_path(scene_id, i) for i in ids]
+    if any(p in images.MEMORY for p in depth_paths):                       # registered frames (synthetic scenes, tests): host, then upload
+        depth = engine.depth_to_device(ingest.read_depth_frames(depth_paths, num_workers, general_reader=images.read_depth,
+                                                                memory=images.MEMORY), device)
+    else:
+        depth = ingest.read_depth_frames_device(depth_paths, device, num_workers, general_reader=images.read_depth)
+    labels = ingest.read_label_frames_device(mask_paths, device, num_workers, general_reader=images.read_depth)
+    H, W = int(labels.shape[1]), int(labels.shape[2])
+    if (H, W) != tuple(color_hw):
+        raise ValueError(f"mask of {(H, W)}, colour frames of {tuple(color_hw)}")
+    rgb = None
+    if with_color:
+        color_paths = [handler.get_image_path(scene_id, i) for i in ids]
+        if any(p in images.MEMORY for p in color_paths):
+            rgb = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(images.read_color_rgb(p)) for p in color_paths]))).to(device)
+        else:
+            rgb = handler.color_frames_device(scene_id, ids, device, num_workers)
+        if tuple(rgb.shape) != (len(ids), H, W, 3) or rgb.dtype != torch.uint8:
+            raise ValueError(f"colour frames of {tuple(rgb.shape)} {rgb.dtype}")
+    return depth, labels, rgb
+
+
+def _split_chunk(handler, scene_id, ids, depth, labels, rgb, device):
+    """One chunk of decoded frames through ONE K3 exact launch (pairs (f, f): xyz_f64 + valid_u8 of every pixel) and the split."""
+    H, W = int(labels.shape[1]), int(labels.shape[2])
+    K = handler.get_intrinsic_matrix(scene_id, ids[0])
+    A = handler.get_world_to_axis_align_matrix(scene_id)
+    mats = torch.from_numpy(engine.frame_matrices(np.asarray(K, np.float64), np.asarray(A, np.float64),
+                                                  [np.asarray(handler.get_extrinsic_matrix(scene_id, i, warning=False), np.float64)
+                                                   for i in ids])).to(device)
+    pairs = torch.arange(len(ids), dtype=torch.int32, device=device)[:, None].repeat(1, 2).contiguous()
+    out = engine.alloc_pair_outputs(len(ids), (H, W), ("xyz_f64", "valid_u8"), device)
+    engine.pair_reproject(depth, mats, pairs, (H, W), out)
+    return engine.instance_split(labels, out["valid_u8"], out["xyz_f64"], rgb)
+
+
+def _host_composition(handler, scene_id, ids, with_color, device, images) -> InstanceClouds:
+    """The same object from the per-object composition the reference writes: get_instance_mask + project_image_to_3d_with_mask
+    per (image, label present in the mask)."""
+    per_frame, n_labels = [], 256
+    for i in ids:
+        clouds = {}
+        if handler.is_posed_image_valid(scene_id, i):
+            path = _mask_path(handler, scene_id, i)
+            try:
+                mask_image = images.read_depth(path)
+            except Exception:
+                mask_image = None
+            if mask_image is None:
+                raise FileNotFoundError(f"Mask image not found at path: {path}")
+            for v in np.unique(np.asarray(mask_image)):
+                if int(v) > 0:
+                    c = handler.project_image_to_3d_with_mask(scene_id, i, handler.get_instance_mask(scene_id, i, int(v) - 1), with_color)
+                    if len(c):
+                        clouds[int(v)] = np.asarray(c, dtype=np.float64)
+                        n_labels = max(n_labels, int(v) + 1)
+        else:
+            handler.get_extrinsic_matrix(scene_id, i)                      # (the reference's warning)
+        per_frame.append(clouds)
+    C = 6 if with_color else 3
+    counts = np.zeros((len(ids), n_labels), dtype=np.int64)
+    lo = np.full((len(ids), n_labels, 3), np.inf)
+    hi = np.full((len(ids), n_labels, 3), -np.inf)
+    blocks = []
+    for k, clouds in enumerate(per_frame):
+        for v in sorted(clouds):
+            counts[k, v] = len(clouds[v])
+            lo[k, v], hi[k, v] = clouds[v][:, :3].min(axis=0), clouds[v][:, :3].max(axis=0)
+            blocks.append(clouds[v])
+    rows = np.concatenate(blocks) if blocks else np.zeros((0, C))
+    return InstanceClouds(ids, counts, torch.from_numpy(np.ascontiguousarray(rows.reshape(-1, C))).to(device), None,
+                          torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device))
+
+
+def build(handler, scene_id, image_ids=None, with_color=False, device="cuda", num_workers=8, max_dense_bytes=1 << 30,
+          images=None) -> InstanceClouds:
+    """``SceneInfoHandler.instance_clouds``: see there.  ``images`` is the handler's image-I/O module (its in-memory registry and
+    general readers)."""
+    ids = handler.get_all_image_ids(scene_id) if image_ids is None else list(image_ids)
+    LAST_INSTANCE_CLOUDS.clear()
+    posed = [i for i in ids if handler.is_posed_image_valid(scene_id, i)]
+    mask_paths = {}
+    for i in posed:
+        p = _mask_path(handler, scene_id, i)
+        if p not in images.MEMORY and not os.path.isfile(p):
+            raise FileNotFoundError(f"Mask image not found at path: {p}")
+        mask_paths[InstanceClouds._key(i)] = p
+    reason = ""
+    if any(p in images.MEMORY for p in mask_paths.values()):
+        reason = "a mask is registered in memory, not a file"
+    color_hw = tuple(handler.get_image_shape(scene_id, posed[0])) if posed else (0, 0)
+    parts = []
+    if not reason and posed:
+        per_chunk = max(1, int(max_dense_bytes) // max(1, color_hw[0] * color_hw[1] * 24))
+        try:
+            group = max(per_chunk, DECODE_GROUP // per_chunk * per_chunk)
+            for g in range(0, len(posed), group):
+                gids = posed[g:g + group]
+                depth, labels, rgb = _decode_group(handler, scene_id, gids, [mask_paths[InstanceClouds._key(i)] for i in gids], with_color,
+                                                   device, num_workers, images, color_hw)
+                for b in range(0, len(gids), per_chunk):
+                    e = b + per_chunk
+                    parts.append(_split_chunk(handler, scene_id, gids[b:e], depth[b:e], labels[b:e], None if rgb is None else rgb[b:e],
+                                              device))
+        except ValueError as e:
+            reason = str(e)
+    if reason:
+        LAST_INSTANCE_CLOUDS.update(path="host", reason=reason)
+        return _host_composition(handler, scene_id, ids, with_color, device, images)
+    LAST_INSTANCE_CLOUDS.update(path="device", reason="")
+    # the chunks' segments back to back, the frames without a finite pose as empty rows of the tables
+    L = engine.SPLIT_LABELS
+    counts = np.zeros((len(ids), L), dtype=np.int64)
+    lo = torch.full((len(ids), L, 3), float("inf"), dtype=torch.float64, device=device)
+    hi = torch.full((len(ids), L, 3), float("-inf"), dtype=torch.float64, device=device)
+    where = {InstanceClouds._key(i): k for k, i in enumerate(ids)}
+    at = [where[InstanceClouds._key(i)] for i in posed]
+    for i in ids:
+        if InstanceClouds._key(i) not in mask_paths:
+            handler.get_extrinsic_matrix(scene_id, i)                      # (the reference's warning for a non-finite pose)
+    C = 6 if with_color else 3
+    if parts:
+        counts[at] = np.concatenate([p[0] for p in parts])
+        idx = torch.tensor(at, dtype=torch.int64, device=device)
+        lo[idx] = torch.cat([p[5] for p in parts])
+        hi[idx] = torch.cat([p[6] for p in parts])
+        xyz = parts[0][2] if len(parts) == 1 else torch.cat([p[2] for p in parts])
+        rgb = None if not with_color else (parts[0][3] if len(parts) == 1 else torch.cat([p[3] for p in parts]))
+        pixel = parts[0][4] if len(parts) == 1 else torch.cat([p[4] for p in parts])
+        rows = _rows(xyz, rgb)
+    else:
+        rows, rgb = torch.zeros((0, C), dtype=torch.float64, device=device), None
+        pixel = torch.zeros((0,), dtype=torch.int32, device=device)
+    return InstanceClouds(ids, counts, rows, pixel, lo, hi, rgb)

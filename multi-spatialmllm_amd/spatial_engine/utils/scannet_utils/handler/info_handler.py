@@ -277,6 +277,19 @@ class SceneInfoHandler:
             raise FileNotFoundError(f"Mask image not found at path: {path}")
         return np.where(mask_image == target_id + 1, 1, 0)
 
+    def instance_clouds(self, scene_id, image_ids=None, with_color=False, device="cuda", num_workers=8, max_dense_bytes=1 << 30):
+        """The clouds of EVERY object of every image in ``image_ids`` (default: all) as one ``mspa.instances.InstanceClouds`` on
+        the device: ``clouds.cloud(image_id, target_id)`` is value for value what ``project_image_to_3d_with_mask(scene_id,
+        image_id, get_instance_mask(scene_id, image_id, target_id), with_color)`` returns, the empty [0, C] result for an object
+        the image does not show included -- from one decode of each file, one K3 exact pass per frame and one stable split by label
+        (``mspa.instances.build``; frames are taken in chunks whose dense xyz table stays under ``max_dense_bytes``).  A frame
+        with a non-finite pose is left out with the reference's warning; its clouds are empty.  Nothing is downloaded.  Where the
+        device path does not apply -- a label above 255, a mask of another size than the colour frames, a mask registered in
+        memory -- the same object is built from the per-object composition and ``mspa.instances.LAST_INSTANCE_CLOUDS`` says why.
+        A missing mask file raises ``FileNotFoundError`` as ``get_instance_mask`` does.  No reference counterpart."""
+        from mspa import instances
+        return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
+
     # ---- resident scene (what the per-scene scripts use) -----------------------------------------
     def color_frames_device(self, scene_id, image_ids=None, device="cuda", num_workers=8):
         """[F, H, W, 3] uint8 RGB device tensor of the scene's colour frames (``image_ids``, default every image), the JPEG files
