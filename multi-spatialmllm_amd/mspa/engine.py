@@ -249,11 +249,15 @@ def inflate_blocks_device(src: torch.Tensor, offsets: torch.Tensor, nbytes: torc
     offsets multiples of 8) -- inflated by one wave each into ``out[k, :block_bytes]`` (mspa_inflate_blocks_device; replaces
     the per-frame zlib.decompress / cv2.imread of the reference, extract_posed_images.py:49-57, info_handler.py:149-155).
     Returns (out [n, pitch] uint8, status [n] int32): status 0 = inflated to exactly ``block_bytes`` with a matching
-    Adler-32; anything else = decode that block on the host.  Only enqueues; read ``status`` after a synchronisation."""
+    Adler-32; anything else = decode that block on the host.  An ``out`` allocated here has the pitch ``block_bytes`` rounded up
+    to 256 and zeros behind ``block_bytes``; a caller's ``out`` keeps what it held there.  Only enqueues; read ``status`` after a
+    synchronisation."""
     _check("src", src, torch.uint8, (None,))
     n = _check_streams(offsets, nbytes)
     if out is None:
         out = torch.empty((n, (int(block_bytes) + 255) // 256 * 256), dtype=torch.uint8, device=src.device)
+        if n and 0 < int(block_bytes) < out.shape[1]:
+            out[:, int(block_bytes):].zero_()             # the kernels write a row's first block_bytes: at most 255 bytes of padding a row
     _check("out", out, torch.uint8, ((n,), (block_bytes,)))
     _require(out.shape[1] % 256 == 0, f"out: a pitch that is a multiple of 256, got {out.shape[1]}")
     status = torch.empty((n,), dtype=torch.int32, device=src.device) if status is None else _check("status", status, torch.int32, ((n,),))
@@ -900,6 +904,11 @@ def scene_overlap(bits: torch.Tensor, want_counts: bool = False):
         ws = _overlap_workspace(F, F, n_words, dev)
         _lib.check(_lib.load().mspa_scene_overlap(_ptr(bits), F, n_words, _ptr(ws), ws.numel() * 4, _ptr(overlap),
                                                   _ptr(inter), _ptr(uni), _stream_ptr()))
+    elif n_pairs:                           # bitsets of no points: no launch has a word to read; every union is empty (CFR:136)
+        overlap.fill_(float("nan"))
+        if want_counts:
+            inter.zero_()
+            uni.zero_()
     return (overlap, inter, uni) if want_counts else overlap
 
 
@@ -913,6 +922,8 @@ def overlap_matrix(bits_a: torch.Tensor, bits_b: torch.Tensor) -> torch.Tensor:
         ws = _overlap_workspace(n_a, n_b, n_words, bits_a.device)
         _lib.check(_lib.load().mspa_overlap_matrix(_ptr(bits_a), n_a, _ptr(bits_b), n_b, n_words, _ptr(ws),
                                                    ws.numel() * 4, _ptr(out), _stream_ptr()))
+    else:
+        out.zero_()                         # (no rows, or bitsets of no points: nothing is launched and nothing intersects)
     return out
 
 
