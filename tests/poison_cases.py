@@ -1,5 +1,6 @@
-"""The device surface of ``mspa.engine`` as cases for tests/test_gpu_poisoned_memory.py: one case per op, or per chain of ops
-that hand state to each other (a producer's unspecified region then reaches its consumer still poisoned).
+"""The device surface of ``mspa.engine`` as cases for tests/test_gpu_poisoned_memory.py and tests/test_gpu_fenced_memory.py: one
+case per op, or per chain of ops that hand state to each other (a producer's unspecified region then reaches its consumer still
+poisoned).
 
 A case has a name, a family (one process per family on the GPU machine), the engine functions it covers, ``build()`` (the
 inputs: real device tensors, built OUTSIDE the patch, so inputs are never poisoned), ``run(inputs)`` (calls the ops and returns
@@ -8,7 +9,9 @@ every tensor the wrappers return, padding included), an optional ``defined`` (po
 helpers the suite already has.
 
 A region is masked out by ``defined`` only where include/mspa.h or the wrapper's docstring already calls it unspecified; the
-sentence is quoted next to the mask.  Importing this module touches no GPU (the completeness check reads ``CASES`` on the CPU).
+sentence is quoted next to the mask.  ``writes`` names the inputs an op is documented to write (the fenced run takes every other
+input to be unchanged afterwards), each with its sentence quoted the same way; no case needs one today.  Importing this module
+touches no GPU (the completeness check reads ``CASES`` on the CPU).
 """
 from __future__ import annotations
 
@@ -39,6 +42,7 @@ class Case:
     run: Callable[[dict], object]
     expect: Callable[[dict, object], None]
     defined: Optional[Dict[str, object]] = None
+    writes: Tuple[str, ...] = ()      # paths into ``inputs`` the op is documented to write (tests/test_gpu_fenced_memory.py), each with its sentence
 
 
 CASES = []
@@ -50,10 +54,10 @@ NOT_COVERED = {
 }
 
 
-def case(name, family, covers, defined=None):
+def case(name, family, covers, defined=None, writes=()):
     """Decorator of a class with static ``build`` / ``run`` / ``expect``: registers it as a Case."""
     def register(cls):
-        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined))
+        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined, tuple(writes)))
         return cls
     return register
 
@@ -1287,6 +1291,35 @@ class _SnappyDecode:
             elif kind in ("writer", "neighbour") or brc == blocks:
                 assert routed == blocks, (name, int(routed), blocks)
         assert taken > 100
+
+
+@case("empty_batches", "visindex", ["snappy_compress_device", "snappy_decompress_device", "snappy_block_starts_device",
+                                    "snappy_decompress_blocks_device", "index_spans_to_lists"])
+class _EmptyBatches:
+    """Tables of no streams and of no rows: the wrappers' early returns, which no other case reaches -- zero-length outputs and the
+    one-element prefix arrays, allocated and returned without a kernel."""
+    @staticmethod
+    def build():
+        return {"src": dev(np.frombuffer(b"no stream is cut out of this", dtype=np.uint8)), "none": _i64([])}
+
+    @staticmethod
+    def run(i):
+        src, none = i["src"], i["none"]
+        return {"compress": engine.snappy_compress_device(src, none, none), "serial": engine.snappy_decompress_device(src, none, none, none),
+                "starts": engine.snappy_block_starts_device(src, none, none, none),
+                "blocks": engine.snappy_decompress_blocks_device(src, none, none, none), "lists": engine.index_spans_to_lists(src, none, none)}
+
+    @staticmethod
+    def expect(i, z):
+        z = host(z)
+        assert z["compress"][0].shape == (0,) and z["compress"][1].tolist() == [0]
+        for key, n_outputs in (("serial", 3), ("blocks", 4)):
+            assert len(z[key]) == n_outputs and z[key][0].shape == (0,) and z[key][1].tolist() == [0], key
+            assert all(t.shape == (0,) for t in z[key][2:]), key
+        assert z["starts"][0].shape == (0,) and z["starts"][1].tolist() == [0] and z["starts"][2].shape == (0,)
+        lists = z["lists"]
+        assert lists["values"].shape == (0,) and lists["offsets"].tolist() == [0] and lists["n_points"] == 1
+        assert len(lists["counts"]) == len(lists["row_status"]) == len(lists["page_status"]) == 0
 
 
 @case("parquet_spans_to_bits_and_lists", "visindex", ["parquet_plain_spans_device", "parquet_dict_spans_device", "index_rows_to_bits",
