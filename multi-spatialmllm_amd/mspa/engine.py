@@ -748,7 +748,9 @@ def pair_reproject(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.Tensor,
                    out: Dict[str, torch.Tensor], rgb: Optional[torch.Tensor] = None, flags: int = 0):
     """Enqueue K3 on the current stream.  depth [F,DH,DW] int16(bits of uint16), mats [F,8,16] f64,
     pairs [B,2] int32, rgb [F,H,W,3] uint8 (only for out['rgba']).  ``out`` comes from
-    alloc_pair_outputs and is filled in place."""
+    alloc_pair_outputs and is filled in place.  Only enqueues, with one exception: under MSPA_PAIR_FAST the first launch
+    on a ``mats`` tensor object (and the first after an in-place write to it) reads the pinhole verdict back
+    (``_require_pinhole``), which waits for the current stream."""
     F, DH, DW, n = _check_pair_inputs(depth, mats, pairs)
     if flags & _lib.PAIR_FAST:
         _require_pinhole(mats)
@@ -790,7 +792,8 @@ def pair_correspondences(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.T
     """Enqueue K3 with the compacted correspondence output: the visibility bitset plus, per 64 x 48 tile of frame 1, the
     frame-2 pixel (xi, yi) of its VISIBLE pixels in (row, column) order.  One fused kernel on whole-tile shapes with
     MSPA_PAIR_FAST (640x480); other shapes / the reference-order mode go through a dense table in ``workspace`` (int32 or
-    uint8, allocated here when not given or too small).  ``out`` from ``alloc_pair_correspondences``."""
+    uint8, allocated here when not given or too small).  ``out`` from ``alloc_pair_correspondences``.  Only enqueues, with
+    ``pair_reproject``'s exception: the pinhole verdict of a ``mats`` object that MSPA_PAIR_FAST sees for the first time."""
     lib = _lib.load()
     F, DH, DW, n = _check_pair_inputs(depth, mats, pairs)
     if flags & _lib.PAIR_FAST:
@@ -929,7 +932,8 @@ def overlap_matrix(bits_a: torch.Tensor, bits_b: torch.Tensor) -> torch.Tensor:
 
 def bitset_csr(bits: torch.Tensor):
     """K9: rows of a bit matrix -> CSR of their set bits.  bits [R, n_words] int64 (device) -> (offsets [R+1] int64,
-    indices [nnz] int32), both on the device; row r's set-bit positions, ascending, are indices[offsets[r]:offsets[r+1]]."""
+    indices [nnz] int32), both on the device; row r's set-bit positions, ascending, are indices[offsets[r]:offsets[r+1]].
+    One small read-back (the number of set bits: the size to allocate)."""
     lib = _lib.load()
     R, n_words = _check_bits("bits", bits)
     dev = bits.device
@@ -1810,8 +1814,9 @@ def object_extents(vis_bits: torch.Tensor, xyz: torch.Tensor, obj_offsets: torch
 
 
 def track_pair_distances(world: torch.Tensor, points: Sequence[int], visible_frames: Sequence[np.ndarray]):
-    """Enqueue K5c: for each selected point, the distances between its world positions in every two of its visible
-    frames (i < j, row-major).  Returns a list of float64 NumPy arrays, one per point (n(n-1)/2 entries)."""
+    """K5c: for each selected point, the distances between its world positions in every two of its visible
+    frames (i < j, row-major).  Returns a list of float64 NumPy arrays, one per point (n(n-1)/2 entries).  Synchronises the
+    current stream: four small tables go up from pageable memory and the distances come back to the host."""
     T, P = _check_tracks("world", world)
     S = len(points)
     if S == 0:
@@ -1930,7 +1935,8 @@ def track_pair_resolve(state: Dict[str, torch.Tensor], bin_counts: torch.Tensor,
                        future_frame_windows: float = 1e8) -> torch.Tensor:
     """Enqueue K5d's resolve: picks [k,3] i32 ON THE HOST (selected point, class 0..9 a bin / 10 static, rank) and class_counts
     [s,11] i32 on the host (the classes' sizes: a rank outside them is refused before any launch) -> [k,2] i32 (frame1, frame2) on
-    the device.  ``payload`` is ``track_pair_order``'s."""
+    the device.  ``payload`` is ``track_pair_order``'s.  The picks go up from pageable memory, which waits for the current stream:
+    of the K5d calls this one does not return before the work in front of it has run."""
     n, T = _check_track_state(state)
     _check("bin_counts", bin_counts, torch.int32, (n, _lib.TRACK_BINS))
     s = _check("rows", rows, torch.int32, (None,)).shape[0]
@@ -2009,7 +2015,8 @@ def prep_align(spans: dict, vertices: torch.Tensor, axis_align: torch.Tensor) ->
 def prep_objects(spans: dict, instance_ids: torch.Tensor, vertices: torch.Tensor, aligned: torch.Tensor, n_objects: Sequence[int]) -> dict:
     """Enqueue ``mspa_prep_objects`` and K9 on its membership rows.  ``n_objects[s]``: object slots of scene s (slot k - 1 <-> id k).
     Returns device tensors: count [M], lo / hi_unaligned and lo / hi_aligned [M, 3] float64, unique [S], and the stable split as CSR
-    (``offsets`` [M + 1] int64, ``indices`` int32: scene-local vertex numbers, ascending within an object)."""
+    (``offsets`` [M + 1] int64, ``indices`` int32: scene-local vertex numbers, ascending within an object).  Synchronises the
+    current stream: the slot offsets go up from pageable memory and ``bitset_csr`` reads its total back."""
     S, N = _check_spans(spans)
     _require(len(n_objects) == S, f"n_objects: one per scene ({S}), got {len(n_objects)}")
     _check("instance_ids", instance_ids, torch.int32, (N,))

@@ -1,6 +1,6 @@
-"""The device surface of ``mspa.engine`` as cases for tests/test_gpu_poisoned_memory.py and tests/test_gpu_fenced_memory.py: one
-case per op, or per chain of ops that hand state to each other (a producer's unspecified region then reaches its consumer still
-poisoned).
+"""The device surface of ``mspa.engine`` as cases for tests/test_gpu_poisoned_memory.py, tests/test_gpu_fenced_memory.py and
+tests/test_gpu_stream_order.py: one case per op, or per chain of ops that hand state to each other (a producer's unspecified
+region then reaches its consumer still poisoned).
 
 A case has a name, a family (one process per family on the GPU machine), the engine functions it covers, ``build()`` (the
 inputs: real device tensors, built OUTSIDE the patch, so inputs are never poisoned), ``run(inputs)`` (calls the ops and returns
@@ -10,7 +10,9 @@ helpers the suite already has.
 
 A region is masked out by ``defined`` only where include/mspa.h or the wrapper's docstring already calls it unspecified; the
 sentence is quoted next to the mask.  ``writes`` names the inputs an op is documented to write (the fenced run takes every other
-input to be unchanged afterwards), each with its sentence quoted the same way; no case needs one today.  Importing this module
+input to be unchanged afterwards), each with its sentence quoted the same way; no case needs one today.  ``enqueue_only`` holds
+the sentence that promises that no covered function synchronises the host (tests/test_gpu_stream_order.py holds the case to
+it); where it is None, a comment at the case quotes the read-back that the documents name instead.  Importing this module
 touches no GPU (the completeness check reads ``CASES`` on the CPU).
 """
 from __future__ import annotations
@@ -43,6 +45,7 @@ class Case:
     expect: Callable[[dict, object], None]
     defined: Optional[Dict[str, object]] = None
     writes: Tuple[str, ...] = ()      # paths into ``inputs`` the op is documented to write (tests/test_gpu_fenced_memory.py), each with its sentence
+    enqueue_only: Optional[str] = None    # the documents' promise that no covered function synchronises the host (tests/test_gpu_stream_order.py)
 
 
 CASES = []
@@ -54,10 +57,71 @@ NOT_COVERED = {
 }
 
 
-def case(name, family, covers, defined=None, writes=()):
+# The sentence with which mspa/engine.py (a wrapper's docstring) or include/mspa.h promises that a function only enqueues on the
+# current stream: no read-back, no upload from pageable memory, no host synchronisation of any kind.  A wrapper without a sentence
+# of its own that does nothing but check its arguments, allocate and call the C entry point stands under the header's general one.
+# A function that is absent here documents a read-back instead (quoted at its cases).  ``Case.enqueue_only`` is set where every
+# covered function is listed AND ``run`` itself does nothing else on the host (``HOST_STEPS`` names the cases where it does);
+# tests/test_stream_util_cpu.py holds the three tables against each other and every sentence against the two files, word for word
+# (line breaks folded).
+C_ABI = "Calls enqueue work and return; they never synchronise."
+ENQUEUES = {
+    "vertex_visibility": "Enqueue K1.",
+    "check_visibility": C_ABI,
+    "pair_overlap": "Enqueue K2 on K1's bitsets.",
+    "scene_overlap": "Enqueue the tiled K2 over ALL pairs i < j of a scene's bitsets",
+    "overlap_matrix": "Enqueue the tiled K2 on a rectangle",
+    "bits_transpose": C_ABI,
+    "select_common_point": "Enqueue K6a.",
+    "project_samples": "Enqueue K6b.",
+    "object_extents": "Enqueue K8",
+    "extract_yaw_pitch": C_ABI,
+    "pair_pose": "Enqueue K4.",
+    "track_to_world": "Enqueue K5a.",
+    "track_displacement": "Enqueue K5b.",
+    "track_rigidity_loss": "Enqueue K7",
+    "track_rigidity_loss_batch": "Enqueue K7 for equal-shape track blocks in one launch",
+    "track_linkage": "Enqueue only: the status is a device tensor like the rest.",
+    "track_pair_stats": "Enqueue K5d's statistics.",
+    "track_pair_bin_counts": "Enqueue K5d's second pass",
+    "track_pair_sort": "Enqueue K5d's segmented sort on its own, in place",
+    "track_pair_order": "Enqueue K5d's order",
+    "inflate_blocks_device": "Only enqueues; read ``status`` after a synchronisation.",
+    "png_unfilter_device": C_ABI,
+    "png_unfilter8_device": C_ABI,
+    "jpeg_decode_device": "Only enqueues; read ``status`` after a synchronisation.",
+    "jpeg_decode_luma_device": "Same arguments, same (out, status) contract; only enqueues.",
+    "laplacian_moments": "Only enqueues.",
+    "resize_rgb_device": "Only enqueues on the current stream otherwise.",
+    "draw_spans_device": C_ABI,
+    "blend_masks_device": C_ABI,
+    "jpeg_encode_device": "Only enqueues; read ``nbytes`` after a synchronisation.",
+    "png_encode_device": "Runs on the current torch stream and only enqueues",
+    "parquet_plain_spans_device": "Only enqueues.",
+    "parquet_dict_spans_device": "Only enqueues.",
+    "rle_hybrid_expand_device": "One lane per value; only enqueues.",
+    "pair_bin_codes": "Only enqueues.",
+    "pair_partition": "Only enqueues.",
+    "index_lists_pick": "Only enqueues: the caller reads ``status`` before a vertex goes anywhere that indexes with it",
+    "prep_labels": "Enqueue ``mspa_prep_labels``",
+    "prep_align": "Enqueue ``mspa_prep_align``",
+}
+
+# pair_reproject's promise holds from a table's second launch on (its cases build a new table every time and so have no
+# ``enqueue_only``); tests/test_gpu_stream_order.py runs them once more on a table whose verdict is known.
+PAIR_REPROJECT_SEEN_TABLE = "Only enqueues, with one exception: under MSPA_PAIR_FAST the first launch"
+
+# Cases whose covered functions all only enqueue, but whose ``run`` does more on the host than call them.
+HOST_STEPS = {
+    "heads_end_to_end": "the heads read samples, records and the visibility index back; the prefetcher uploads scenes",
+    "prefetch_packed_scenes": "ScenePrefetcher packs on the host, uploads and hands each scene out after its slot's decode",
+}
+
+
+def case(name, family, covers, defined=None, writes=(), enqueue_only=None):
     """Decorator of a class with static ``build`` / ``run`` / ``expect``: registers it as a Case."""
     def register(cls):
-        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined, tuple(writes)))
+        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined, tuple(writes), enqueue_only))
         return cls
     return register
 
@@ -132,7 +196,7 @@ def scene_on_device(sc, ids):
 K1_WANTS = {"all": ("bits", "mask", "uv", "depth", "count"), "lists": ("bits", "mask", "count"), "bits": ("bits",), "count": ("count",)}
 
 
-@case("vertex_visibility", "k1k2", ["vertex_visibility"])
+@case("vertex_visibility", "k1k2", ["vertex_visibility"], enqueue_only=ENQUEUES["vertex_visibility"])
 class _VertexVisibility:
     @staticmethod
     def build():
@@ -169,7 +233,7 @@ class _VertexVisibility:
                     assert nan_equal_bits(res["uv"][k], uvc) and nan_equal_bits(res["depth"][k], dc), key
 
 
-@case("check_visibility", "k1k2", ["check_visibility"])
+@case("check_visibility", "k1k2", ["check_visibility"], enqueue_only=ENQUEUES["check_visibility"])
 class _CheckVisibility:
     @staticmethod
     def build():
@@ -208,7 +272,7 @@ def overlap_reference(masks):
 def _overlap_case(name, F, n_bits, unaligned=False):
     """F rows of n_bits bits, rows 3 and F // 2 empty (their pair: an empty union, NaN).  An odd word count takes the popcount tile
     kernel, an even one in a 16-byte aligned table the matrix-core one; ``unaligned`` puts an even count 8 bytes past a boundary."""
-    @case(name, "k1k2", ["pair_overlap", "scene_overlap", "overlap_matrix"])
+    @case(name, "k1k2", ["pair_overlap", "scene_overlap", "overlap_matrix"], enqueue_only=ENQUEUES["pair_overlap"])
     class _Overlap:
         @staticmethod
         def build():
@@ -253,7 +317,7 @@ _overlap_case("overlap_even_words_8320", 70, 8320)                      # 130 wo
 _overlap_case("overlap_even_words_unaligned", 33, 66 * 64, unaligned=True)   # an even count 8 bytes past a 16-byte boundary
 
 
-@case("overlap_no_words", "k1k2", ["scene_overlap", "overlap_matrix"])
+@case("overlap_no_words", "k1k2", ["scene_overlap", "overlap_matrix"], enqueue_only=ENQUEUES["scene_overlap"])
 class _OverlapNoWords:
     """Bitsets of no points (n_words == 0): every union is empty -> NaN, every intersection 0.  No kernel has a word to read, so
     the wrappers have to write the results themselves (pair_overlap refuses such a table: it has no address)."""
@@ -274,7 +338,7 @@ class _OverlapNoWords:
 
 
 def _bitset_case(name, R, n_bits):
-    @case(name, "k1k2", ["bitset_csr", "bits_transpose"])
+    @case(name, "k1k2", ["bitset_csr", "bits_transpose"])          # bitset_csr: "One small read-back (the number of set bits: the size to allocate)"
     class _Bitset:
         @staticmethod
         def build():
@@ -311,7 +375,7 @@ _bitset_case("bitset_5x700", 5, 700)
 _bitset_case("bitset_70x8320", 70, 8320)
 
 
-@case("bitset_empty", "k1k2", ["bitset_csr", "bits_transpose"])
+@case("bitset_empty", "k1k2", ["bitset_csr", "bits_transpose"])          # bitset_csr's read-back of the number of set bits
 class _BitsetEmpty:
     @staticmethod
     def build():
@@ -331,7 +395,7 @@ class _BitsetEmpty:
 
 
 def _common_point_case(name, F, n_bits):
-    @case(name, "k1k2", ["select_common_point"])
+    @case(name, "k1k2", ["select_common_point"], enqueue_only=ENQUEUES["select_common_point"])
     class _CommonPoint:
         @staticmethod
         def build():
@@ -364,7 +428,7 @@ _common_point_case("select_common_point_700", 9, 700)
 _common_point_case("select_common_point_8320", 9, 8320)                # 130 words: a lane owns more than one word, with a carry
 
 
-@case("project_samples", "k1k2", ["project_samples"])
+@case("project_samples", "k1k2", ["project_samples"], enqueue_only=ENQUEUES["project_samples"])
 class _ProjectSamples:
     @staticmethod
     def build():
@@ -391,7 +455,7 @@ class _ProjectSamples:
         assert 0 < ok.sum() < len(ok)
 
 
-@case("object_extents", "k1k2", ["object_extents"])
+@case("object_extents", "k1k2", ["object_extents"], enqueue_only=ENQUEUES["object_extents"])
 class _ObjectExtents:
     @staticmethod
     def build():
@@ -461,6 +525,8 @@ def _k3_references(i):
 
 
 def _pair_reproject_case(shape):
+    # pair_reproject: "under MSPA_PAIR_FAST the first launch on a ``mats`` tensor object [...] reads the pinhole verdict back" -- and
+    # build() makes a new table every time
     @case(f"pair_reproject_{shape}", "k3", ["pair_reproject"])
     class _PairReproject:
         @staticmethod
@@ -508,6 +574,7 @@ def _cpix_defined(which):
 
 
 def _pair_correspondences_case(shape):
+    # correspondences_rowmajor: torch.nonzero reads the number of visible pixels back ("torch indexing as plumbing")
     @case(f"pair_correspondences_{shape}", "k3", ["pair_correspondences", "correspondences_rowmajor"],
           defined={"fast/out/cpix": _cpix_defined("fast"), "reference_order/out/cpix": _cpix_defined("reference_order"),
                    "stream/out/cpix": _cpix_defined("stream")})
@@ -552,7 +619,7 @@ def _f64_ok(a, b):
     return same_f64(a, b) or close_f64(a, b, rtol=1e-12, scale=1e-9)
 
 
-@case("extract_yaw_pitch", "tracks", ["extract_yaw_pitch"])
+@case("extract_yaw_pitch", "tracks", ["extract_yaw_pitch"], enqueue_only=ENQUEUES["extract_yaw_pitch"])
 class _YawPitch:
     @staticmethod
     def build():
@@ -580,7 +647,7 @@ class _YawPitch:
         assert abs(yaw[-1] + 90.0) < 1e-12 and abs(pitch[-1]) < 1e-12
 
 
-@case("pair_pose", "tracks", ["pair_pose"])
+@case("pair_pose", "tracks", ["pair_pose"], enqueue_only=ENQUEUES["pair_pose"])
 class _PairPose:
     @staticmethod
     def build():
@@ -623,6 +690,7 @@ def small_tracks():
     return tr, xyz
 
 
+# track_pair_distances: "four small tables go up from pageable memory and the distances come back to the host"
 @case("track_geometry", "tracks", ["track_to_world", "track_displacement", "track_pair_distances"])
 class _TrackGeometry:
     """K5a -> K5b and K5c, which read K5a's world positions."""
@@ -687,6 +755,7 @@ class _TrackGeometry:
         assert n_checked > 150
 
 
+# track_rigid_groups: "only the labels (4 P bytes) and the status come back"
 @case("track_rigidity", "tracks", ["track_rigidity_loss", "track_rigidity_loss_batch", "track_linkage", "track_rigid_groups"])
 class _TrackRigidity:
     """K7 (single and batched) -> K7b -> the groups: the loss matrix, the linkage workspace and the labels all stay on the device."""
@@ -742,6 +811,8 @@ def _first_v(name):
 _ROW0 = (slice(0, 1),)
 
 
+# track_pair_resolve: "The picks go up from pageable memory, which waits for the current stream" (and run() reads the statistics back
+# between the calls, as heads._mine_pairs_device does)
 @case("track_mining_chain", "mining", ["track_pair_stats", "track_pair_bin_counts", "track_pair_order", "track_pair_resolve", "track_pair_sort"],
       defined={"state/frames": _first_v("frames"), "state/positions": _first_v("positions"), "keys": _ROW0, "payload": _ROW0})
 class _TrackMining:
@@ -833,7 +904,7 @@ def _png_case(name, bits, h, w):
     row = w * (2 if bits == 16 else 1) + 1
 
     @case(name, "ingest", ["inflate_blocks_device", "png_unfilter_device" if bits == 16 else "png_unfilter8_device"],
-          defined={"raw": _status_rows(("status_inflate",), 2), "images": _status_rows(("status",), 3)})
+          defined={"raw": _status_rows(("status_inflate",), 2), "images": _status_rows(("status",), 3)}, enqueue_only=ENQUEUES["inflate_blocks_device"])
     class _Png:
         @staticmethod
         def build():
@@ -886,7 +957,7 @@ _png_case("mask_png_70x130", 8, 70, 130)
 
 def _jpeg_case(name, hw):
     @case(name, "ingest", ["jpeg_decode_device", "jpeg_decode_luma_device"],
-          defined={"rgb/0": _status_rows(("rgb", 1), 4), "luma/0": _status_rows(("luma", 1), 3)})
+          defined={"rgb/0": _status_rows(("rgb", 1), 4), "luma/0": _status_rows(("luma", 1), 3)}, enqueue_only=ENQUEUES["jpeg_decode_device"])
     class _Jpeg:
         @staticmethod
         def build():
@@ -932,7 +1003,7 @@ _jpeg_case("jpeg_17x33", (17, 33))
 _jpeg_case("jpeg_61x83", (61, 83))
 
 
-@case("laplacian_moments", "ingest", ["laplacian_moments"])
+@case("laplacian_moments", "ingest", ["laplacian_moments"], enqueue_only=ENQUEUES["laplacian_moments"])
 class _Laplacian:
     @staticmethod
     def build():
@@ -959,7 +1030,7 @@ class _Laplacian:
         assert not z["small"][1].any()
 
 
-@case("instance_split", "ingest", ["instance_split"])
+@case("instance_split", "ingest", ["instance_split"])          # "reading the counts is the call's one synchronisation"
 class _InstanceSplit:
     @staticmethod
     def build():
@@ -989,7 +1060,7 @@ class _InstanceSplit:
         assert not counts[1].any() and not counts[:, 5].any() and counts[0, 4] > 0 and z["nothing"][1][-1] == 0
 
 
-@case("knn_mean_distance", "ingest", ["knn_mean_distance"])
+@case("knn_mean_distance", "ingest", ["knn_mean_distance"])          # "read back from a device sort: synchronises once"
 class _Knn:
     CLOUDS = (("uniform", 65, 20), ("uniform", 1000, 20), ("clusters", 1000, 5), ("identical", 200, 20), ("uniform", 19, 20))
 
@@ -1016,7 +1087,7 @@ class _Knn:
         assert np.array_equal(z[-1], z[0][0]) and (z[3][0] == 0).all()
 
 
-@case("resize_rgb_device", "ingest", ["resize_rgb_device"])
+@case("resize_rgb_device", "ingest", ["resize_rgb_device"], enqueue_only=ENQUEUES["resize_rgb_device"])
 class _Resize:
     PAIRS = (((17, 33), (61, 83), "bicubic"), ((61, 83), (17, 33), "bicubic"), ((61, 83), (30, 83), "bilinear"), ((17, 33), (17, 70), "bilinear"),
              ((17, 33), (17, 33), "bicubic"))               # both passes (a workspace), one pass each way, a copy
@@ -1054,7 +1125,7 @@ def _file_bytes(which, round_to=1):
 
 
 @case("annotate_and_encode_jpeg", "export", ["draw_spans_device", "blend_masks_device", "jpeg_encode_device"],
-      defined={"420/0": _file_bytes("420"), "444/0": _file_bytes("444"), "422/0": _file_bytes("422")})
+      defined={"420/0": _file_bytes("420"), "444/0": _file_bytes("444"), "422/0": _file_bytes("422")}, enqueue_only=ENQUEUES["jpeg_encode_device"])
 class _AnnotateJpeg:
     """draw_spans_device -> blend_masks_device on per-job copies (allocated under the patch, as DeviceAnnotator's are) ->
     jpeg_encode_device: the annotated-image export."""
@@ -1108,7 +1179,8 @@ class _AnnotateJpeg:
                 assert files[n, :nbytes[n]].tobytes() == encode(want[n], quality=q, subsampling=sub), (key, n)
 
 
-@case("png_encode_device", "export", ["png_encode_device"], defined={"small/0": _file_bytes("small", 4), "large/0": _file_bytes("large", 4)})
+@case("png_encode_device", "export", ["png_encode_device"], defined={"small/0": _file_bytes("small", 4), "large/0": _file_bytes("large", 4)},
+      enqueue_only=ENQUEUES["png_encode_device"])
 class _PngEncode:
     @staticmethod
     def build():
@@ -1145,6 +1217,7 @@ def _i64(a):
     return dev(np.asarray(a, dtype=np.int64))
 
 
+# format_lists_device: "one small read-back: the size to allocate"; parquet_string_pages_device: "Synchronises the current stream."
 @case("index_text_and_pages", "visindex", ["format_lists_device", "parquet_string_pages_device"])
 class _IndexText:
     """format_lists_device (integers, then tokens) -> one string column -> parquet_string_pages_device (PLAIN pages, Snappy by the
@@ -1198,7 +1271,7 @@ class _IndexText:
         assert len(z["pages_4k"]["compressed"]) > 5 and len(z["pages_1m"]["compressed"]) == 1
 
 
-@case("snappy_compress_device", "visindex", ["snappy_compress_device"])
+@case("snappy_compress_device", "visindex", ["snappy_compress_device"])          # "Three small read-backs (block count, total, the kernels' flag)"
 class _SnappyCompress:
     @staticmethod
     def build():
@@ -1239,6 +1312,7 @@ def _taken_bytes(which):
     return mask
 
 
+# each of the three: "One small read-back (the size(s) to allocate)"
 @case("snappy_decode", "visindex", ["snappy_decompress_device", "snappy_block_starts_device", "snappy_decompress_blocks_device"],
       defined={"serial/0": _taken_bytes("serial"), "blocks/0": _taken_bytes("blocks")})
 class _SnappyDecode:
@@ -1293,6 +1367,7 @@ class _SnappyDecode:
         assert taken > 100
 
 
+# the early returns read nothing back, but the functions document read-backs (snappy_*: above; index_spans_to_lists: "Synchronises")
 @case("empty_batches", "visindex", ["snappy_compress_device", "snappy_decompress_device", "snappy_block_starts_device",
                                     "snappy_decompress_blocks_device", "index_spans_to_lists"])
 class _EmptyBatches:
@@ -1322,6 +1397,8 @@ class _EmptyBatches:
         assert len(lists["counts"]) == len(lists["row_status"]) == len(lists["page_status"]) == 0
 
 
+# index_rows_to_bits: "Synchronises (three or four small read-backs)"; index_spans_to_lists: "Synchronises: the pipeline's two totals and ONE
+# read-back of statuses, counts and width"
 @case("parquet_spans_to_bits_and_lists", "visindex", ["parquet_plain_spans_device", "parquet_dict_spans_device", "index_rows_to_bits",
                                                       "index_spans_to_lists", "index_rows_to_lists", "index_lists_pick", "index_spans_to_bits"])
 class _IndexRows:
@@ -1434,6 +1511,7 @@ class _IndexRows:
         assert z["no_rows"]["bits"].shape == (0, 7)
 
 
+# rle_hybrid_runs_device: "A counting launch, ONE small read-back (the sizes to allocate)"
 @case("rle_hybrid", "visindex", ["rle_hybrid_runs_device", "rle_hybrid_expand_device"])
 class _RleHybrid:
     @staticmethod
@@ -1471,6 +1549,7 @@ class _RleHybrid:
         assert z["outside"]["status"].tolist() == [_lib.MSPA_EINVAL] * 2 and z["outside_values"].tolist() == [-1] * 6
 
 
+# parquet_double_columns_device: "Two small read-backs."
 @case("pair_table", "visindex", ["parquet_double_columns_device", "pair_bin_codes", "pair_partition"])
 class _PairTable:
     """pairtable.PairTable on small files -- dictionary-coded v1 pages, v2 pages, PLAIN pages of the project's own writer, a file of
@@ -1529,6 +1608,7 @@ class _PairTable:
 # ScanNet prep (K11)
 # =====================================================================================================================
 
+# prep_objects: "the slot offsets go up from pageable memory and ``bitset_csr`` reads its total back"
 @case("scan_prep", "scanprep", ["prep_labels", "prep_align", "prep_objects"])
 class _ScanPrep:
     """One ragged window -- 1, 65, 130 (no objects) and 1001 vertices -- through prep_align, prep_labels and prep_objects (with K9 on
@@ -1601,7 +1681,7 @@ class _ScanPrep:
         assert (b["lo_unaligned"] == np.inf).all() and (b["hi_aligned"] == -np.inf).all()
 
 
-@case("parse_int_lists_device", "scanprep", ["parse_int_lists_device"])
+@case("parse_int_lists_device", "scanprep", ["parse_int_lists_device"])          # "one small read-back: the size to allocate"; offsets and status return on the host
 class _ParseIntLists:
     DAMAGED = {1: b"1,,2", 3: b"1 2", 4: b"01,5", 6: b"2147483648", 7: b"12345678901", 9: b"1,2,x", 10: b"-4,5", 12: b",1", 13: b"1,", 15: b"1.5"}
 
@@ -1671,6 +1751,7 @@ def _head_records(scene, sc, rows):
     return out
 
 
+# HOST_STEPS: the heads and the prefetcher work on the host between the launches
 @case("heads_end_to_end", "e2e", ["vertex_visibility", "select_common_point", "project_samples", "pair_pose"])
 class _HeadsEndToEnd:
     """A scene uploaded directly (SceneOnDevice) and handed out by a ScenePrefetcher whose upload slots are allocated under the
@@ -1764,6 +1845,7 @@ class _HeadsEndToEnd:
         assert int(np.sum(pages["num_values"])) == len(ids) + sc.points.shape[0] and len(pages["chunk"]) == int(np.sum(pages["compressed"]))
 
 
+# index_rows_to_bits / index_rows_to_lists: "Synchronises"
 @case("index_readers", "e2e", ["index_rows_to_bits", "index_rows_to_lists", "index_lists_pick", "snappy_decompress_blocks_device"])
 class _IndexReaders:
     """visindex.SceneRowGroups on the edge file of tests/index_lists_util.py (4 KiB pages, one row 190 KB long): the scene's rows
@@ -1807,6 +1889,7 @@ class _IndexReaders:
         LU.check_edge_lists(i["lists_of_run"][0])           # the zero run's lists object against json.loads, in full
 
 
+# HOST_STEPS: packing, upload and the hand-over of each slot
 @case("prefetch_packed_scenes", "e2e", ["inflate_blocks_device", "png_unfilter_device"])
 class _PrefetchPacked:
     """Scenes whose depth frames arrive as PNG files, packed (pinned staging) and decoded on the device inside the upload slots: two
