@@ -1091,6 +1091,57 @@ int mspa_knn_mean_distance_device(const double *xyz_dev, int64_t n, int32_t k, c
 int mspa_knn_mean_distance_host(const double *xyz_host, int64_t n, int32_t k, double *mean_host, int32_t *evals_host);
 
 /*
+ * The same search and the statistical-outlier rule for a RAGGED BATCH of clouds in a fixed number of launches -- csrc/cloud_segments.hip,
+ * rule in csrc/cloud_segments_core.h on top of csrc/knn_grid_core.h.  A batch is xyz [N, 3] f64 plus offsets [S + 1] int64
+ * (offsets[0] = 0, ascending, offsets[S] = N <= 2^30, S <= MSPA_SEGMENTS_MAX); segment s is the rows offsets[s] .. offsets[s + 1],
+ * empty segments allowed anywhere.  Per segment the grid is the one mspa_knn_grid_host builds for that cloud alone, so mean and
+ * evals equal mspa_knn_mean_distance_device's on the segment bit for bit.  Every device entry point takes the offsets (and the
+ * grids) TWICE: the host copy, which it checks before anything is enqueued, and the device copy the kernels read, which the caller
+ * uploads and which must hold the same bytes.
+ *   mspa_knn_segments_tables_host          offsets, k -> cell_base [S + 1] int64: the exclusive prefix of the most cells a
+ *                                          non-empty segment's grid can have.  A row's sort key is cell_base[s] + its cell.
+ *   mspa_knn_segments_grids_host           boxes lo / hi [S, 3] (per-axis order statistics of rank n_s / 100 and n_s - 1 - n_s / 100
+ *                                          of each segment; an empty segment's box is not read) -> grids [S] records of
+ *                                          MSPA_KNN_GRID_BYTES (an empty segment's: zeros).
+ *   mspa_knn_segments_cells_device         -> keys_dev [N] int64, monotone in the segment.  The caller sorts them STABLY and passes
+ *                                          the permutation on as order_dev [N] int64.
+ *   mspa_knn_segments_mean_distance_device -> mean_dev [N] f64 and, when evals_dev is not null, the distances evaluated per row
+ *                                          [N] int32.  Every entry of order_dev is clamped into [0, N) and then into the segment
+ *                                          of its slot: an order_dev that is no such permutation gives wrong means, never an access
+ *                                          outside the buffers.  workspace: mspa_knn_segments_workspace_bytes(), 16-byte aligned.
+ *   mspa_outlier_segments_device           avg_dev [N], xyz_dev [N, 3] -> keep_dev [N] uint8 (1: the row stays) and per segment
+ *                                          kept_dev [S] int64, mean_dev / sd_dev / thr_dev [S] f64, lo_dev / hi_dev [S, 3] f64, the
+ *                                          extents of the kept rows (+inf / -inf where none stays).  With P the rows of a segment of
+ *                                          n whose avg > 0: mean = sum_P avg / n, sd = sqrt(sum_P (avg - mean)^2 / (n - 1)), thr =
+ *                                          mean + std_ratio * sd, a row stays iff 0 < avg < thr; n = 0 has no mean, n < 2 no sd and no
+ *                                          thr (one quiet NaN) and keeps nothing.  The two sums are taken in the order
+ *                                          csrc/cloud_segments_core.h states (256 lane sums, folded by halving strides): not
+ *                                          torch.sum's.  One workgroup per segment, no atomics.
+ *   mspa_knn_segments_mean_distance_host,
+ *   mspa_outlier_segments_host             the same two steps on the CPU through the same headers: the device's twins for tests on a
+ *                                          machine without a GPU, not a fallback.
+ */
+#define MSPA_SEGMENTS_MAX (1 << 24)
+int mspa_knn_segments_tables_host(const int64_t *offsets_host, int64_t S, int32_t k, int64_t *cell_base_out);
+int mspa_knn_segments_grids_host(const double *lo, const double *hi, const int64_t *offsets_host, int64_t S, int32_t k, void *grids_out);
+int64_t mspa_knn_segments_workspace_bytes(const int64_t *offsets_host, int64_t S, int32_t k);
+int mspa_knn_segments_cells_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, const void *grids_host,
+                                   const int64_t *offsets_dev, const void *grids_dev, const int64_t *cell_base_dev, int64_t *keys_dev,
+                                   mspa_stream_t stream);
+int mspa_knn_segments_mean_distance_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, int32_t k, const void *grids_host,
+                                           const int64_t *offsets_dev, const void *grids_dev, const int64_t *cell_base_dev,
+                                           const int64_t *order_dev, double *mean_dev, int32_t *evals_dev, void *workspace,
+                                           int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_outlier_segments_device(const double *avg_dev, const double *xyz_dev, const int64_t *offsets_host, int64_t S, double std_ratio,
+                                 const int64_t *offsets_dev, uint8_t *keep_dev, int64_t *kept_dev, double *mean_dev, double *sd_dev,
+                                 double *thr_dev, double *lo_dev, double *hi_dev, mspa_stream_t stream);
+int mspa_knn_segments_mean_distance_host(const double *xyz_host, const int64_t *offsets_host, int64_t S, int32_t k, double *mean_host,
+                                         int32_t *evals_host);
+int mspa_outlier_segments_host(const double *avg_host, const double *xyz_host, const int64_t *offsets_host, int64_t S, double std_ratio,
+                               uint8_t *keep_host, int64_t *kept_host, double *mean_host, double *sd_host, double *thr_host,
+                               double *lo_host, double *hi_host);
+
+/*
  * Instance-mask decode ON THE DEVICE (csrc/mask_ingest.hip, rule in csrc/png_unfilter8_core.h): the 8-bit twin of the depth-frame
  * decode above, for ScanNet's `instance-filt/<image>.png` label images (`cv2.imread(path, -1)` per (image, object) in the
  * reference's get_instance_mask).  The inflate in front of the un-filter is mspa_inflate_blocks_device with block_bytes = h * (w + 1).

@@ -18,6 +18,7 @@ PAIR_WORD_STRIPES = 0x200      # retired: accepted and ignored (the word-stripe 
 CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
 JPEG_DESC_BYTES = 4224
 KNN_GRID_BYTES, KNN_MAX_K = 112, 64      # csrc/knn_grid_core.h: sizeof(Grid), kMaxK
+SEGMENTS_MAX = 1 << 24                   # csrc/cloud_segments_core.h: kMaxSegments
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
@@ -218,6 +219,17 @@ _SIGNATURES = {
     "mspa_knn_cells_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mspa_knn_mean_distance_device": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mspa_knn_mean_distance_host": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "mspa_knn_segments_tables_host": (c_int, [c_void_p, c_int64, c_int32, c_void_p]),
+    "mspa_knn_segments_grids_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "mspa_knn_segments_workspace_bytes": (c_int64, [c_void_p, c_int64, c_int32]),
+    "mspa_knn_segments_cells_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_knn_segments_mean_distance_device": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_outlier_segments_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_knn_segments_mean_distance_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "mspa_outlier_segments_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
     "mspa_png_pack_idat8_host": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                          POINTER(c_int64), c_int32]),
     "mspa_png_unfilter8_device": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,248 @@
+"""Cleaning and boxing a ragged batch of clouds on the device: the k-nearest mean distance, the statistical-outlier rule and the
+kept rows' extents for every segment at once (csrc/cloud_segments.hip, rule in csrc/cloud_segments_core.h).
+
+A batch is ``rows`` [N, C >= 3] on the device plus ``offsets`` [S + 1], a HOST int64 array: ascending, ``offsets[0] = 0``,
+``offsets[S] = N``; segment s is ``rows[offsets[s]:offsets[s + 1]]``, and empty segments are allowed anywhere.  The number of
+launches and of read-backs of each function does not depend on S.  Per segment the search is the single-cloud op's
+(``engine.knn_mean_distance``) bit for bit; the two sums of the rule follow the order csrc/cloud_segments_core.h states, which
+is not ``torch.sum``'s, so a threshold may differ from ``ops.remove_statistical_outliers``' in the last bits.
+
+torch is plumbing, as in ``mspa.engine``: the segmented order statistics (two sorts), the one sort of the keys, ``nonzero`` and
+``index_select``.  Host tables go up through pinned memory without a host wait.
+"""
+from __future__ import annotations
+
+
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import _check, _ptr, _require, _stream_ptr, _workspace
+
+
+def _offsets(offsets, n_rows: int) -> np.ndarray:
+    """The host offsets of a batch of ``n_rows`` rows, checked: int64 [S + 1], ascending from 0 to ``n_rows``."""
+    if isinstance(offsets, torch.Tensor):
+        _require(not offsets.is_cuda, "offsets: a host array (the launch shapes come from it)")
+        offsets = offsets.numpy()
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    _require(off.ndim == 1 and off.size >= 1, f"offsets: [S + 1], got {list(off.shape)}")
+    _require(off.size - 1 <= _lib.SEGMENTS_MAX, f"offsets: at most 2^24 segments, got {off.size - 1}")
+    _require(int(off[0]) == 0 and int(off[-1]) == n_rows and bool((np.diff(off) >= 0).all()),
+             f"offsets: ascending from 0 to the {n_rows} rows")
+    return off
+
+
+def _upload(*arrays, device) -> list:
+    """Host arrays -> device tensors of the same dtypes and shapes through ONE pinned staging buffer and one non-blocking copy,
+    each part on a 16-byte boundary.  Enqueues only."""
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    starts, total = [], 0
+    for a in arrays:
+        starts.append(total)
+        total += (a.nbytes + 15) // 16 * 16
+    staged = torch.empty((max(total, 16),), dtype=torch.uint8, pin_memory=True)
+    view = staged.numpy()
+    for a, at in zip(arrays, starts):
+        view[at:at + a.nbytes] = a.reshape(-1).view(np.uint8)
+    on_device = staged.to(device, non_blocking=True)
+    return [on_device[at:at + a.nbytes].view(torch.from_numpy(np.empty((0,), dtype=a.dtype)).dtype).reshape(a.shape)
+            for a, at in zip(arrays, starts)]
+
+
+def _knn_check(k: int) -> int:
+    k = int(k)
+    _require(1 <= k <= _lib.KNN_MAX_K, f"k: between 1 and {_lib.KNN_MAX_K}, got {k}")
+    return k
+
+
+def _search_tables(xyz: torch.Tensor, off: np.ndarray, k: int):
+    """The tables of a non-empty batch's search: (grids [S, 112] uint8 on the host, and on the device the offsets, the grids and
+    cell_base).  Holds THE read-back of ``knn_mean_distance_segments``; raises its ValueError."""
+    lib = _lib.load()
+    N, S = int(xyz.shape[0]), off.size - 1
+    counts = np.diff(off)
+    live = np.nonzero(counts)[0]
+    rank = counts[live] // 100
+    where = np.concatenate([off[live] + rank, off[live] + counts[live] - 1 - rank])
+    off_dev, where_dev = _upload(off, where, device=xyz.device)
+    # the segmented order statistics: every column ascending, then stably by segment -- each segment's range holds its own values ascending
+    segment = torch.searchsorted(off_dev[1:], torch.arange(N, dtype=torch.int64, device=xyz.device), right=True).to(torch.int32)
+    values, by_value = torch.sort(xyz.t().contiguous(), dim=1)
+    by_segment = torch.sort(segment[by_value], dim=1, stable=True).indices
+    ranked = values.gather(1, by_segment).index_select(1, where_dev)                      # [3, 2 * live]
+    finite = torch.isfinite(xyz).all().to(torch.float64).reshape(1)
+    back = torch.cat([ranked.reshape(-1), finite]).cpu().numpy()                            # THE read-back
+    if back[-1] != 1.0:
+        raise ValueError("mspa.cloud_segments: requirement not met: xyz: finite coordinates")
+    box = back[:-1].reshape(3, 2, live.size)
+    lo, hi = np.zeros((S, 3)), np.zeros((S, 3))
+    lo[live], hi[live] = box[:, 0].T, box[:, 1].T
+    grids = np.zeros((S, _lib.KNN_GRID_BYTES), dtype=np.uint8)
+    cell_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_knn_segments_grids_host(lo.ctypes.data, hi.ctypes.data, off.ctypes.data, S, k, grids.ctypes.data))
+    _lib.check(lib.mspa_knn_segments_tables_host(off.ctypes.data, S, k, cell_base.ctypes.data))
+    grids_dev, base_dev = _upload(grids, cell_base, device=xyz.device)
+    return grids, off_dev, grids_dev, base_dev
+
+
+def knn_mean_distance_segments(xyz: torch.Tensor, offsets, k: int, want_evals: bool = False):
+    """[N, 3] float64 finite points and host ``offsets`` [S + 1] -> ``avg`` [N] float64: per segment what
+    ``engine.knn_mean_distance(xyz[a:b], k)`` returns, bit for bit (the mean distance from each point to its min(k, n_s) nearest
+    points of its own segment, itself included).  With ``want_evals`` also [N] int32, the distances each point evaluated.  One
+    read-back per call, whatever S is: the boxes of all segments (the per-axis order statistics of rank n_s // 100 and
+    n_s - 1 - n_s // 100, from two device sorts) together with the flag that every coordinate is finite; non-finite
+    coordinates raise ValueError."""
+    N = _check("xyz", xyz, torch.float64, (None, 3)).shape[0]
+    off = _offsets(offsets, N)
+    k = _knn_check(k)
+    _require(N <= 1 << 30, f"xyz: at most 2^30 points, got {N}")
+    S = off.size - 1
+    mean = torch.empty((N,), dtype=torch.float64, device=xyz.device)
+    evals = torch.empty((N,), dtype=torch.int32, device=xyz.device) if want_evals else None
+    if N == 0:
+        return (mean, evals) if want_evals else mean
+    lib = _lib.load()
+    grids, off_dev, grids_dev, base_dev = _search_tables(xyz, off, k)
+    keys = torch.empty((N,), dtype=torch.int64, device=xyz.device)
+    _lib.check(lib.mspa_knn_segments_cells_device(_ptr(xyz), off.ctypes.data, S, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev),
+                                                  _ptr(base_dev), _ptr(keys), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    work = _workspace(int(lib.mspa_knn_segments_workspace_bytes(off.ctypes.data, S, k)), xyz.device)
+    _lib.check(lib.mspa_knn_segments_mean_distance_device(_ptr(xyz), off.ctypes.data, S, k, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev),
+                                                          _ptr(base_dev), _ptr(order), _ptr(mean), _ptr(evals), _ptr(work),
+                                                          int(work.numel()), _stream_ptr()))
+    return (mean, evals) if want_evals else mean
+
+
+def outlier_stats_segments(avg: torch.Tensor, offsets, std_ratio: float, xyz: torch.Tensor) -> dict:
+    """``avg`` [N] float64 (``knn_mean_distance_segments``' output), host ``offsets`` [S + 1] and the rows' ``xyz`` [N, 3] float64 ->
+    a dict of device tensors: ``keep`` [N] bool, the rows that stay, and per segment ``kept`` [S] int64, ``mean``, ``sd``, ``thr`` [S]
+    float64 and ``lo`` / ``hi`` [S, 3] float64, the extents of the kept rows (+inf / -inf where none stays).  The rule is
+    ``ops.remove_statistical_outliers``' per segment, with the two sums in the order csrc/cloud_segments_core.h states; a segment
+    of fewer than two rows has NaN statistics and keeps nothing.  Enqueue only: the offsets go up through pinned memory and
+    nothing is read back."""
+    N = _check("avg", avg, torch.float64, (None,)).shape[0]
+    _check("xyz", xyz, torch.float64, (N, 3))
+    off = _offsets(offsets, N)
+    S = off.size - 1
+    std_ratio = float(std_ratio)
+    _require(np.isfinite(std_ratio), f"std_ratio: finite, got {std_ratio}")
+    dev = avg.device
+    keep = torch.empty((N,), dtype=torch.uint8, device=dev)
+    out = {"keep": keep.view(torch.bool), "kept": torch.empty((S,), dtype=torch.int64, device=dev)}
+    for name in ("mean", "sd", "thr"):
+        out[name] = torch.empty((S,), dtype=torch.float64, device=dev)
+    for name in ("lo", "hi"):
+        out[name] = torch.empty((S, 3), dtype=torch.float64, device=dev)
+    if S:
+        off_dev, = _upload(off, device=dev)
+        _lib.check(_lib.load().mspa_outlier_segments_device(_ptr(avg), _ptr(xyz), off.ctypes.data, S, std_ratio, _ptr(off_dev), _ptr(keep),
+                                                            _ptr(out["kept"]), _ptr(out["mean"]), _ptr(out["sd"]), _ptr(out["thr"]),
+                                                            _ptr(out["lo"]), _ptr(out["hi"]), _stream_ptr()))
+    return out
+
+
+def _check_rule(nb_neighbors, std_ratio) -> None:
+    """``ops.remove_statistical_outliers``' argument errors, word for word."""
+    if nb_neighbors < 1 or std_ratio <= 0:
+        raise RuntimeError("remove_statistical_outliers: nb_neighbors must be at least 1 and std_ratio positive "
+                           f"(got {nb_neighbors}, {std_ratio})")
+    if nb_neighbors > _lib.KNN_MAX_K:
+        raise NotImplementedError(f"remove_statistical_outliers: nb_neighbors is limited to {_lib.KNN_MAX_K} (got {nb_neighbors})")
+
+
+def clean_segments(rows: torch.Tensor, offsets, nb_neighbors=20, std_ratio=1.0):
+    """``remove_statistical_outliers_segments`` plus the kept rows' indices into ``rows`` [M] int64 (device), ascending: ``(rows_kept,
+    offsets_kept, lo, hi, index)``.  For a caller that filters further per-row arrays the same way."""
+    _check_rule(nb_neighbors, std_ratio)
+    _require(isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[1] >= 3,
+             "rows: a device tensor [N, C >= 3]")
+    off = _offsets(offsets, int(rows.shape[0]))
+    xyz = rows[:, :3].to(torch.float64).contiguous()
+    try:
+        avg = knn_mean_distance_segments(xyz, off, int(nb_neighbors))
+    except ValueError as e:
+        if "finite coordinates" in str(e):
+            raise ValueError("remove_statistical_outliers: the cloud has non-finite coordinates") from None
+        raise
+    stats = outlier_stats_segments(avg, off, std_ratio, xyz)
+    kept = stats["kept"].cpu().numpy()                                                      # THE second read-back
+    kept_offsets = np.zeros((off.size,), dtype=np.int64)
+    np.cumsum(kept, out=kept_offsets[1:])
+    index = torch.nonzero_static(stats["keep"], size=int(kept_offsets[-1])).flatten()       # its size is known: no read-back of its own
+    return rows.index_select(0, index), kept_offsets, stats["lo"], stats["hi"], index
+
+
+def remove_statistical_outliers_segments(rows: torch.Tensor, offsets, nb_neighbors=20, std_ratio=1.0):
+    """A batch ``rows`` [N, C >= 3] (device; all columns and the dtype are kept, float32 coordinates are widened exactly for the
+    search, as the single-cloud op does) and host ``offsets`` [S + 1] -> ``(rows_kept, offsets_kept, lo, hi)``: per segment the rows
+    ``ops.remove_statistical_outliers(rows[a:b], nb_neighbors, std_ratio)`` keeps, in ascending order and back to back;
+    ``offsets_kept`` [S + 1] a host int64 array again; ``lo`` / ``hi`` [S, 3] float64 (device) the kept rows' extents, +inf / -inf
+    where none stays.  The same exceptions as the single-cloud op: RuntimeError for ``nb_neighbors < 1`` or ``std_ratio <= 0``,
+    NotImplementedError above 64, ValueError for non-finite coordinates.  Two read-backs per call, whatever S is: the boxes of all
+    segments (``knn_mean_distance_segments``) and the kept counts."""
+    return clean_segments(rows, offsets, nb_neighbors, std_ratio)[:4]
+
+
+def knn_mean_distance_segments_host(xyz, offsets, k: int, want_evals: bool = False):
+    """``knn_mean_distance_segments`` on the CPU for NumPy input, through the same headers (mspa_knn_segments_mean_distance_host).
+    The device's twin for tests on a machine without a GPU, not a fallback."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"mspa.cloud_segments: xyz: expected [N, 3], got {list(xyz.shape)}")
+    off = _offsets(offsets, xyz.shape[0])
+    k = _knn_check(k)
+    mean = np.empty((xyz.shape[0],), dtype=np.float64)
+    evals = np.empty((xyz.shape[0],), dtype=np.int32) if want_evals else None
+    _lib.check(_lib.load().mspa_knn_segments_mean_distance_host(xyz.ctypes.data, off.ctypes.data, off.size - 1, k, mean.ctypes.data,
+                                                                evals.ctypes.data if want_evals else None))
+    return (mean, evals) if want_evals else mean
+
+
+def outlier_stats_segments_host(avg, offsets, std_ratio: float, xyz) -> dict:
+    """``outlier_stats_segments`` on the CPU for NumPy input (mspa_outlier_segments_host): the same keys, NumPy arrays."""
+    avg = np.ascontiguousarray(avg, dtype=np.float64)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    N = avg.shape[0]
+    if avg.ndim != 1 or xyz.shape != (N, 3):
+        raise ValueError(f"mspa.cloud_segments: avg [N] and xyz [N, 3], got {list(avg.shape)} and {list(xyz.shape)}")
+    off = _offsets(offsets, N)
+    S = off.size - 1
+    keep = np.zeros((N,), dtype=np.uint8)
+    out = {"kept": np.zeros((S,), dtype=np.int64), "mean": np.zeros((S,)), "sd": np.zeros((S,)), "thr": np.zeros((S,)),
+           "lo": np.zeros((S, 3)), "hi": np.zeros((S, 3))}
+    _lib.check(_lib.load().mspa_outlier_segments_host(avg.ctypes.data, xyz.ctypes.data, off.ctypes.data, S, float(std_ratio), keep.ctypes.data,
+                                                      *(out[n].ctypes.data for n in ("kept", "mean", "sd", "thr", "lo", "hi"))))
+    out["keep"] = keep.astype(bool)
+    return out
+
+
+def remove_statistical_outliers_segments_host(rows, offsets, nb_neighbors=20, std_ratio=1.0):
+    """``remove_statistical_outliers_segments`` over the two host twins, NumPy in and out: for tests on a machine without a GPU."""
+    _check_rule(nb_neighbors, std_ratio)
+    rows = np.asarray(rows)
+    off = _offsets(offsets, rows.shape[0])
+    xyz = np.ascontiguousarray(rows[:, :3], dtype=np.float64)
+    if not np.isfinite(xyz).all():
+        raise ValueError("remove_statistical_outliers: the cloud has non-finite coordinates")
+    stats = outlier_stats_segments_host(knn_mean_distance_segments_host(xyz, off, int(nb_neighbors)), off, std_ratio, xyz)
+    kept_offsets = np.zeros((off.size,), dtype=np.int64)
+    np.cumsum(stats["kept"], out=kept_offsets[1:])
+    return rows[stats["keep"]], kept_offsets, stats["lo"], stats["hi"]
+
+
+def boxes_of(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    """Extents lo / hi [..., 3] -> [..., 6]: ``[(hi + lo) / 2, hi - lo]``, what ``ops.calculate_aabb`` returns for the rows they
+    span; NaN where lo > hi (the +inf / -inf of a segment without rows).  Enqueue only."""
+    box = torch.cat([(hi + lo) / 2, hi - lo], dim=-1)
+    return torch.where((lo > hi).any(dim=-1, keepdim=True), torch.full_like(box, float("nan")), box)
+
+
+def iou_3d(boxes: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
+    """``ops.calculate_iou_3d``'s device branch along a trailing axis: boxes [..., 6] against gt [..., 6] -> [...]; the same torch
+    operations in the same order, so each entry equals the single call's.  NaN boxes give NaN."""
+    dim = torch.minimum(boxes[..., :3] + boxes[..., 3:] / 2, gt[..., :3] + gt[..., 3:] / 2) - \
+        torch.maximum(boxes[..., :3] - boxes[..., 3:] / 2, gt[..., :3] - gt[..., 3:] / 2)
+    inter = torch.where((dim > 0).all(dim=-1), dim.prod(dim=-1), torch.zeros((), dtype=dim.dtype, device=dim.device))
+    return inter / (boxes[..., 3:].prod(dim=-1) + gt[..., 3:].prod(dim=-1) - inter)

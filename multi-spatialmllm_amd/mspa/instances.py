@@ -81,6 +81,62 @@ class InstanceClouds:
         """The object's rows over all images, in ``image_ids`` order: one device concatenation."""
         return torch.cat([self.cloud(i, target_id) for i in self.image_ids] or [self.rows[:0]])
 
+    # ---- every segment at once (mspa.cloud_segments): launches and read-backs do not depend on the number of segments ----------
+    def cleaned(self, nb_neighbors=20, std_ratio=1.0) -> "InstanceClouds":
+        """A new ``InstanceClouds`` of the same ``image_ids`` that holds, per (image, object), the rows
+        ``ops.remove_statistical_outliers(cloud(image, object), nb_neighbors, std_ratio)`` keeps: ``counts``, ``offsets``, ``rows``,
+        ``rgb``, ``lo`` / ``hi`` (and ``pixel``, where this one has it) are those of the kept rows.  One batched pass
+        (``cloud_segments.remove_statistical_outliers_segments``: two read-backs, its exceptions)."""
+        from . import cloud_segments
+        rows, offsets, lo, hi, index = cloud_segments.clean_segments(self.rows, self.offsets, nb_neighbors, std_ratio)
+        shape = self.counts.shape
+        return InstanceClouds(self.image_ids, np.diff(offsets).reshape(shape), rows, None if self.pixel is None else self.pixel.index_select(0, index),
+                              lo.reshape(shape + (3,)), hi.reshape(shape + (3,)), None if self.rgb is None else self.rgb.index_select(0, index))
+
+    def boxes(self) -> torch.Tensor:
+        """[F, L, 6] float64 on the device: ``aabb`` of every (image, label) at once, ``[(hi + lo) / 2, hi - lo]``; NaN where the
+        segment is empty.  Enqueue only."""
+        from . import cloud_segments
+        return cloud_segments.boxes_of(self.lo, self.hi)
+
+    def _object_runs(self):
+        """(shift [O * F], lengths [O * F], offsets [O + 1], object_ids [O]) as host int64 arrays: run (j, k) of the regrouped rows is
+        object ``object_ids[j]`` = label ``object_ids[j] + 1`` in frame k; regrouped row p of that run is row p + shift of ``rows``.  The
+        objects with at least one row, ascending; the frames in ``image_ids`` order."""
+        F, L = self.counts.shape
+        labels = np.array([v for v in range(1, L) if self.counts[:, v].any()], dtype=np.int64)
+        segments = (np.arange(F, dtype=np.int64)[None, :] * L + labels[:, None]).reshape(-1)      # object-major, then frame
+        lengths = self.counts.reshape(-1)[segments]
+        ends = np.cumsum(lengths)
+        offsets = np.zeros((len(labels) + 1,), dtype=np.int64)
+        if len(labels):
+            offsets[1:] = ends.reshape(len(labels), F)[:, -1]
+        return self.offsets[segments] - (ends - lengths), lengths, offsets, labels - 1
+
+    def by_object(self):
+        """``(rows, offsets, object_ids)``: the same rows regrouped so that the rows of object ``object_ids[j]`` over all images are
+        ``rows[offsets[j]:offsets[j + 1]]``, value for value ``object_cloud(object_ids[j])``; the objects with at least one row,
+        ascending; ``offsets`` and ``object_ids`` are host int64 arrays.  One device gather whose index is built from the host
+        ``offsets``: a run table of O * F entries goes up, the index itself is expanded on the device.  Enqueue only."""
+        shift, lengths, offsets, object_ids = self._object_runs()
+        total = int(offsets[-1])
+        if self.rows.is_cuda:
+            from . import cloud_segments
+            shift, lengths = cloud_segments._upload(shift, lengths, device=self.rows.device)
+        else:
+            shift, lengths = torch.from_numpy(shift), torch.from_numpy(lengths)
+        index = torch.arange(total, dtype=torch.int64, device=self.rows.device) + torch.repeat_interleave(shift, lengths, output_size=total)
+        return self.rows.index_select(0, index), offsets, object_ids
+
+    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0):
+        """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
+        ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``
+        [O + 1]; ``boxes`` [O, 6] float64 (device) their ``calculate_aabb``, NaN where nothing is kept."""
+        from . import cloud_segments
+        rows, offsets, object_ids = self.by_object()
+        kept, kept_offsets, lo, hi = cloud_segments.remove_statistical_outliers_segments(rows, offsets, nb_neighbors, std_ratio)
+        return kept, kept_offsets, object_ids, cloud_segments.boxes_of(lo, hi)
+
 
 def _mask_path(handler, scene_id, image_id) -> str:
     return os.path.join(handler.mask_image_root, scene_id, "instance-filt", f"{int(image_id)}.png")

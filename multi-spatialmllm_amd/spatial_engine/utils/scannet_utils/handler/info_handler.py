@@ -290,6 +290,39 @@ class SceneInfoHandler:
         from mspa import instances
         return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
 
+    def instance_boxes(self, scene_id, image_ids=None, nb_neighbors=20, std_ratio=1.0, per="image", device="cuda", num_workers=8):
+        """The rest of the tool chain for every object of a scene at once: ``instance_clouds`` -> cleaned clouds
+        (``remove_statistical_outliers(cloud, nb_neighbors, std_ratio)`` per segment) -> boxes (``calculate_aabb``) -> IoU against
+        ``get_object_gt_bbox(scene_id, target_id, axis_aligned=True)[:6]`` (``calculate_iou_3d``), in a number of launches and
+        read-backs that does not depend on the number of objects (``mspa.cloud_segments``).  A dict of
+
+          per="image"    ``boxes`` [F, L, 6], ``kept`` [F, L] (host int64), ``iou`` [F, L]: entry (k, v) is object v - 1 in
+                         ``image_ids[k]``; ``image_ids`` the frames;
+          per="object"   ``boxes`` [O, 6], ``kept`` [O] (host int64), ``iou`` [O], ``object_ids`` [O] (host int64): each object's
+                         rows over all frames, fused (``InstanceClouds.object_cloud``), for the objects with at least one row.
+
+        ``boxes`` and ``iou`` are float64 device tensors; NaN where nothing is kept (no box) and, for ``iou``, where the scene's
+        annotation has no such object.  Works on either path of ``instance_clouds``.  No reference counterpart."""
+        from mspa import cloud_segments
+        if per not in ("image", "object"):
+            raise ValueError(f"instance_boxes: per must be 'image' or 'object', got {per!r}")
+        clouds = self.instance_clouds(scene_id, image_ids, False, device, num_workers)
+        n_objects = self.get_num_objects(scene_id)
+        if per == "image":
+            cleaned = clouds.cleaned(nb_neighbors, std_ratio)
+            boxes, kept, targets = cleaned.boxes(), cleaned.counts, np.arange(clouds.n_labels, dtype=np.int64) - 1
+            out = {"image_ids": list(clouds.image_ids)}
+        else:
+            _rows, offsets, targets, boxes = clouds.cleaned_objects(nb_neighbors, std_ratio)
+            kept = np.diff(offsets)
+            out = {"object_ids": targets}
+        gt = np.full((len(targets), 6), np.nan)
+        for j, t in enumerate(targets):
+            if 0 <= t < n_objects:
+                gt[j] = np.asarray(self.get_object_gt_bbox(scene_id, int(t), axis_aligned=True), dtype=np.float64)[:6]
+        out.update(boxes=boxes, kept=kept, iou=cloud_segments.iou_3d(boxes, torch.from_numpy(gt).to(boxes.device)))
+        return out
+
     # ---- resident scene (what the per-scene scripts use) -----------------------------------------
     def color_frames_device(self, scene_id, image_ids=None, device="cuda", num_workers=8):
         """[F, H, W, 3] uint8 RGB device tensor of the scene's colour frames (``image_ids``, default every image), the JPEG files
