@@ -142,6 +142,12 @@ int mspa_device_info(int device, int *n_cu, int *wave_size, int64_t *hbm_bytes, 
  *                                                and camera-2 depth; NaN where invalid
  *   out_counts    [n_pairs, 2] int32             (#valid, #visible); zeroed by the call
  * Requires 2 <= dw,dh,W,H <= 32767 and H*W*W < 2^32.
+ * Alignment: out_pix_i16 must be 4-byte aligned (MSPA_EINVAL otherwise): every kernel stores an (xi, yi) pair as one 32-bit
+ * word.  Every other pointer needs its element's alignment only (rgb: any; the whole-tile kernel reads a row's colour bytes
+ * as one 32-bit word per pixel at byte 3 x - 1 of the row, at every residue mod 4 wherever rgb starts, and never in front of
+ * it).  The whole-tile and rectangular-tile kernels (MSPA_KERNEL_PAIR_FAST_TIGHT / _RECT) additionally want depth and
+ * out_vis_u8 4-byte, out_vis_bits 8-byte and out_pix_i16, out_xyz_f32 and out_rgba 16-byte aligned; a launch with one of them
+ * elsewhere takes the general kernel of its mode.
  */
 int mspa_pair_reproject(const uint16_t *depth, const uint8_t *rgb, const double *frame_mats,
                         int32_t n_frames, const int32_t *pairs, int64_t n_pairs,
@@ -206,7 +212,8 @@ int mspa_pair_correspondences(const uint16_t *depth, const double *frame_mats, i
                               uint64_t *out_vis_bits, int16_t *out_cpix_i16, int32_t *out_tile_counts,
                               int32_t *out_counts, void *workspace, int64_t workspace_bytes, uint32_t flags,
                               mspa_stream_t stream);
-/* The compaction step on its own: (vis_bits, dense pix_i16 [n_pairs, P, 2]) of mspa_pair_reproject -> segments + counts. */
+/* The compaction step on its own: (vis_bits, dense pix_i16 [n_pairs, P, 2]) of mspa_pair_reproject -> segments + counts.
+ * pix_i16 and out_cpix_i16 must be 4-byte aligned (MSPA_EINVAL otherwise): an (xi, yi) pair moves as one 32-bit word. */
 int mspa_compact_correspondences(const uint64_t *vis_bits, const int16_t *pix_i16, int64_t n_pairs, int32_t H, int32_t W,
                                  int16_t *out_cpix_i16, int32_t *out_tile_counts, mspa_stream_t stream);
 

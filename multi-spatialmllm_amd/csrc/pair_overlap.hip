@@ -28,7 +28,11 @@ __global__ __launch_bounds__(kOThreads) void pair_overlap_kernel(OverlapArgs a) 
     const uint64_t *__restrict__ rb = a.bits + (int64_t)a.pairs[2 * p + 1] * a.n_words;
     int inter = 0, uni = 0;
     const int64_t n2 = a.n_words >> 1;
-    const bool aligned = ((a.n_words & 1) == 0);   // rows stay 16-byte aligned only for even n_words
+    // Whole 16-byte pieces for an even n_words.  Every row then starts a multiple of 16 bytes behind a.bits, which is an int64
+    // table and so known to be 8-byte aligned only: in a view one word into a buffer every load here sits at 8 mod 16.  That is
+    // inside what the ISA defines for a multi-dword global load (dword alignment; only LDS and atomics ask for more), so this
+    // kernel does not look at the pointer.  The tiled form does (launch_tiles): its matrix-core kernel stages 16-byte pieces in LDS.
+    const bool aligned = ((a.n_words & 1) == 0);
     if (aligned) {
         const ulonglong2 *__restrict__ va = reinterpret_cast<const ulonglong2 *>(ra);
         const ulonglong2 *__restrict__ vb = reinterpret_cast<const ulonglong2 *>(rb);

@@ -1644,6 +1644,9 @@ extern "C" int mspa_pair_reproject(const uint16_t *depth, const uint8_t *rgb, co
                                    float *out_xyz_f32, uint32_t *out_rgba, double *out_xyz_f64,
                                    double *out_uv_f64, double *out_depth_f64, int32_t *out_counts,
                                    uint32_t flags, mspa_stream_t stream) {
+    // every kernel stores a pixel's (xi, yi) as ONE 32-bit word: a table that is only 2-byte aligned (a view one int16 in) is refused
+    // (mspa_pair_correspondences hands pair_reproject_impl its workspace here, which it has held to 16 bytes)
+    if ((uintptr_t)out_pix_i16 & 3u) return fail(MSPA_EINVAL, "mspa_pair_reproject: out_pix_i16 must be 4-byte aligned");
     return pair_reproject_impl(depth, rgb, frame_mats, n_frames, pairs, n_pairs, dh, dw, H, W, out_vis_bits, out_vis_u8,
                                out_valid_u8, out_pix_i16, out_xyz_f32, out_rgba, out_xyz_f64, out_uv_f64, out_depth_f64,
                                out_counts, nullptr, nullptr, flags, stream);

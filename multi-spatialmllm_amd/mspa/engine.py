@@ -748,7 +748,9 @@ def pair_reproject(depth: torch.Tensor, mats: torch.Tensor, pairs: torch.Tensor,
                    out: Dict[str, torch.Tensor], rgb: Optional[torch.Tensor] = None, flags: int = 0):
     """Enqueue K3 on the current stream.  depth [F,DH,DW] int16(bits of uint16), mats [F,8,16] f64,
     pairs [B,2] int32, rgb [F,H,W,3] uint8 (only for out['rgba']).  ``out`` comes from
-    alloc_pair_outputs and is filled in place.  Only enqueues, with one exception: under MSPA_PAIR_FAST the first launch
+    alloc_pair_outputs and is filled in place; a caller's own ``out['pix_i16']`` starts 4-byte aligned (MspaError otherwise, as
+    from the C ABI: a view one int16 into a buffer is refused).
+    Only enqueues, with one exception: under MSPA_PAIR_FAST the first launch
     on a ``mats`` tensor object (and the first after an in-place write to it) reads the pinhole verdict back
     (``_require_pinhole``), which waits for the current stream."""
     F, DH, DW, n = _check_pair_inputs(depth, mats, pairs)

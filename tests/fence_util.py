@@ -13,8 +13,8 @@ lives on a watched device and has elements is moved into one flat uint8 buffer
 
 and handed on as a view of the payload with the result's dtype, shape and strides.  The payload starts ``width`` bytes -- a
 multiple of 512, the alignment torch's allocator gives anyway -- behind the buffer's base, so an alignment check sees what it sees
-without the fences; it ends at its exact last byte, and the back fence begins at the next one.  ``width`` is the payload size
-rounded up to 512, at least 4 KiB and at most 1 MiB: an error of one row, one tile or one segment still lands in it.  Host tensors,
+without the fences (tests/skew_util.py asks ``rehome`` for a ``skew`` on top of that, on purpose); it ends at its exact last byte,
+and the back fence begins at the next one.  ``width`` is the payload size rounded up to 512, at least 4 KiB and at most 1 MiB: an error of one row, one tile or one segment still lands in it.  Host tensors,
 pinned ones included, pass through untouched, and so do tensors of no elements.
 
 The fences hold poison_util's fill, viewed in the payload's dtype, mode "a" or "b".  Those values are small on purpose: a stray
@@ -49,6 +49,7 @@ _HERE = os.path.abspath(__file__)
 _ROOT = os.path.dirname(os.path.dirname(_HERE))
 PACKAGE_DIR = os.path.join(_ROOT, "multi-spatialmllm_amd") + os.sep
 _REAL_EMPTY = torch.empty                                # (the module is imported outside any patch)
+HARNESS = {_HERE}                                        # files whose frames are no call site (tests/skew_util.py adds itself)
 
 
 def fence_width(payload_bytes: int) -> int:
@@ -65,7 +66,7 @@ def call_site() -> str:
         path = os.path.abspath(f.f_code.co_filename)
         if path.startswith(PACKAGE_DIR):
             return f"{os.path.relpath(path, _ROOT)}:{f.f_lineno} {f.f_code.co_name}"
-        if outside is None and path != _HERE and "contextlib" not in path:
+        if outside is None and path not in HARNESS and "contextlib" not in path:
             outside = f"{os.path.basename(path)}:{f.f_lineno} {f.f_code.co_name}"
         f = f.f_back
     return outside or "?"
@@ -85,23 +86,30 @@ class Fences:
         poison_value(torch.int32, mode)
         self.mode = mode
         self.records = []                                # (site, dtype, shape, flat buffer, width, payload bytes)
+        self.skews = []                                  # per record: the bytes its payload starts behind ``width`` (tests/skew_util.py)
         self.empty_sites = []                            # sites of the zero-length tensors that passed through: the early returns taken
         self._expected = {}
 
     def __len__(self):
         return len(self.records)
 
-    def rehome(self, t: torch.Tensor, site: str) -> torch.Tensor:
-        """An equal tensor (dtype, shape, strides, and every byte of the storage range ``t`` spans) between two fences."""
+    def rehome(self, t: torch.Tensor, site: str, skew: int = 0) -> torch.Tensor:
+        """An equal tensor (dtype, shape, strides, and every byte of the storage range ``t`` spans) between two fences.  ``skew``
+        (bytes, a multiple of the element size) moves the payload that far behind its 512-aligned place: the front fence grows by
+        it, the payload still ends at its exact last byte and the back fence begins at the next one."""
         span, size = _span(t), t.element_size()
+        if skew < 0 or skew % size:
+            raise ValueError(f"skew {skew}: a non-negative multiple of the element size {size}")
         nbytes = span * size
         width = fence_width(nbytes)
-        buf = _REAL_EMPTY((width + nbytes + width,), dtype=torch.uint8, device=t.device)
-        fill_poison(buf[:width].view(t.dtype), self.mode)
-        fill_poison(buf[width + nbytes:].view(t.dtype), self.mode)
-        payload = buf[width:width + nbytes].view(t.dtype)
+        front = width + skew
+        buf = _REAL_EMPTY((front + nbytes + width,), dtype=torch.uint8, device=t.device)
+        fill_poison(buf[:front].view(t.dtype), self.mode)
+        fill_poison(buf[front + nbytes:].view(t.dtype), self.mode)
+        payload = buf[front:front + nbytes].view(t.dtype)
         payload.copy_(t.detach().as_strided((span,), (1,)))
         self.records.append((site, t.dtype, tuple(t.shape), buf, width, nbytes))
+        self.skews.append(skew)
         return payload.as_strided(t.shape, t.stride())
 
     def _fill(self, dtype, width):
@@ -116,8 +124,9 @@ class Fences:
         if any(r[3].is_cuda for r in self.records):
             torch.cuda.synchronize()
         found = []
-        for site, dtype, shape, buf, width, nbytes in self.records:
-            for side, fence in (("before", buf[:width]), ("after", buf[width + nbytes:])):
+        for (site, dtype, shape, buf, back, nbytes), skew in zip(self.records, self.skews):
+            for side, fence in (("before", buf[:back + skew]), ("after", buf[back + skew + nbytes:])):
+                width = fence.numel()
                 want = self._fill(dtype, width)
                 if fence.is_cuda:                        # compare where the bytes are; only a damaged fence comes to the host
                     key = (dtype, width, fence.device)

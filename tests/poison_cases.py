@@ -46,6 +46,12 @@ class Case:
     defined: Optional[Dict[str, object]] = None
     writes: Tuple[str, ...] = ()      # paths into ``inputs`` the op is documented to write (tests/test_gpu_fenced_memory.py), each with its sentence
     enqueue_only: Optional[str] = None    # the documents' promise that no covered function synchronises the host (tests/test_gpu_stream_order.py)
+    # tests/test_gpu_skewed_memory.py: path into ``inputs`` (or "own/<name>": a buffer ``run`` allocates with ``own``) -> (the bytes of
+    # alignment the documents demand for that argument, the sentence that demands them); every other caller-owned tensor is run at
+    # the alignment of its element.  ``own_buffers``: the names ``run`` may pass to ``own`` (checked on the CPU).
+    aligned: Optional[Dict[str, Tuple[int, str]]] = None
+    own_buffers: Tuple[str, ...] = ()
+    refused_by: Optional[str] = None      # where it matters WHICH entry point refuses: a piece of the error string of every refusal of the case
 
 
 CASES = []
@@ -118,12 +124,63 @@ HOST_STEPS = {
 }
 
 
-def case(name, family, covers, defined=None, writes=(), enqueue_only=None):
+def case(name, family, covers, defined=None, writes=(), enqueue_only=None, aligned=None, own_buffers=(), refused_by=None):
     """Decorator of a class with static ``build`` / ``run`` / ``expect``: registers it as a Case."""
     def register(cls):
-        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined, tuple(writes), enqueue_only))
+        CASES.append(Case(name, family, tuple(covers), cls.build, cls.run, cls.expect, defined, tuple(writes), enqueue_only,
+                          dict(aligned) if aligned else None, tuple(own_buffers), refused_by))
         return cls
     return register
+
+
+# The alignment sentences of include/mspa.h and of the wrappers' docstrings, word for word (tests/test_skew_util_cpu.py holds every
+# one against the two files, line breaks folded).  An argument without a sentence is run at its element's alignment: what
+# ``engine._check`` lets through.  Where the header offers a route instead of a refusal ("a table at an odd 2-byte offset takes the
+# dense route as well", "a launch with one of them elsewhere takes the general kernel of its mode") the argument has no entry and
+# is skewed fully: the result must not change.
+ALIGN_INFLATE = "src_dev 16-byte, dst_dev and dst_pitch 256-byte aligned"
+ALIGN_JPEG_SRC = "src_dev 4-byte aligned"
+ALIGN_JPEG_DESC = "desc_dev, 16-byte aligned"
+ALIGN_PIX = "out_pix_i16 must be 4-byte aligned (MSPA_EINVAL otherwise)"
+ALIGN_CPIX = "out_cpix_i16 must be 16-byte aligned"
+ALIGN_CORR_WORKSPACE = "`workspace` (caller-owned, 16-byte aligned, at least mspa_pair_correspondences_workspace_bytes(...) bytes"
+ALIGN_PNG_ENCODE = "Alignment: depth_dev 2 bytes, out_dev 4 bytes, nbytes_dev 8 bytes, workspace 16 bytes"
+# Sentences about buffers that no case can place, because the wrappers allocate them themselves (``engine._workspace``: "on a 16-byte
+# boundary (allocated as int64 pairs)"; the un-filters' ``raw`` is inflate_blocks_device's own output in every chain): each with the
+# test that exercises its refusal, or the reason there is none.
+ALIGN_WRAPPER_OWNED = {
+    "raw_dev 4-byte aligned (MSPA_EINVAL otherwise)": "tests/test_gpu_png_unfilter.py and tests/test_gpu_png_unfilter8.py: test_unaligned_layouts_are_refused",
+    "workspace: caller-owned, 16-byte aligned": "engine._workspace allocates it in every wrapper but pair_correspondences (whose case pair_correspondences_own_workspace places one)",
+    "bytes (4-byte aligned)": "mspa_overlap_workspace_bytes: an int32 tensor of the wrapper's, element alignment",
+    "the workspace of both calls (4-byte aligned)": "mspa_instance_split_workspace_bytes: an int32 tensor of the wrapper's, element alignment",
+    "mspa_knn_workspace_bytes(n, k), 16-byte aligned": "engine._workspace allocates it",
+    "pix_i16 and out_cpix_i16 must be 4-byte aligned (MSPA_EINVAL otherwise)":
+        "mspa_compact_correspondences on its own: no wrapper calls it; tests/test_gpu_compact.py holds its refusal",
+    "mspa_knn_segments_workspace_bytes(), 16-byte aligned": "the wrapper of mspa/instances.py allocates it; no case of this registry reaches it",
+}
+# Sentences that offer a route instead of a refusal, each with the cases that take the other route: no entry, skewed fully.
+ALIGN_ROUTES = {
+    "`depth` 4-byte aligned (any allocator's base address is): a table at an odd 2-byte offset takes the dense route as well":
+        "pair_correspondences_tight96x128 / _rect64x80: depth at 2 mod 4 (mode a) and 6 mod 8 (mode b); the wrapper allocates the workspace",
+    "additionally want depth and out_vis_u8 4-byte, out_vis_bits 8-byte and out_pix_i16, out_xyz_f32 and out_rgba 16-byte aligned":
+        "pair_reproject_tight96x128 (depth) and pair_reproject_own_* (one output pointer each): the general kernel of the mode runs; "
+        "pair_reproject_kept_depth_*: all of them aligned, rgb / mats / pairs skewed, the tile kernels stay",
+    "out_dev needs no more than the 2-byte alignment of uint16": "depth_png_own_17x34: the images at 2 mod 4 take the bytes route",
+    "pitches in bytes, any alignment": "resize_rgb_device and resize_rgb_device_own: sources and destinations at 1 / 3 mod 4",
+}
+
+
+def skewed_mode():
+    """"a" / "b" while tests/test_gpu_skewed_memory.py runs a case skewed, else None: where a case asserts the residue a branch needs."""
+    import skew_util
+    return skew_util.active_mode()
+
+
+def own(name, shape, dtype):
+    """A buffer the CALLER of an op allocates -- an ``out=``, a status array, a slot -- named so that ``Case.aligned`` can speak of it
+    ("own/<name>") and tests/skew_util.py can place it."""
+    import skew_util
+    return skew_util.caller_buffer(name, shape, dtype, DEV)
 
 
 def dev(a) -> torch.Tensor:
@@ -315,6 +372,9 @@ def _overlap_case(name, F, n_bits, unaligned=False):
 _overlap_case("overlap_odd_words_700", 33, 700)                         # 11 words: the popcount tile kernel; a ragged second row tile
 _overlap_case("overlap_even_words_8320", 70, 8320)                      # 130 words in an aligned table: the matrix-core tiles, three row tiles
 _overlap_case("overlap_even_words_unaligned", 33, 66 * 64, unaligned=True)   # an even count 8 bytes past a 16-byte boundary
+# tests/test_gpu_skewed_memory.py puts every int64 table at 8 mod 16 (data_ptr() % 16 == 8, asserted there): pair_overlap_kernel's
+# 16-byte pieces of an even-count row then sit at 8 mod 16 (csrc/pair_overlap.hip says why that stands), and launch_tiles'
+# ``((uintptr_t)bits_a & 15u) == 0`` fails, so overlap_even_words_8320 takes the popcount tiles where its plain run took the matrix cores.
 
 
 @case("overlap_no_words", "k1k2", ["scene_overlap", "overlap_matrix"], enqueue_only=ENQUEUES["scene_overlap"])
@@ -504,6 +564,9 @@ class _ObjectExtents:
 K3_SHAPES = {"tight96x128": ((96, 128), (96, 128)),        # whole tiles, colour grid == depth grid: the tight kernels
              "ragged61x83": ((61, 83), (37, 53)),          # nothing divides: the exact, the general fast and the linear fast kernel
              "rect64x80": ((64, 80), (32, 40))}            # rect_shape: the tight kernel's scaled form
+# Skewed (tests/test_gpu_skewed_memory.py) the depth table of every K3 case sits at 2 mod 4 / 6 mod 8: pair_reproject_impl's
+# ``((uintptr_t)depth & 3u) == 0`` fails, the whole-tile and rectangular-tile kernels are not taken (tight96x128, rect64x80: the
+# general kernels run where the plain run took the tight ones), and mspa_pair_correspondences goes through the dense table.
 K3_PAIRS = [(0, 1), (1, 0), (0, 4), (2, 2), (3, 0), (0, 3)]         # an identity pair; frame 3 has no valid depth
 K3_EXACT = ("vis_bits", "vis_u8", "valid_u8", "pix_i16", "xyz_f32", "xyz_f64", "uv_f64", "depth_f64", "counts", "rgba")
 K3_FAST_SETS = {"generic": ("vis_bits", "vis_u8", "valid_u8", "pix_i16", "xyz_f32", "counts"), "corr": ("vis_bits", "pix_i16", "counts"),
@@ -608,6 +671,172 @@ def _pair_correspondences_case(shape):
 for _shape in K3_SHAPES:
     _pair_reproject_case(_shape)
     _pair_correspondences_case(_shape)
+
+
+class Kept:
+    """An input that tests/skew_util.py and tests/fence_util.py leave where the allocator put it (they walk dicts, lists and tuples
+    only): the depth table of the cases below, which are about ONE output pointer each -- a skewed depth table alone already takes the
+    whole-tile kernel away (the K3 cases above, tests/pair_route_cases.py's ``misaligned``)."""
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
+# csrc/pair_reproject.hip, pair_reproject_impl: "the tight kernel's LDS-DMA moves depth in 4-byte units and its 16-byte stores need
+# aligned outputs" -- the alignment below which each pointer takes the whole-tile kernel away from a launch
+K3_POINTER_NEEDS = {"pix_i16": 16, "vis_bits": 8, "cpix": 16, "xyz_f32": 16, "rgba": 16, "vis_u8": 4}
+
+
+def _k3_check_some(res, n, ref_np, hw, color):
+    """tests/test_gpu_parity.py's ``check_pair_against`` for whichever of the fast outputs ``res`` holds."""
+    valid, vis = ref_np["valid"], ref_np["vis"]
+    if "vis_u8" in res:
+        assert np.array_equal(res["vis_u8"][n].astype(bool), vis)
+    if "vis_bits" in res:
+        assert np.array_equal(unpack_rows(res["vis_bits"][n:n + 1], hw[0] * hw[1])[0], vis)
+    assert tuple(res["counts"][n]) == (ref_np["n_valid"], ref_np["n_vis"])
+    if "pix_i16" in res:
+        pix = res["pix_i16"][n]
+        with np.errstate(invalid="ignore"):
+            inview = valid & O.check_point_in_image_boundary(ref_np["uv2"], hw) & (ref_np["depth2"] > 0)
+        assert np.array_equal(pix[inview, 0], ref_np["xi"][inview]) and np.array_equal(pix[inview, 1], ref_np["yi"][inview])
+        assert (pix[~inview] == -1).all()
+    if "rgba" in res:
+        exp = color.reshape(-1, 3).astype(np.uint32)
+        exp = exp[:, 0] | (exp[:, 1] << 8) | (exp[:, 2] << 16) | np.where(valid, 0xFF000000, 0).astype(np.uint32)
+        assert np.array_equal(res["rgba"][n].view(np.uint32), exp)
+    if "xyz_f32" in res:
+        assert np.isnan(res["xyz_f32"][n][~valid]).all()
+        assert np.allclose(res["xyz_f32"][n][valid], ref_np["xyz"][valid], rtol=2e-7, atol=1e-7)
+
+
+def _k3_own_output_case(name, set_name):
+    """A whole-tile MSPA_PAIR_FAST launch (96 x 128: tests/pair_route_cases.py's smallest) in which ONE output is the caller's own
+    buffer and every other pointer, the depth table included, is the allocator's.  Skewed, that output sits one / three units past
+    a boundary -- int16 pairs at 4 mod 8 (their documented 4 bytes), float32 and int32 at 4 / 12 mod 16, uint8 at 1 / 3 mod 4, int64
+    at 8 mod 16 -- and route() (csrc/pair_route.h) sees ``aligned == false`` exactly when ``data_ptr() % K3_POINTER_NEEDS[name]``
+    is not 0: the general whole-tile kernel (MSPA_KERNEL_PAIR_FAST) then runs instead of MSPA_KERNEL_PAIR_FAST_TIGHT, which ``run``
+    asserts from the pointers it handed over; a bitset at 8 mod 16 keeps the tight kernel (it needs 8)."""
+    outputs = K3_FAST_SETS[set_name]
+
+    @case(f"pair_reproject_own_{name}", "k3", ["pair_reproject"], aligned={"own/pix_i16": (4, ALIGN_PIX)} if name == "pix_i16" else None,
+          own_buffers=(name,))
+    class _OwnOutput:
+        @staticmethod
+        def build():
+            i = _k3_inputs("tight96x128")
+            i["depth"] = Kept(i["depth"])
+            return i
+
+        @staticmethod
+        def run(i):
+            import pair_route_cases as R
+            n, hw, depth = len(K3_PAIRS), i["hw"], i["depth"].tensor
+            out = engine.alloc_pair_outputs(n, hw, outputs, DEV)
+            out[name] = own(name, out[name].shape, out[name].dtype)
+            engine.pair_reproject(depth, i["mats"], i["pairs"], hw, out, rgb=i["rgb"] if "rgba" in outputs else None, flags=_lib.PAIR_FAST)
+            ran = _lib.load().mspa_pair_reproject_last_kernel()
+            assert depth.data_ptr() % 4 == 0 and all(t.data_ptr() % K3_POINTER_NEEDS[k] == 0 for k, t in out.items() if k in K3_POINTER_NEEDS and k != name)
+            aligned = out[name].data_ptr() % K3_POINTER_NEEDS[name] == 0
+            want = R.parent_route(hw[0], hw[1], hw[0], hw[1], R.bits(outputs), aligned, R.FAST)
+            assert want.err == 0 and want.family == (R.TIGHT_FAMILY if aligned else R.FAST_FAMILY) and ran == want.family, (name, aligned, ran, want)
+            return out
+
+        @staticmethod
+        def expect(i, z):
+            z = host(z)
+            for n, ((a, _b), (_c, ref_np)) in enumerate(zip(K3_PAIRS, _k3_references(i))):
+                _k3_check_some(z, n, ref_np, i["hw"], i["sc"].color[i["ids"][a]])
+    return _OwnOutput
+
+
+for _name, _set in (("pix_i16", "dense"), ("xyz_f32", "dense"), ("rgba", "dense"), ("vis_u8", "dense"), ("vis_bits", "corr")):
+    _k3_own_output_case(_name, _set)
+
+
+def _k3_kept_depth_case(shape, set_names, family):
+    """MSPA_PAIR_FAST launches whose depth table and outputs are the allocator's, so that route() keeps the whole-tile (96 x 128)
+    or the rectangular-tile (64 x 80 over 32 x 40) kernel while ``rgb``, ``mats`` and ``pairs`` are skewed -- ``run`` asserts the
+    family that ran.  The whole-tile kernel's dense set reads a row's colour bytes with one 32-bit buffer load per lane at byte
+    ``stripe * 192 + 3 * lane - 1`` of the row (lane 0: byte 0): (rgb + f1 * P * 3 + row * W * 3 + 3 * lane - 1) % 4 takes every
+    residue in any run, wherever ``rgb`` starts, and no load begins in front of ``rgb``; there is no guard and none is needed (the
+    rectangular kernel has no set with colour).  What moves with rgb % 4 = 1 / 3 is WHICH lanes load off a word."""
+    @case(f"pair_reproject_kept_depth_{shape}", "k3", ["pair_reproject"])
+    class _KeptDepth:
+        @staticmethod
+        def build():
+            i = _k3_inputs(shape)
+            i["depth"] = Kept(i["depth"])
+            return i
+
+        @staticmethod
+        def run(i):
+            import pair_route_cases as R
+            n, hw, depth = len(K3_PAIRS), i["hw"], i["depth"].tensor
+            dh, dw = depth.shape[1:]
+            mode = skewed_mode()
+            if mode:                                      # uint8 at 1 / 3 mod 4, float64 at 8 mod 16, int32 at 4 / 12 mod 16
+                assert i["rgb"].data_ptr() % 4 == {"a": 1, "b": 3}[mode] and i["mats"].data_ptr() % 16 == 8
+                assert i["pairs"].data_ptr() % 16 == {"a": 4, "b": 12}[mode] and depth.data_ptr() % 4 == 0
+            out = {}
+            for name in set_names:
+                outputs = K3_FAST_SETS[name]
+                for suffix, flags in (("", _lib.PAIR_FAST), ("_stream", _lib.PAIR_FAST | _lib.PAIR_STREAM)):
+                    res = engine.alloc_pair_outputs(n, hw, outputs, DEV)
+                    engine.pair_reproject(depth, i["mats"], i["pairs"], hw, res, rgb=i["rgb"] if "rgba" in outputs else None, flags=flags)
+                    ran = _lib.load().mspa_pair_reproject_last_kernel()
+                    want = R.parent_route(dh, dw, hw[0], hw[1], R.bits(outputs), True, flags)
+                    assert want.err == 0 and ran == want.family == family, (shape, name, suffix, ran, want)
+                    out[name + suffix] = res
+            return out
+
+        @staticmethod
+        def expect(i, z):
+            z = host(z)
+            for n, ((a, _b), (_c, ref_np)) in enumerate(zip(K3_PAIRS, _k3_references(i))):
+                for res in z.values():
+                    _k3_check_some(res, n, ref_np, i["hw"], i["sc"].color[i["ids"][a]])
+    return _KeptDepth
+
+
+_k3_kept_depth_case("tight96x128", ("dense", "dense_xyz", "corr", "minimal"), 4)      # MSPA_KERNEL_PAIR_FAST_TIGHT
+_k3_kept_depth_case("rect64x80", ("corr", "minimal"), 6)                               # MSPA_KERNEL_PAIR_FAST_RECT
+
+
+def _corr_own_case(name, shape, sentence):
+    """mspa_pair_correspondences with the caller's own ``cpix`` (the fused kernel, 96 x 128) or ``workspace`` (61 x 83: the dense
+    route): both documented 16 bytes, so both sit at 16 mod 32 and nothing may change; 8 mod 16 is refused."""
+    @case(f"pair_correspondences_own_{name}", "k3", ["pair_correspondences"], aligned={f"own/{name}": (16, sentence)}, own_buffers=(name,),
+          defined={"cpix": lambda zero: np.broadcast_to((np.arange(host(zero["cpix"]).shape[2])[None, None, :] <
+                                                         host(zero["tile_counts"])[:, :, None])[..., None], zero["cpix"].shape)})
+    class _OwnCorr:
+        @staticmethod
+        def build():
+            i = _k3_inputs(shape)
+            i["depth"] = Kept(i["depth"])
+            return i
+
+        @staticmethod
+        def run(i):
+            n, hw, depth = len(K3_PAIRS), i["hw"], i["depth"].tensor
+            out = engine.alloc_pair_correspondences(n, hw, DEV)
+            workspace = None
+            if name == "cpix":
+                out["cpix"] = own("cpix", out["cpix"].shape, out["cpix"].dtype)
+            else:
+                workspace = own("workspace", (n * hw[0] * hw[1],), torch.int32)
+            return engine.pair_correspondences(depth, i["mats"], i["pairs"], hw, out, flags=_lib.PAIR_FAST, workspace=workspace)
+
+        @staticmethod
+        def expect(i, z):
+            from test_gpu_compact import check_pair
+            z = host(z)
+            for n, (_c, ref) in enumerate(_k3_references(i)):
+                check_pair(z, n, ref, i["hw"])
+    return _OwnCorr
+
+
+_corr_own_case("cpix", "tight96x128", ALIGN_CPIX)
+_corr_own_case("workspace", "ragged61x83", ALIGN_CORR_WORKSPACE)
 
 
 # =====================================================================================================================
@@ -898,13 +1127,17 @@ def _status_rows(path_of_status, ndim):
     return mask
 
 
-def _png_case(name, bits, h, w):
+def _png_case(name, bits, h, w, caller=False):
     """inflate_blocks_device -> png_unfilter(8)_device: every filter kind, images taller than one 64-row band where h says so; one
-    stream with a damaged trailer (declined by the inflate, skipped by the un-filter) and one image with a filter byte 5."""
+    stream with a damaged trailer (declined by the inflate, skipped by the un-filter) and one image with a filter byte 5.
+    ``caller``: the scanline blocks, the status array and the images are the caller's own buffers (``own``)."""
     row = w * (2 if bits == 16 else 1) + 1
+    pitch = (h * row + 255) // 256 * 256
+    owned = ("raw", "status", "images") if caller else ()
 
     @case(name, "ingest", ["inflate_blocks_device", "png_unfilter_device" if bits == 16 else "png_unfilter8_device"],
-          defined={"raw": _status_rows(("status_inflate",), 2), "images": _status_rows(("status",), 3)}, enqueue_only=ENQUEUES["inflate_blocks_device"])
+          defined={"raw": _status_rows(("status_inflate",), 2), "images": _status_rows(("status",), 3)}, enqueue_only=ENQUEUES["inflate_blocks_device"],
+          aligned={"src": (16, ALIGN_INFLATE), "own/raw": (256, ALIGN_INFLATE)} if caller else {"src": (16, ALIGN_INFLATE)}, own_buffers=owned)
     class _Png:
         @staticmethod
         def build():
@@ -928,9 +1161,23 @@ def _png_case(name, bits, h, w):
 
         @staticmethod
         def run(i):
+            unfilter = engine.png_unfilter_device if bits == 16 else engine.png_unfilter8_device
+            if caller:
+                # the caller's blocks at 256 mod 512 (their documented 256), its status at 4 / 12 mod 16; its images one / three
+                # elements past a boundary: int16 at 2 mod 4 -- png_unfilter_kernel's and png_unfilter_hard_kernel's word routes want
+                # ``((uintptr_t)out & 3u) == 0`` (w is even here, so the pointer alone decides) and every image takes the bytes route --,
+                # uint8 at 1 / 3 mod 4
+                n = i["off"].shape[0]
+                raw, status = engine.inflate_blocks_device(i["src"], i["off"], i["nb"], h * row, out=own("raw", (n, pitch), torch.uint8),
+                                                           status=own("status", (n,), torch.int32))
+                after_inflate = status.clone()
+                images = unfilter(raw, h, w, status, out=own("images", (n, h, w), torch.int16 if bits == 16 else torch.uint8))
+                if skewed_mode():                        # image k starts at images + k * h * w elements: h * w * 2 = 1156 is a multiple of 4
+                    assert raw.data_ptr() % 512 == 256 and images.data_ptr() % 4 == (2 if bits == 16 else {"a": 1, "b": 3}[skewed_mode()])
+                    assert bits != 16 or (w % 2 == 0 and (h * w * 2) % 4 == 0)      # so EVERY image fails ``(out & 3) == 0``, and for the address alone
+                return {"raw": raw, "status_inflate": after_inflate, "images": images, "status": status}
             raw, status = engine.inflate_blocks_device(i["src"], i["off"], i["nb"], h * row)
             after_inflate = status.clone()
-            unfilter = engine.png_unfilter_device if bits == 16 else engine.png_unfilter8_device
             return {"raw": raw, "status_inflate": after_inflate, "images": unfilter(raw, h, w, status), "status": status}
 
         @staticmethod
@@ -953,11 +1200,15 @@ _png_case("depth_png_17x33", 16, 17, 33)
 _png_case("depth_png_70x83", 16, 70, 83)                  # past one 64-row band
 _png_case("mask_png_17x33", 8, 17, 33)
 _png_case("mask_png_70x130", 8, 70, 130)
+_png_case("depth_png_own_17x34", 16, 17, 34, caller=True)       # an even width: only the images' address keeps the word routes away
+_png_case("mask_png_own_17x33", 8, 17, 33, caller=True)
 
 
-def _jpeg_case(name, hw):
+def _jpeg_case(name, hw, caller=False):
     @case(name, "ingest", ["jpeg_decode_device", "jpeg_decode_luma_device"],
-          defined={"rgb/0": _status_rows(("rgb", 1), 4), "luma/0": _status_rows(("luma", 1), 3)}, enqueue_only=ENQUEUES["jpeg_decode_device"])
+          defined={"rgb/0": _status_rows(("rgb", 1), 4), "luma/0": _status_rows(("luma", 1), 3)}, enqueue_only=ENQUEUES["jpeg_decode_device"],
+          aligned={"src": (4, ALIGN_JPEG_SRC), "desc": (16, ALIGN_JPEG_DESC)}, own_buffers=("rgb", "luma", "status_rgb", "status_luma") if caller else (),
+          refused_by="mspa_jpeg_decode_luma_device:" if caller else "mspa_jpeg_decode_device:")
     class _Jpeg:
         @staticmethod
         def build():
@@ -982,6 +1233,18 @@ def _jpeg_case(name, hw):
 
         @staticmethod
         def run(i):
+            if caller:
+                # the caller's pixels at 1 / 3 mod 4: color_kernel's ``((uintptr_t)o & 3u) == 0`` fails for every group of four
+                # pixels (o = out + 12 * group keeps out's residue), so all of them take the byte stores
+                n = i["off"].shape[0]
+                rgb, luma = own("rgb", (n,) + tuple(hw) + (3,), torch.uint8), own("luma", (n,) + tuple(hw), torch.uint8)
+                if skewed_mode():                        # (out + 12 * group) % 4 == out % 4 == 1 / 3: never 0
+                    assert rgb.data_ptr() % 4 == luma.data_ptr() % 4 == {"a": 1, "b": 3}[skewed_mode()]
+                # the grey decode FIRST: this case's refusal runs (src at 2 mod 4, desc at 8 mod 16) then stop in mspa_jpeg_decode_luma_device,
+                # where jpeg_17x33's and jpeg_61x83's stop in mspa_jpeg_decode_device
+                grey = engine.jpeg_decode_luma_device(i["src"], i["off"], i["nb"], i["desc"], hw, out=luma, status=own("status_luma", (n,), torch.int32))
+                return {"rgb": engine.jpeg_decode_device(i["src"], i["off"], i["nb"], i["desc"], hw, out=rgb, status=own("status_rgb", (n,), torch.int32)),
+                        "luma": grey}
             return {"rgb": engine.jpeg_decode_device(i["src"], i["off"], i["nb"], i["desc"], hw),
                     "luma": engine.jpeg_decode_luma_device(i["src"], i["off"], i["nb"], i["desc"], hw)}
 
@@ -1001,6 +1264,7 @@ def _jpeg_case(name, hw):
 
 _jpeg_case("jpeg_17x33", (17, 33))
 _jpeg_case("jpeg_61x83", (61, 83))
+_jpeg_case("jpeg_own_17x33", (17, 33), caller=True)
 
 
 @case("laplacian_moments", "ingest", ["laplacian_moments"], enqueue_only=ENQUEUES["laplacian_moments"])
@@ -1110,6 +1374,29 @@ class _Resize:
                 assert np.array_equal(got[k], pillow_resize(img, dst, FILTERS[f])), (src, dst, f, k)
 
 
+@case("resize_rgb_device_own", "ingest", ["resize_rgb_device"], enqueue_only=ENQUEUES["resize_rgb_device"],
+      own_buffers=tuple(f"resized{k}" for k in range(len(_Resize.PAIRS))))
+class _ResizeOwn:
+    """``_Resize`` into the caller's own ``out`` at 1 / 3 mod 4.  csrc/resize.hip's ``store4`` writes a 32-bit word where
+    ``((uintptr_t)p & 3) == 0`` and bytes elsewhere; p = out + row * W * 3 + 12 * group, and no W * 3 here (249, 99, 210) is a
+    multiple of 4, so which rows take which store moves with ``out % 4`` -- rows 0, 4, 8, .. take words in the plain run and bytes in
+    both skewed ones.  The sources' skew (``stage_rows``' words from the address rounded down to 4, the vertical pass's ``skew0`` /
+    ``skew_step``, the route switch on ``(src | row_pitch | image_pitch) & 3``) comes with the inputs, which are at 1 / 3 mod 4 too."""
+    build = _Resize.build
+    expect = _Resize.expect
+
+    @staticmethod
+    def run(i):
+        outs = [own(f"resized{k}", (3,) + dst + (3,), torch.uint8) for k, (_src, dst, _f) in enumerate(_Resize.PAIRS)]
+        if skewed_mode():
+            r = {"a": 1, "b": 3}[skewed_mode()]
+            assert all(o.data_ptr() % 4 == r for o in outs) and all(t.data_ptr() % 4 == r for t in i["dev"].values())
+            for o in outs:                               # row y's stores go to (out + y * W * 3 + 12 * group + 4 * d): the row's residue
+                pitch = o.shape[2] * 3                     # row 0 takes the byte stores now; with an odd pitch one of rows 1..3 takes words
+                assert pitch % 4 and o.data_ptr() % 4 != 0 and (pitch % 2 == 0 or any((o.data_ptr() + y * pitch) % 4 == 0 for y in (1, 2, 3)))
+        return [engine.resize_rgb_device(i["dev"][src], dst, f, out=outs[k], fallback=False) for k, (src, dst, f) in enumerate(_Resize.PAIRS)]
+
+
 # =====================================================================================================================
 # Export
 # =====================================================================================================================
@@ -1207,6 +1494,28 @@ class _PngEncode:
                 assert PU.strict_idat(data, h, w) == PU.strict_idat(PU.pillow_png(frame), h, w), (key, k)    # Pillow's filtered scanlines
                 assert np.array_equal(np.asarray(Image.open(io.BytesIO(data))), frame), (key, k)
                 assert not files[k, nbytes[k]:(nbytes[k] + 3) // 4 * 4].any()                              # "(the padding bytes are 0)"
+
+
+@case("png_encode_device_own", "export", ["png_encode_device"], defined={"small/0": _file_bytes("small", 4)}, enqueue_only=ENQUEUES["png_encode_device"],
+      aligned={"own/files": (4, ALIGN_PNG_ENCODE)}, own_buffers=("files", "nbytes"))
+class _PngEncodeOwn:
+    """``_PngEncode``'s small frames into the caller's own rows: ``out_dev 4 bytes`` -- copy_kernel stores whole 32-bit words at
+    ``out + k * out_pitch + i``, i a multiple of 4 -- so the rows sit at 4 mod 8 and 2 mod 4 is refused; ``nbytes`` at 8 mod 16; the
+    frames (``depth_dev 2 bytes``) come at 2 mod 4 / 6 mod 8 with the inputs."""
+    @staticmethod
+    def build():
+        i = _PngEncode.build()
+        return {"small_np": i["small_np"], "large_np": i["large_np"][:0], "small": i["small"]}
+
+    @staticmethod
+    def run(i):
+        n, h, w = i["small"].shape
+        pitch = (engine.png_encode_capacity((h, w)) + 3) // 4 * 4
+        return {"small": engine.png_encode_device(i["small"], out=own("files", (n, pitch), torch.uint8), nbytes=own("nbytes", (n,), torch.int64))}
+
+    @staticmethod
+    def expect(i, z):
+        _PngEncode.expect(i, {**z, "large": (z["small"][0][:0], z["small"][1][:0])})
 
 
 # =====================================================================================================================
@@ -1365,6 +1674,57 @@ class _SnappyDecode:
             elif kind in ("writer", "neighbour") or brc == blocks:
                 assert routed == blocks, (name, int(routed), blocks)
         assert taken > 100
+
+
+def small_snappy_stream():
+    """A hand-made stream of 31 bytes -> 42: a literal SHORTER than a word first, a copy (1-byte offset form) that reaches back to
+    output byte 0, a 20-byte literal, a copy (2-byte offset form) that reaches back to output byte 0 again.  -> (stream, output)."""
+    out, s = bytearray(b"abc"), bytearray([42])                  # the preamble: varint(42)
+    s += bytes([(3 - 1) << 2]) + b"abc"
+    s += bytes([((9 - 4) << 2) | 1, 3])                          # 9 bytes from 3 back
+    for _ in range(9):
+        out.append(out[-3])
+    lit = bytes(range(100, 120))
+    s += bytes([(20 - 1) << 2]) + lit
+    out += lit
+    s += bytes([((10 - 1) << 2) | 2, 32, 0])                     # 10 bytes from 32 back
+    for _ in range(10):
+        out.append(out[-32])
+    assert len(s) == 31 and len(out) == 42
+    return bytes(s), bytes(out)
+
+
+# each of the two: "One small read-back (the size(s) to allocate)"
+@case("snappy_decode_every_residue", "visindex", ["snappy_decompress_device", "snappy_decompress_blocks_device"])
+class _SnappyResidues:
+    """``small_snappy_stream`` four times in one ``src``, at offsets 0, 33, 66 and 99: whatever ``src % 4`` is, one copy starts at
+    each of 0, 1, 2 and 3 mod 4 (asserted in ``run``).  csrc/snappy_decode_loop.inc: ``mis = sp & 3``; ``wbase = p - ((p + mis) & 3)``
+    is negative for the three that start off a word (-1, -2, -3), and lane 0's ``fetch(wbase)`` takes the byte loop that reads the
+    bytes in front of the stream as zero; the last copy ends at ``src``'s last byte, so the window's last words take that loop too."""
+    OFFSETS = (0, 33, 66, 99)
+
+    @staticmethod
+    def build():
+        stream, want = small_snappy_stream()
+        buf = bytearray(b"\xee" * (_SnappyResidues.OFFSETS[-1] + len(stream)))
+        for o in _SnappyResidues.OFFSETS:
+            buf[o:o + len(stream)] = stream
+        return {"want": want, "src": dev(np.frombuffer(bytes(buf), dtype=np.uint8)), "off": _i64(_SnappyResidues.OFFSETS),
+                "nb": _i64([len(stream)] * 4), "sizes": _i64([len(want)] * 4)}
+
+    @staticmethod
+    def run(i):
+        assert sorted((i["src"].data_ptr() + o) % 4 for o in _SnappyResidues.OFFSETS) == [0, 1, 2, 3]
+        args = (i["src"], i["off"], i["nb"], i["sizes"])
+        return {"serial": engine.snappy_decompress_device(*args), "blocks": engine.snappy_decompress_blocks_device(*args)}
+
+    @staticmethod
+    def expect(i, z):
+        z = host(z)
+        for key in ("serial", "blocks"):
+            out, out_offsets, status = z[key][:3]
+            assert status.tolist() == [0] * 4 and out_offsets.tolist() == [0, 42, 84, 126, 168], (key, status, out_offsets)
+            assert out.tobytes() == i["want"] * 4, key
 
 
 # the early returns read nothing back, but the functions document read-backs (snappy_*: above; index_spans_to_lists: "Synchronises")
@@ -1602,6 +1962,55 @@ class _PairTable:
             assert np.array_equal(tile_counts, np.stack([np.bincount(want[t:t + rows], minlength=256) for t in range(0, n, rows)]))
             assert np.array_equal(begin, np.concatenate([[0], np.cumsum(np.bincount(want, minlength=256))]))
             assert np.array_equal(order, np.argsort(want, kind="stable"))
+
+
+# parquet_double_columns_device: "Two small read-backs."
+@case("pair_table_values_at_the_edges", "visindex", ["parquet_double_columns_device"])
+class _PairTableEdges:
+    """csrc/pair_table.hip ``load64``: "two aligned words where both lie inside the buffer, bytes otherwise".  Two PLAIN pages of
+    three DOUBLE values each, in buffers of their own:
+
+      front  [1 byte][3 values][16 bytes]   the first value starts at byte 1 of ``pages``.  With ``pages`` at 1 (3) mod 8 its address
+             is 2 (4) mod 8, ``lo_at`` = that address rounded down to 8 = pages - 1 (- 3) < base: the byte loop, whose result must not
+             know the bytes in front of the buffer.  In the plain run (pages at 0 mod 8) lo_at == base: the two-word form.
+      back   [16 bytes][1 byte][3 values]   the last value ENDS at the buffer's last byte, bytes 33 .. 40 of 41: its address is
+             (pages + 33) mod 8 = 1, 2 or 4, never 0, so lo_at + 16 >= pages + 32 + 16 > pages + 41 in every run: the byte loop.
+    The values in between take the two-word form everywhere."""
+    VALUES = (0x3FF8000000000000, 0x8000000000000000, 0x7FF8000000ABCDEF, 0x0000000000000001, 0xC08F400000000000, 0x7FF0000000000000)
+
+    @staticmethod
+    def build():
+        import struct
+        v = [struct.pack("<Q", x) for x in _PairTableEdges.VALUES]
+        front = b"\x11" + b"".join(v[:3]) + b"\x22" * 16
+        back = b"\x33" * 17 + b"".join(v[3:])
+        assert len(front) == len(back) == 41
+        one = lambda x: _i64([x])                                                # noqa: E731
+        return {"front": dev(np.frombuffer(front, dtype=np.uint8)), "back": dev(np.frombuffer(back, dtype=np.uint8)),
+                "tables": {"front": (one(1), one(24), one(3)), "back": (one(17), one(24), one(3))},
+                "flags": dev(np.zeros(1, dtype=np.int32)), "zero": one(0)}
+
+    @staticmethod
+    def run(i):
+        out = {}
+        for key in ("front", "back"):
+            pages, (off, size, values) = i[key], i["tables"][key]
+            r = pages.data_ptr() % 8
+            if key == "front" and r:
+                assert 0 < (r + 1) % 8 and (pages.data_ptr() + 1) // 8 * 8 < pages.data_ptr()        # shift != 0 and lo_at < base
+            if key == "back":
+                a = pages.data_ptr() + 33
+                assert a % 8 and a // 8 * 8 + 16 > pages.data_ptr() + 41                              # shift != 0 and lo_at + 16 > base + bytes
+            out[key] = engine.parquet_double_columns_device(pages, off, size, values, i["flags"], i["zero"], 3, i["zero"], i["zero"], i["zero"], i["zero"])
+        return out
+
+    @staticmethod
+    def expect(i, z):
+        z = host(z)
+        for key, want in (("front", _PairTableEdges.VALUES[:3]), ("back", _PairTableEdges.VALUES[3:])):
+            values, status = z[key]
+            assert values.view(np.uint64).tolist() == list(want), (key, values)
+            assert not any(np.asarray(status[k]).any() for k in ("layout", "levels", "indices", "values")) and status["null_pages"] == 0
 
 
 # =====================================================================================================================
