@@ -1203,6 +1203,57 @@ int mspa_instance_split_host(const uint8_t *labels, const uint8_t *valid, const 
                              int64_t P, int32_t *out_counts, int64_t *out_offsets, int32_t *workspace, double *out_xyz,
                              uint8_t *out_rgb, int32_t *out_pixel, double *out_lo, double *out_hi, int32_t reversed);
 
+/*
+ * Voxel-grid down-sampling of a RAGGED BATCH of clouds (csrc/voxel_segments.hip, rule in csrc/voxel_grid_core.h): one output row
+ * per occupied voxel of every segment, every column the mean over the voxel's rows, plus the voxel's row count.  The rule restates
+ * Open3D's voxel_down_sample as the maintainers recall it and is NOT checked against Open3D.  A batch is rows [N, C] f64 (xyz
+ * first, 3 <= C <= MSPA_VOXEL_MAX_COLUMNS) plus offsets [S + 1] int64 (offsets[0] = 0, ascending, offsets[S] = N <= 2^30, S <=
+ * MSPA_SEGMENTS_MAX).  Per segment and axis: min_bound = lo - voxel_size * 0.5 (lo the segment's minimum), idx = floor((p -
+ * min_bound) / voxel_size) < 2^21, key = ix << 42 | iy << 21 | iz.  Output: segments in order, voxels in ascending key order; a
+ * voxel's rows are summed in ascending input row index, sequentially for a run of m <= 64 rows and, for m > 64, as 64 lane sums
+ * (lane j: rows j, j + 64, ...) folded by strides 32 .. 1; mean = sum / m.  The same bits on every run: no atomic places a row or
+ * takes part in a sum.
+ * Every device entry point takes the offsets TWICE, as the segmented search does: the host copy, which it checks together with all
+ * other arguments before anything is enqueued (MSPA_EINVAL: null pointer, offsets that descend or do not start at 0, N > 2^30,
+ * S > 2^24, C out of range, voxel_size not positive and finite, workspace too small or misaligned), and the device copy the
+ * kernels read.  ALIGNMENT: workspace 16 bytes; every other buffer its element's size (f64 and int64: 8, int32: 4).
+ *   mspa_voxel_segments_tables_host    offsets -> tile_base [S + 1] int64: the exclusive prefix of ceil(n_s / 4096), the tiles the
+ *                                      extents pass cuts each segment into (so one huge segment does not serialise it).
+ *   mspa_voxel_segments_workspace_bytes  the one workspace of the three device calls (-1 for offsets that are no batch).  The
+ *                                      calls hand their intermediate tables to each other in it: pass the same bytes on.
+ *   mspa_voxel_segments_keys_device    -> keys_dev [N] int64 and segment_dev [N] int32 (the row's segment), and seg_voxels_dev
+ *                                      [S + 1] int32 zeroed, whose LAST word is the flag word: bit 0 a non-finite xyz, bit 1 an
+ *                                      index >= 2^21.  Such a row gets a clamped key, so nothing downstream indexes outside a
+ *                                      buffer.  The caller sorts the rows STABLY by key and then STABLY by segment and passes the
+ *                                      permutation on as order_dev [N] int64.
+ *   mspa_voxel_segments_heads_device   keys_dev, order_dev -> seg_voxels_dev[0 .. S): the occupied voxels of each segment.  A sorted
+ *                                      slot opens a voxel when it is the first of its segment or its key differs from its
+ *                                      predecessor's.  Every entry of order_dev is clamped into [0, N) and then into the segment
+ *                                      of its slot: an order_dev that is no such permutation gives wrong voxels, never an access
+ *                                      outside the buffers.  The caller reads seg_voxels_dev back (counts and flag word at once);
+ *                                      M is the sum of the counts.
+ *   mspa_voxel_segments_means_device   the same order_dev and workspace, M -> out_rows_dev [M, C] f64 and out_counts_dev [M] int32.
+ *                                      Voxels beyond those the heads call found (an M that is too large) are not written.
+ *   mspa_voxel_segments_host           the whole op on the CPU through the same header: the device's twin for tests and for
+ *                                      NumPy input, not a fallback.  out_rows_host [N, C] and out_counts_host [N] are sized for
+ *                                      the worst case and receive M = out_offsets_host[S] rows; out_offsets_host [S + 1];
+ *                                      *flags_out the flag word (non-zero: the caller refuses the batch).
+ */
+#define MSPA_VOXEL_MAX_COLUMNS 65536
+int mspa_voxel_segments_tables_host(const int64_t *offsets_host, int64_t S, int64_t *tile_base_out);
+int64_t mspa_voxel_segments_workspace_bytes(const int64_t *offsets_host, int64_t S);
+int mspa_voxel_segments_keys_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, double voxel_size,
+                                    const int64_t *offsets_dev, const int64_t *tile_base_dev, int64_t *keys_dev, int32_t *segment_dev,
+                                    int32_t *seg_voxels_dev, void *workspace, int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_voxel_segments_heads_device(const int64_t *offsets_host, int64_t S, const int64_t *offsets_dev, const int64_t *keys_dev,
+                                     const int64_t *order_dev, int32_t *seg_voxels_dev, void *workspace, int64_t workspace_bytes,
+                                     mspa_stream_t stream);
+int mspa_voxel_segments_means_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, const int64_t *offsets_dev,
+                                     const int64_t *order_dev, int64_t M, double *out_rows_dev, int32_t *out_counts_dev, void *workspace,
+                                     int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_voxel_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, double voxel_size,
+                             double *out_rows_host, int64_t *out_offsets_host, int32_t *out_counts_host, int32_t *flags_out);
+
 #ifdef __cplusplus
 }
 #endif

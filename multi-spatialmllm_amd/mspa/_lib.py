@@ -19,7 +19,8 @@ CORR_TILE_W, CORR_TILE_H, CORR_TILE_CAP = 64, 48, 64 * 48
 JPEG_DESC_BYTES = 4224
 KNN_GRID_BYTES, KNN_MAX_K = 112, 64      # csrc/knn_grid_core.h: sizeof(Grid), kMaxK
 SEGMENTS_MAX = 1 << 24                   # csrc/cloud_segments_core.h: kMaxSegments
-RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3      # Pillow's Image.Resampling numbers
+VOXEL_AXIS_BITS, VOXEL_MAX_COLUMNS = 21, 65536   # csrc/voxel_grid_core.h: kAxisBits; include/mspa.h: MSPA_VOXEL_MAX_COLUMNS
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3     # Pillow's Image.Resampling numbers
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
 # csrc/snappy_core.h: what mspa_snappy_decompress_host returns for, and the device writes as the status of, a stream it declines
@@ -240,6 +241,14 @@ _SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mspa_instance_split_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int32]),
+    "mspa_voxel_segments_tables_host": (c_int, [c_void_p, c_int64, c_void_p]),
+    "mspa_voxel_segments_workspace_bytes": (c_int64, [c_void_p, c_int64]),
+    "mspa_voxel_segments_keys_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_int64, c_void_p]),
+    "mspa_voxel_segments_heads_device": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_voxel_segments_means_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                                 c_int64, c_void_p]),
+    "mspa_voxel_segments_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

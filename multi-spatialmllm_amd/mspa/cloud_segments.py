@@ -232,6 +232,100 @@ def remove_statistical_outliers_segments_host(rows, offsets, nb_neighbors=20, st
     return rows[stats["keep"]], kept_offsets, stats["lo"], stats["hi"]
 
 
+VOXEL_NON_FINITE, VOXEL_OUT_OF_RANGE = 1, 2       # csrc/voxel_grid_core.h: the bits of the flag word
+
+
+def _check_voxel_size(voxel_size) -> float:
+    """Open3D's error kind for a bad size, and ``remove_statistical_outliers``' for its arguments."""
+    try:
+        size = float(voxel_size)
+    except (TypeError, ValueError):
+        size = float("nan")
+    if not (0.0 < size < float("inf")):
+        raise RuntimeError(f"voxel_down_sample: voxel_size must be positive and finite (got {voxel_size})")
+    return size
+
+
+def _raise_voxel_flags(flags: int, voxel_size: float) -> None:
+    if flags & VOXEL_NON_FINITE:
+        raise ValueError("voxel_down_sample: the cloud has non-finite coordinates")
+    if flags & VOXEL_OUT_OF_RANGE:
+        raise ValueError(f"voxel_down_sample: voxel_size {voxel_size} is too small for a segment's extent "
+                         f"(a voxel index reaches 2^{_lib.VOXEL_AXIS_BITS} on an axis)")
+
+
+def voxel_down_sample_segments(rows: torch.Tensor, offsets, voxel_size):
+    """A batch ``rows`` [N, C >= 3] (device; float64, or a dtype that widens to it exactly) with finite xyz in front and host
+    ``offsets`` [S + 1] -> ``(out_rows [M, C] float64, out_offsets [S + 1] host int64, counts [M] int32)``: per segment one row per
+    occupied voxel of a grid of ``voxel_size``, every column (colour and other extra columns included) the mean over the voxel's
+    rows, ``counts`` the rows each voxel took.  The rule is csrc/voxel_grid_core.h's: per axis ``min_bound = lo - voxel_size * 0.5``
+    with ``lo`` the segment's own minimum, ``idx = floor((p - min_bound) / voxel_size)``; segments stay in order and a segment's
+    voxels come in ascending (ix, iy, iz); a voxel's rows are summed in ascending row index, sequentially up to 64 rows and as 64
+    strided lane sums folded by halving strides above.  It restates Open3D's ``voxel_down_sample`` as the maintainers recall it
+    and is not checked against Open3D (whose output order is its hash map's).  The same bits on every run.  One read-back per call,
+    whatever S is: the per-segment voxel counts together with the flag word.  ``voxel_size <= 0`` or non-finite raises RuntimeError;
+    a non-finite xyz anywhere, or a voxel index of 2^21 or more on an axis (``voxel_size`` too small), raises ValueError.  torch is
+    plumbing: two stable sorts (by key, then by segment; one when S = 1)."""
+    size = _check_voxel_size(voxel_size)
+    _require(isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[1] >= 3, "rows: a device tensor [N, C >= 3]")
+    rows = _check("rows", rows.to(torch.float64).contiguous(), torch.float64, (None, (3,)))
+    N, C = int(rows.shape[0]), int(rows.shape[1])
+    _require(C <= _lib.VOXEL_MAX_COLUMNS, f"rows: at most {_lib.VOXEL_MAX_COLUMNS} columns, got {C}")
+    off = _offsets(offsets, N)
+    _require(N <= 1 << 30, f"rows: at most 2^30 rows, got {N}")
+    S = off.size - 1
+    dev = rows.device
+    if N == 0:
+        return (torch.empty((0, C), dtype=torch.float64, device=dev), np.zeros((S + 1,), dtype=np.int64),
+                torch.empty((0,), dtype=torch.int32, device=dev))
+    lib = _lib.load()
+    tile_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
+    off_dev, base_dev = _upload(off, tile_base, device=dev)
+    keys = torch.empty((N,), dtype=torch.int64, device=dev)
+    segment = torch.empty((N,), dtype=torch.int32, device=dev)
+    seg_voxels = torch.empty((S + 1,), dtype=torch.int32, device=dev)
+    work = _workspace(int(lib.mspa_voxel_segments_workspace_bytes(off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_voxel_segments_keys_device(_ptr(rows), C, off.ctypes.data, S, size, _ptr(off_dev), _ptr(base_dev), _ptr(keys),
+                                                   _ptr(segment), _ptr(seg_voxels), _ptr(work), int(work.numel()), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    if S > 1:                                              # stably by segment behind stably by key: (segment, key), ties in row order
+        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    _lib.check(lib.mspa_voxel_segments_heads_device(off.ctypes.data, S, _ptr(off_dev), _ptr(keys), _ptr(order), _ptr(seg_voxels), _ptr(work),
+                                                    int(work.numel()), _stream_ptr()))
+    back = seg_voxels.cpu().numpy()                        # THE read-back
+    _raise_voxel_flags(int(back[S]), size)
+    out_offsets = np.zeros((S + 1,), dtype=np.int64)
+    np.cumsum(back[:S], out=out_offsets[1:])
+    M = int(out_offsets[-1])
+    out_rows = torch.empty((M, C), dtype=torch.float64, device=dev)
+    counts = torch.empty((M,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_voxel_segments_means_device(_ptr(rows), C, off.ctypes.data, S, _ptr(off_dev), _ptr(order), M, _ptr(out_rows), _ptr(counts),
+                                                    _ptr(work), int(work.numel()), _stream_ptr()))
+    return out_rows, out_offsets, counts
+
+
+def voxel_down_sample_segments_host(rows, offsets, voxel_size):
+    """``voxel_down_sample_segments`` on the CPU for NumPy input, through the same header (mspa_voxel_segments_host): NumPy arrays
+    out, the same exceptions.  The device's twin for tests and for input that has no device, not a fallback."""
+    size = _check_voxel_size(voxel_size)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] < 3 or rows.shape[1] > _lib.VOXEL_MAX_COLUMNS:
+        raise ValueError(f"mspa.cloud_segments: rows: expected [N, C >= 3], got {list(rows.shape)}")
+    N, C = rows.shape
+    off = _offsets(offsets, N)
+    S = off.size - 1
+    out_rows = np.empty((N, C), dtype=np.float64)
+    out_counts = np.empty((N,), dtype=np.int32)
+    out_offsets = np.zeros((S + 1,), dtype=np.int64)
+    flags = np.zeros((1,), dtype=np.int32)
+    _lib.check(_lib.load().mspa_voxel_segments_host(rows.ctypes.data, C, off.ctypes.data, S, size, out_rows.ctypes.data, out_offsets.ctypes.data,
+                                                    out_counts.ctypes.data, flags.ctypes.data))
+    _raise_voxel_flags(int(flags[0]), size)
+    M = int(out_offsets[-1])
+    return out_rows[:M].copy(), out_offsets, out_counts[:M].copy()
+
+
 def boxes_of(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
     """Extents lo / hi [..., 3] -> [..., 6]: ``[(hi + lo) / 2, hi - lo]``, what ``ops.calculate_aabb`` returns for the rows they
     span; NaN where lo > hi (the +inf / -inf of a segment without rows).  Enqueue only."""

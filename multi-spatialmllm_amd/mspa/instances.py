@@ -113,11 +113,15 @@ class InstanceClouds:
             offsets[1:] = ends.reshape(len(labels), F)[:, -1]
         return self.offsets[segments] - (ends - lengths), lengths, offsets, labels - 1
 
-    def by_object(self):
+    def by_object(self, voxel_size=None):
         """``(rows, offsets, object_ids)``: the same rows regrouped so that the rows of object ``object_ids[j]`` over all images are
         ``rows[offsets[j]:offsets[j + 1]]``, value for value ``object_cloud(object_ids[j])``; the objects with at least one row,
         ascending; ``offsets`` and ``object_ids`` are host int64 arrays.  One device gather whose index is built from the host
-        ``offsets``: a run table of O * F entries goes up, the index itself is expanded on the device.  Enqueue only."""
+        ``offsets``: a run table of O * F entries goes up, the index itself is expanded on the device.  Enqueue only.
+        With a ``voxel_size`` the regrouped rows are the voxel means of each object's fused cloud instead, value for value
+        ``ops.voxel_down_sample(object_cloud(object_ids[j]), voxel_size)``: every overlapping frame contributes its own sample of
+        the same surface, and the grid leaves one row per occupied voxel.  That form makes the one read-back of
+        ``cloud_segments.voxel_down_sample_segments`` and raises its exceptions; it needs the rows on the device."""
         shift, lengths, offsets, object_ids = self._object_runs()
         total = int(offsets[-1])
         if self.rows.is_cuda:
@@ -126,14 +130,20 @@ class InstanceClouds:
         else:
             shift, lengths = torch.from_numpy(shift), torch.from_numpy(lengths)
         index = torch.arange(total, dtype=torch.int64, device=self.rows.device) + torch.repeat_interleave(shift, lengths, output_size=total)
-        return self.rows.index_select(0, index), offsets, object_ids
+        rows = self.rows.index_select(0, index)
+        if voxel_size is not None:
+            from . import cloud_segments
+            rows, offsets, _counts = cloud_segments.voxel_down_sample_segments(rows, offsets, voxel_size)
+        return rows, offsets, object_ids
 
-    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0):
+    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None):
         """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
         ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``
-        [O + 1]; ``boxes`` [O, 6] float64 (device) their ``calculate_aabb``, NaN where nothing is kept."""
+        [O + 1]; ``boxes`` [O, 6] float64 (device) their ``calculate_aabb``, NaN where nothing is kept.  With a ``voxel_size`` each
+        fused cloud is down-sampled first (``by_object(voxel_size)``), then cleaned: the neighbours of a point are then other
+        places of the surface, not its own copies from other frames."""
         from . import cloud_segments
-        rows, offsets, object_ids = self.by_object()
+        rows, offsets, object_ids = self.by_object(voxel_size)
         kept, kept_offsets, lo, hi = cloud_segments.remove_statistical_outliers_segments(rows, offsets, nb_neighbors, std_ratio)
         return kept, kept_offsets, object_ids, cloud_segments.boxes_of(lo, hi)
 

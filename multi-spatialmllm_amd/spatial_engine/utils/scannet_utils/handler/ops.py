@@ -16,6 +16,8 @@ from ._images import read_color_rgb, read_depth
 
 __all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
            "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
+# (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample`` below is this project's own and is reached
+# as ``ops.voxel_down_sample``)
 
 
 def _same_device(a, b):
@@ -115,6 +117,26 @@ def remove_statistical_outliers(point_cloud_data, nb_neighbors=20, std_ratio=1.0
     from .info_handler import _like                 # (info_handler imports this module: not at the top)
     ind = _like(ind, point_cloud_data)
     return data[ind.to(data.device) if is_tensor else ind, :]
+
+
+def voxel_down_sample(point_cloud_data, voxel_size):
+    """[N, C >= 3] cloud -> [M, C] float64: one row per occupied voxel of a grid of ``voxel_size`` whose origin is the cloud's
+    per-axis minimum minus half a voxel; every column (colour and other extra columns included) is the mean over the voxel's rows.
+    The step in front of ``remove_statistical_outliers`` for a cloud fused from overlapping views.  It is the S = 1 case of
+    ``mspa.cloud_segments.voxel_down_sample_segments`` (rule in csrc/voxel_grid_core.h): voxels in ascending (ix, iy, iz), a
+    voxel's rows summed in ascending row order, the same bits on every run.  The rule restates Open3D's ``voxel_down_sample`` as
+    the maintainers recall it and is not checked against Open3D (whose row order is its hash map's); Open3D is not a dependency.
+    NumPy in gives NumPy out (the host twin of the kernels), a device tensor in gives a device tensor out; N = 0 returns the empty
+    [0, C].  ``voxel_size <= 0`` or non-finite raises RuntimeError, as Open3D does; non-finite coordinates, or a size so small
+    that a voxel index reaches 2^21 on an axis, raise ValueError.  No reference counterpart."""
+    from mspa import cloud_segments
+    is_tensor = isinstance(point_cloud_data, torch.Tensor)
+    data = point_cloud_data if is_tensor else np.asarray(point_cloud_data)
+    offsets = np.array([0, int(data.shape[0])], dtype=np.int64)
+    if is_tensor and data.is_cuda:
+        return cloud_segments.voxel_down_sample_segments(data, offsets, voxel_size)[0]
+    out = cloud_segments.voxel_down_sample_segments_host(data.numpy() if is_tensor else data, offsets, voxel_size)[0]
+    return torch.from_numpy(out) if is_tensor else out
 
 
 def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
