@@ -1254,6 +1254,48 @@ int mspa_voxel_segments_means_device(const double *rows_dev, int64_t C, const in
 int mspa_voxel_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, double voxel_size,
                              double *out_rows_host, int64_t *out_offsets_host, int32_t *out_counts_host, int32_t *flags_out);
 
+/*
+ * DBSCAN of a RAGGED BATCH of clouds (csrc/dbscan_segments.hip, rule in csrc/dbscan_core.h): per segment the labels of
+ * sklearn.cluster.DBSCAN(eps, min_samples = min_points, algorithm = "kd_tree"), value for value, and the rows of the largest
+ * cluster.  The batch is the down-sample's: rows [N, C] f64 (xyz first, 3 <= C <= MSPA_VOXEL_MAX_COLUMNS) plus offsets [S + 1].
+ * near(i, j) <=> (dx * dx + dy * dy) + dz * dz <= eps * eps in float64, i near itself; a row is core with min_points near rows;
+ * clusters are the components of the core rows under near, numbered in ascending order of their lowest core row; a row that is not
+ * core takes the lowest cluster number among its near core rows, or -1; the largest cluster has the most rows, a tie going to the
+ * lowest number.  The same values on every run: the union-find hooks the larger root under the smaller by compare-and-swap, whose
+ * result no arrival order changes; no atomic places a row or takes part in a floating-point sum.
+ * The cells are the down-sample's at voxel size mspa_dbscan_cell_side(eps): the caller runs mspa_voxel_segments_keys_device with
+ * that size and seg_voxels_dev = seg_dev + S (which zeroes the flag word seg_dev[2 S]), sorts as for the down-sample, and passes
+ * keys_dev and order_dev on.  The device entry point takes the offsets TWICE, as the down-sample does, and checks every argument
+ * from the host copy before anything is enqueued (MSPA_EINVAL: null pointer, offsets that descend or do not start at 0, N > 2^30,
+ * S > 2^24, C out of range, eps or its square not positive, normal and finite, min_points < 1, workspace too small or
+ * misaligned).  ALIGNMENT: workspace 16 bytes; every other buffer its element's size (f64 and int64: 8, int32: 4, uint8: 1).
+ *   mspa_dbscan_cell_side              eps -> the cell side, eps * (1 + 2^-20): any near pair then lies in cells whose indices
+ *                                      differ by at most 1 per axis (the argument is in csrc/dbscan_core.h); -1 for a bad eps.
+ *   mspa_dbscan_segments_workspace_bytes  the workspace of the device call (-1 for offsets that are no batch).
+ *   mspa_dbscan_segments_device        -> labels_dev [N] int32 in input row order, seg_dev [2 S + 1] int32: [0, S) the rows of each
+ *                                      segment's largest cluster (written where keep_dev is given, else zero), [S, 2 S) the
+ *                                      clusters of each segment, and the flag word seg_dev[2 S], into which bit 2 is ORed where a
+ *                                      union-find loop reached its cap (the keys call's bits 0 and 1 stay).  keep_dev [N] uint8 or
+ *                                      null: 1 for the rows of the largest cluster; with it kept_lo_dev and kept_hi_dev [S, 3] f64
+ *                                      receive the kept rows' extents (+inf / -inf where nothing is kept) and tile_base_dev is
+ *                                      mspa_voxel_segments_tables_host's table on the device; without it the three may be null.
+ *                                      Every entry of order_dev is clamped into [0, N) and then into the segment of its slot, and
+ *                                      a negative key counts as 0: arguments that are not the keys call's and its sort give wrong
+ *                                      labels, never an access outside the buffers.  Thirteen launches with keep_dev, nine
+ *                                      without, whatever S is; with N = 0 only the counts of seg_dev are written.
+ *   mspa_dbscan_segments_host          the whole op on the CPU through the same header: the device's twin for tests and for
+ *                                      NumPy input, not a fallback.  labels_host [N] int32, clusters_host [S] int32, keep_host [N]
+ *                                      uint8 and kept_host [S] int32 (both or neither may be null), *flags_out the flag word.
+ */
+double mspa_dbscan_cell_side(double eps);
+int64_t mspa_dbscan_segments_workspace_bytes(const int64_t *offsets_host, int64_t S);
+int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, double eps, int64_t min_points,
+                                const int64_t *offsets_dev, const int64_t *keys_dev, const int64_t *order_dev, const int64_t *tile_base_dev,
+                                int32_t *labels_dev, uint8_t *keep_dev, double *kept_lo_dev, double *kept_hi_dev, int32_t *seg_dev,
+                                void *workspace, int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_dbscan_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, double eps, int64_t min_points,
+                              int32_t *labels_host, int32_t *clusters_host, uint8_t *keep_host, int32_t *kept_host, int32_t *flags_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,12 @@ _SIGNATURES = {
     "mspa_voxel_segments_means_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                                  c_int64, c_void_p]),
     "mspa_voxel_segments_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_dbscan_cell_side": (c_double, [c_double]),
+    "mspa_dbscan_segments_workspace_bytes": (c_int64, [c_void_p, c_int64]),
+    "mspa_dbscan_segments_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_dbscan_segments_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
 }
 
 

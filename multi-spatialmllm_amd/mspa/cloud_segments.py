@@ -9,6 +9,10 @@ is not ``torch.sum``'s, so a threshold may differ from ``ops.remove_statistical_
 
 torch is plumbing, as in ``mspa.engine``: the segmented order statistics (two sorts), the one sort of the keys, ``nonzero`` and
 ``index_select``.  Host tables go up through pinned memory without a host wait.
+
+Two further ops take the same batch: ``voxel_down_sample_segments`` (csrc/voxel_segments.hip) thins every segment on a voxel grid,
+and ``dbscan_segments`` / ``largest_cluster_segments`` (csrc/dbscan_segments.hip, rule in csrc/dbscan_core.h) label every segment
+as scikit-learn's DBSCAN does and keep its largest cluster.
 """
 from __future__ import annotations
 
@@ -324,6 +328,147 @@ def voxel_down_sample_segments_host(rows, offsets, voxel_size):
     _raise_voxel_flags(int(flags[0]), size)
     M = int(out_offsets[-1])
     return out_rows[:M].copy(), out_offsets, out_counts[:M].copy()
+
+
+DBSCAN_CAP_REACHED = 4                            # csrc/dbscan_core.h: the third bit of the flag word
+
+
+def _check_dbscan(eps, min_points):
+    """``remove_statistical_outliers``' error kind for bad arguments -> (eps, min_points, the cell side)."""
+    try:
+        e, m = float(eps), int(min_points)
+        if m != min_points:
+            m = 0
+    except (TypeError, ValueError):
+        e, m = float("nan"), 0
+    side = _lib.load().mspa_dbscan_cell_side(e) if e == e else -1.0
+    if not side > 0.0 or m < 1:
+        raise RuntimeError(f"cluster_dbscan: eps must be positive and finite and min_points at least 1 (got {eps}, {min_points})")
+    return e, m, side
+
+
+def _raise_dbscan_flags(flags: int, eps: float) -> None:
+    if flags & VOXEL_NON_FINITE:
+        raise ValueError("cluster_dbscan: the cloud has non-finite coordinates")
+    if flags & VOXEL_OUT_OF_RANGE:
+        raise ValueError(f"cluster_dbscan: eps {eps} is too small for a segment's extent "
+                         f"(a cell index reaches 2^{_lib.VOXEL_AXIS_BITS} on an axis)")
+    if flags & DBSCAN_CAP_REACHED:
+        raise RuntimeError("cluster_dbscan: a union-find loop reached its iteration cap (csrc/dbscan_core.h)")
+
+
+def _dbscan_device(rows: torch.Tensor, offsets, eps, min_points, want_keep: bool):
+    """The device op: (labels [N] int32, keep [N] uint8 or None, back [2 S + 1] host int32: kept, clusters, flag word, and the kept
+    rows' extents lo / hi [S, 3] or None).  Holds THE read-back of ``dbscan_segments`` and ``largest_cluster_segments``."""
+    e, m, side = _check_dbscan(eps, min_points)
+    _require(isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[1] >= 3, "rows: a device tensor [N, C >= 3]")
+    xyz = _check("rows", rows[:, :3].to(torch.float64).contiguous(), torch.float64, (None, 3))
+    N = int(xyz.shape[0])
+    off = _offsets(offsets, N)
+    _require(N <= 1 << 30, f"rows: at most 2^30 rows, got {N}")
+    S = off.size - 1
+    dev = rows.device
+    labels = torch.empty((N,), dtype=torch.int32, device=dev)
+    keep = torch.empty((N,), dtype=torch.uint8, device=dev) if want_keep else None
+    lo = torch.full((S, 3), float("inf"), dtype=torch.float64, device=dev) if want_keep else None
+    hi = torch.full((S, 3), float("-inf"), dtype=torch.float64, device=dev) if want_keep else None
+    if N == 0:
+        return labels, keep, np.zeros((2 * S + 1,), dtype=np.int32), lo, hi
+    lib = _lib.load()
+    tile_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
+    off_dev, base_dev = _upload(off, tile_base, device=dev)
+    keys = torch.empty((N,), dtype=torch.int64, device=dev)
+    segment = torch.empty((N,), dtype=torch.int32, device=dev)
+    seg = torch.empty((2 * S + 1,), dtype=torch.int32, device=dev)
+    cells_work = _workspace(int(lib.mspa_voxel_segments_workspace_bytes(off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_voxel_segments_keys_device(_ptr(xyz), 3, off.ctypes.data, S, side, _ptr(off_dev), _ptr(base_dev), _ptr(keys),
+                                                   _ptr(segment), _ptr(seg[S:]), _ptr(cells_work), int(cells_work.numel()), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    if S > 1:                                              # stably by segment behind stably by key, as the down-sample sorts
+        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    work = _workspace(int(lib.mspa_dbscan_segments_workspace_bytes(off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_dbscan_segments_device(_ptr(xyz), 3, off.ctypes.data, S, e, m, _ptr(off_dev), _ptr(keys), _ptr(order), _ptr(base_dev),
+                                               _ptr(labels), _ptr(keep), _ptr(lo), _ptr(hi), _ptr(seg), _ptr(work), int(work.numel()),
+                                               _stream_ptr()))
+    back = seg.cpu().numpy()                               # THE read-back
+    _raise_dbscan_flags(int(back[2 * S]), e)
+    return labels, keep, back, lo, hi
+
+
+def dbscan_segments(rows: torch.Tensor, offsets, eps, min_points):
+    """A batch ``rows`` [N, C >= 3] (device; xyz in front, float64 or a dtype that widens to it exactly) and host ``offsets`` [S + 1]
+    -> ``(labels [N] int32 device, clusters [S] host int64)``: per segment the labels of
+    ``sklearn.cluster.DBSCAN(eps, min_samples=min_points, algorithm="kd_tree").fit(rows[a:b, :3]).labels_``, value for value, and the
+    number of clusters.  The rule is csrc/dbscan_core.h's: ``near(i, j)`` iff ``(dx*dx + dy*dy) + dz*dz <= eps*eps`` in float64, a
+    point near itself; a point is core with ``min_points`` near points, itself and duplicates included; clusters are the connected
+    components of the core points, numbered in ascending order of their lowest core row; any other point takes the lowest cluster
+    number among the core points near it, or -1.  The same values on every run.  One read-back per call, whatever S is: the
+    per-segment cluster counts together with the flag word.  ``eps <= 0``, non-finite ``eps`` or ``min_points < 1`` raises
+    RuntimeError; a non-finite xyz anywhere, or a cell index of 2^21 or more on an axis (``eps`` too small for a segment's extent),
+    raises ValueError.  torch is plumbing: the two stable sorts of the cell keys (one when S = 1).  The work of a point grows with
+    the rows of the 27 cells around it: thin fused clouds (``voxel_down_sample_segments``) first."""
+    labels, _keep, back, _lo, _hi = _dbscan_device(rows, offsets, eps, min_points, False)
+    S = (back.size - 1) // 2
+    return labels, back[S:2 * S].astype(np.int64)
+
+
+def largest_cluster_segments(rows: torch.Tensor, offsets, eps, min_points):
+    """``dbscan_segments`` and then, per segment, the rows of its largest cluster (the most rows, core and border together; a tie
+    goes to the lowest cluster number; a segment that is all noise keeps nothing): ``(rows_kept, offsets_kept, lo, hi, index)``,
+    shaped like ``clean_segments``' -- all columns and the dtype kept, ``offsets_kept`` [S + 1] a host int64 array, ``lo`` / ``hi``
+    [S, 3] float64 (device) the kept rows' extents (+inf / -inf where none stays), ``index`` [M] int64 (device) the kept rows'
+    indices into ``rows``, ascending.  One read-back per call, whatever S is: the kept counts with the flag word.  The exceptions are
+    ``dbscan_segments``'."""
+    _labels, keep, back, lo, hi = _dbscan_device(rows, offsets, eps, min_points, True)
+    S = (back.size - 1) // 2
+    kept_offsets = np.zeros((S + 1,), dtype=np.int64)
+    np.cumsum(back[:S], out=kept_offsets[1:])
+    index = torch.nonzero_static(keep.view(torch.bool), size=int(kept_offsets[-1])).flatten()    # its size is known: no read-back of its own
+    return rows.index_select(0, index), kept_offsets, lo, hi, index
+
+
+def _dbscan_host(rows, offsets, eps, min_points, want_keep: bool):
+    e, m, _side = _check_dbscan(eps, min_points)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < 3:
+        raise ValueError(f"mspa.cloud_segments: rows: expected [N, C >= 3], got {list(rows.shape)}")
+    xyz = np.ascontiguousarray(rows[:, :3], dtype=np.float64)
+    N = xyz.shape[0]
+    off = _offsets(offsets, N)
+    S = off.size - 1
+    labels = np.full((N,), -1, dtype=np.int32)
+    clusters, kept = np.zeros((S,), dtype=np.int32), np.zeros((S,), dtype=np.int32)
+    keep = np.zeros((N,), dtype=np.uint8)
+    flags = np.zeros((1,), dtype=np.int32)
+    _lib.check(_lib.load().mspa_dbscan_segments_host(xyz.ctypes.data, 3, off.ctypes.data, S, e, m, labels.ctypes.data, clusters.ctypes.data,
+                                                     keep.ctypes.data if want_keep else None, kept.ctypes.data if want_keep else None,
+                                                     flags.ctypes.data))
+    _raise_dbscan_flags(int(flags[0]), e)
+    return rows, off, labels, clusters.astype(np.int64), keep.astype(bool), kept.astype(np.int64)
+
+
+def dbscan_segments_host(rows, offsets, eps, min_points):
+    """``dbscan_segments`` on the CPU for NumPy input, through the same header (mspa_dbscan_segments_host): NumPy arrays out, the
+    same exceptions.  The device's twin for tests and for input that has no device, not a fallback."""
+    _rows, _off, labels, clusters, _keep, _kept = _dbscan_host(rows, offsets, eps, min_points, False)
+    return labels, clusters
+
+
+def largest_cluster_segments_host(rows, offsets, eps, min_points):
+    """``largest_cluster_segments`` on the CPU for NumPy input, through the same header: NumPy arrays out, the same exceptions."""
+    rows, off, _labels, _clusters, keep, kept = _dbscan_host(rows, offsets, eps, min_points, True)
+    S = off.size - 1
+    kept_offsets = np.zeros((S + 1,), dtype=np.int64)
+    np.cumsum(kept, out=kept_offsets[1:])
+    index = np.nonzero(keep)[0].astype(np.int64)
+    out = rows[index]
+    lo, hi = np.full((S, 3), np.inf), np.full((S, 3), -np.inf)
+    for s in range(S):
+        part = np.asarray(out[kept_offsets[s]:kept_offsets[s + 1], :3], dtype=np.float64)
+        if len(part):
+            lo[s], hi[s] = part.min(axis=0), part.max(axis=0)
+    return out, kept_offsets, lo, hi, index
 
 
 def boxes_of(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:

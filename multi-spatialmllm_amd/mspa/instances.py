@@ -82,13 +82,19 @@ class InstanceClouds:
         return torch.cat([self.cloud(i, target_id) for i in self.image_ids] or [self.rows[:0]])
 
     # ---- every segment at once (mspa.cloud_segments): launches and read-backs do not depend on the number of segments ----------
-    def cleaned(self, nb_neighbors=20, std_ratio=1.0) -> "InstanceClouds":
+    def cleaned(self, nb_neighbors=20, std_ratio=1.0, cluster=None) -> "InstanceClouds":
         """A new ``InstanceClouds`` of the same ``image_ids`` that holds, per (image, object), the rows
         ``ops.remove_statistical_outliers(cloud(image, object), nb_neighbors, std_ratio)`` keeps: ``counts``, ``offsets``, ``rows``,
         ``rgb``, ``lo`` / ``hi`` (and ``pixel``, where this one has it) are those of the kept rows.  One batched pass
-        (``cloud_segments.remove_statistical_outliers_segments``: two read-backs, its exceptions)."""
+        (``cloud_segments.remove_statistical_outliers_segments``: two read-backs, its exceptions).
+        With ``cluster=(eps, min_points)`` each cleaned segment is then cut down to its largest DBSCAN cluster
+        (``cloud_segments.largest_cluster_segments``: one more read-back, its exceptions) -- the blob a mask's edge bleeds onto the
+        wall behind the object is dense, so the statistical rule keeps it, and a box over both blobs is not the object's."""
         from . import cloud_segments
         rows, offsets, lo, hi, index = cloud_segments.clean_segments(self.rows, self.offsets, nb_neighbors, std_ratio)
+        if cluster is not None:
+            rows, offsets, lo, hi, of_cleaned = cloud_segments.largest_cluster_segments(rows, offsets, *cluster)
+            index = index.index_select(0, of_cleaned)
         shape = self.counts.shape
         return InstanceClouds(self.image_ids, np.diff(offsets).reshape(shape), rows, None if self.pixel is None else self.pixel.index_select(0, index),
                               lo.reshape(shape + (3,)), hi.reshape(shape + (3,)), None if self.rgb is None else self.rgb.index_select(0, index))
@@ -136,15 +142,19 @@ class InstanceClouds:
             rows, offsets, _counts = cloud_segments.voxel_down_sample_segments(rows, offsets, voxel_size)
         return rows, offsets, object_ids
 
-    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None):
+    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None, cluster=None):
         """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
         ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``
         [O + 1]; ``boxes`` [O, 6] float64 (device) their ``calculate_aabb``, NaN where nothing is kept.  With a ``voxel_size`` each
         fused cloud is down-sampled first (``by_object(voxel_size)``), then cleaned: the neighbours of a point are then other
-        places of the surface, not its own copies from other frames."""
+        places of the surface, not its own copies from other frames.  With ``cluster=(eps, min_points)`` each cleaned cloud is then
+        cut down to its largest DBSCAN cluster (``cloud_segments.largest_cluster_segments``), and the boxes are those of what is
+        kept."""
         from . import cloud_segments
         rows, offsets, object_ids = self.by_object(voxel_size)
         kept, kept_offsets, lo, hi = cloud_segments.remove_statistical_outliers_segments(rows, offsets, nb_neighbors, std_ratio)
+        if cluster is not None:
+            kept, kept_offsets, lo, hi, _index = cloud_segments.largest_cluster_segments(kept, kept_offsets, *cluster)
         return kept, kept_offsets, object_ids, cloud_segments.boxes_of(lo, hi)
 
 

@@ -291,7 +291,7 @@ class SceneInfoHandler:
         return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
 
     def instance_boxes(self, scene_id, image_ids=None, nb_neighbors=20, std_ratio=1.0, per="image", device="cuda", num_workers=8,
-                       voxel_size=None):
+                       voxel_size=None, cluster=None):
         """The rest of the tool chain for every object of a scene at once: ``instance_clouds`` -> cleaned clouds
         (``remove_statistical_outliers(cloud, nb_neighbors, std_ratio)`` per segment) -> boxes (``calculate_aabb``) -> IoU against
         ``get_object_gt_bbox(scene_id, target_id, axis_aligned=True)[:6]`` (``calculate_iou_3d``), in a number of launches and
@@ -306,7 +306,8 @@ class SceneInfoHandler:
         annotation has no such object.  Works on either path of ``instance_clouds``.  No reference counterpart.
         With ``per="object"`` a ``voxel_size`` down-samples each fused cloud on a voxel grid before it is cleaned
         (``InstanceClouds.cleaned_objects(voxel_size=...)``); with ``per="image"`` a size raises ValueError: a single view's cloud
-        is already one sample per pixel."""
+        is already one sample per pixel.  ``cluster=(eps, min_points)`` keeps, after the cleaning, each cloud's largest DBSCAN
+        cluster (``mspa.cloud_segments.largest_cluster_segments``): boxes, ``kept`` and IoU are taken from what is kept."""
         from mspa import cloud_segments
         if per not in ("image", "object"):
             raise ValueError(f"instance_boxes: per must be 'image' or 'object', got {per!r}")
@@ -315,11 +316,11 @@ class SceneInfoHandler:
         clouds = self.instance_clouds(scene_id, image_ids, False, device, num_workers)
         n_objects = self.get_num_objects(scene_id)
         if per == "image":
-            cleaned = clouds.cleaned(nb_neighbors, std_ratio)
+            cleaned = clouds.cleaned(nb_neighbors, std_ratio, cluster)
             boxes, kept, targets = cleaned.boxes(), cleaned.counts, np.arange(clouds.n_labels, dtype=np.int64) - 1
             out = {"image_ids": list(clouds.image_ids)}
         else:
-            _rows, offsets, targets, boxes = clouds.cleaned_objects(nb_neighbors, std_ratio, voxel_size)
+            _rows, offsets, targets, boxes = clouds.cleaned_objects(nb_neighbors, std_ratio, voxel_size, cluster)
             kept = np.diff(offsets)
             out = {"object_ids": targets}
         gt = np.full((len(targets), 6), np.nan)

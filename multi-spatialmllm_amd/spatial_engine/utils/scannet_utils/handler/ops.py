@@ -16,8 +16,8 @@ from ._images import read_color_rgb, read_depth
 
 __all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
            "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
-# (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample`` below is this project's own and is reached
-# as ``ops.voxel_down_sample``)
+# (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample`` and ``cluster_dbscan`` below are this
+# project's own and are reached as ``ops.voxel_down_sample`` and ``ops.cluster_dbscan``)
 
 
 def _same_device(a, b):
@@ -136,6 +136,28 @@ def voxel_down_sample(point_cloud_data, voxel_size):
     if is_tensor and data.is_cuda:
         return cloud_segments.voxel_down_sample_segments(data, offsets, voxel_size)[0]
     out = cloud_segments.voxel_down_sample_segments_host(data.numpy() if is_tensor else data, offsets, voxel_size)[0]
+    return torch.from_numpy(out) if is_tensor else out
+
+
+def cluster_dbscan(point_cloud_data, eps, min_points):
+    """[N, C >= 3] cloud -> labels [N] int32: density clustering of the xyz columns, -1 for noise.  The name and the arguments are
+    Open3D's ``cluster_dbscan(eps, min_points)``; the labels are scikit-learn's, value for value:
+    ``sklearn.cluster.DBSCAN(eps, min_samples=min_points, algorithm="kd_tree").fit(xyz).labels_`` (a point counts itself; clusters
+    are numbered in ascending order of their lowest core row; a point that is not core takes the lowest cluster number among the
+    core points within ``eps``).  It is the S = 1 case of ``mspa.cloud_segments.dbscan_segments`` (rule in csrc/dbscan_core.h), the
+    same values on every run.  The step between ``remove_statistical_outliers`` and ``calculate_aabb`` for a cloud whose mask
+    bleeds onto what lies behind the object: keep ``cloud[labels == np.bincount(labels[labels >= 0]).argmax()]``.  NumPy in gives
+    NumPy out (the host twin of the kernels), a device tensor in gives a device tensor out; N = 0 returns the empty [0].
+    ``eps <= 0``, non-finite ``eps`` or ``min_points < 1`` raises RuntimeError; non-finite coordinates, or an ``eps`` so small that a
+    cell index reaches 2^21 on an axis, raise ValueError.  Neither Open3D nor scikit-learn is a dependency.  No reference
+    counterpart."""
+    from mspa import cloud_segments
+    is_tensor = isinstance(point_cloud_data, torch.Tensor)
+    data = point_cloud_data if is_tensor else np.asarray(point_cloud_data)
+    offsets = np.array([0, int(data.shape[0])], dtype=np.int64)
+    if is_tensor and data.is_cuda:
+        return cloud_segments.dbscan_segments(data, offsets, eps, min_points)[0]
+    out = cloud_segments.dbscan_segments_host(data.numpy() if is_tensor else data, offsets, eps, min_points)[0]
     return torch.from_numpy(out) if is_tensor else out
 
 
