@@ -71,8 +71,6 @@ __global__ void __launch_bounds__(kWave) knn_kernel(Grid g, const double *__rest
     if (evals) evals[o] = (int32_t)e;
 }
 
-int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
-
 }  // namespace knn
 }  // namespace mspa
 
@@ -94,7 +92,7 @@ extern "C" int mspa_knn_grid_host(const double *lo, const double *hi, int64_t n,
 
 extern "C" int64_t mspa_knn_workspace_bytes(int64_t n, int32_t k) {
     if (n < 0 || n > knn::kMaxPoints || k < 1 || k > knn::kMaxK) return -1;
-    return knn::align16(n * 24) + knn::align16(n * 4) + knn::align16((knn::max_cells(n, k) + 1) * 4);
+    return align16(n * 24) + align16(n * 4) + align16((knn::max_cells(n, k) + 1) * 4);
 }
 
 extern "C" int mspa_knn_cells_device(const double *xyz_dev, int64_t n, const void *grid_host, int32_t *cells_dev, void *stream) {
@@ -122,8 +120,8 @@ extern "C" int mspa_knn_mean_distance_device(const double *xyz_dev, int64_t n, i
     if ((uintptr_t)workspace & 15u) return fail(MSPA_EINVAL, "mspa_knn_mean_distance_device: workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     double *pts = (double *)workspace;
-    int32_t *sorted_cells = (int32_t *)((uint8_t *)workspace + knn::align16(n * 24));
-    int32_t *starts = (int32_t *)((uint8_t *)sorted_cells + knn::align16(n * 4));
+    int32_t *sorted_cells = (int32_t *)((uint8_t *)workspace + align16(n * 24));
+    int32_t *starts = (int32_t *)((uint8_t *)sorted_cells + align16(n * 4));
     hipLaunchKernelGGL(knn::gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, xyz_dev, order_dev, n, pts, sorted_cells);
     hipLaunchKernelGGL(knn::starts_kernel, dim3((unsigned)(((int64_t)g.cells + 1 + 255) / 256)), dim3(256), 0, st,
                        (const int32_t *)sorted_cells, n, g.cells, starts);

@@ -16,7 +16,7 @@
 //   5. seg_stats_kernel  -- one workgroup of 256 per segment, three passes over its avg: sum -> mean, squared deviations -> sd and
 //      thr, keep flags with the kept count and the kept rows' extents.  No atomics: lane sums, then folds through LDS.
 #include "mspa_common.h"
-#include "cloud_segments_core.h"
+#include "segments_device.h"
 
 namespace mspa {
 namespace segs {
@@ -173,16 +173,6 @@ __global__ void __launch_bounds__(kLanes) seg_stats_kernel(const double *__restr
     }
 }
 
-int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
-
-// N of a batch the entry points take, or -1 with the error text set.
-int64_t checked_batch(const char *who, const int64_t *offsets_host, int64_t S) {
-    const int64_t N = batch_rows(offsets_host, S);
-    if (N < 0)
-        fail(MSPA_EINVAL, std::string(who) + ": offsets must be [S + 1] with offsets[0] = 0, ascending, at most 2^30 rows and 2^24 segments");
-    return N;
-}
-
 }  // namespace segs
 }  // namespace mspa
 
@@ -191,7 +181,7 @@ using namespace mspa;
 extern "C" int mspa_knn_segments_tables_host(const int64_t *offsets_host, int64_t S, int32_t k, int64_t *cell_base_out) {
     if (!cell_base_out) return fail(MSPA_EINVAL, "mspa_knn_segments_tables_host: null pointer");
     if (k < 1 || k > knn::kMaxK) return fail(MSPA_EINVAL, "mspa_knn_segments_tables_host: k outside [1, 64]");
-    if (segs::checked_batch("mspa_knn_segments_tables_host", offsets_host, S) < 0) return MSPA_EINVAL;
+    if (segs::checked_rows("mspa_knn_segments_tables_host", offsets_host, S) < 0) return MSPA_EINVAL;
     segs::cell_tables(offsets_host, S, k, cell_base_out);
     return MSPA_OK;
 }
@@ -199,7 +189,7 @@ extern "C" int mspa_knn_segments_tables_host(const int64_t *offsets_host, int64_
 extern "C" int mspa_knn_segments_grids_host(const double *lo, const double *hi, const int64_t *offsets_host, int64_t S, int32_t k,
                                             void *grids_out) {
     if (k < 1 || k > knn::kMaxK) return fail(MSPA_EINVAL, "mspa_knn_segments_grids_host: k outside [1, 64]");
-    if (segs::checked_batch("mspa_knn_segments_grids_host", offsets_host, S) < 0) return MSPA_EINVAL;
+    if (segs::checked_rows("mspa_knn_segments_grids_host", offsets_host, S) < 0) return MSPA_EINVAL;
     if (S == 0) return MSPA_OK;
     if (!lo || !hi || !grids_out) return fail(MSPA_EINVAL, "mspa_knn_segments_grids_host: null pointer");
     if (!segs::make_grids(lo, hi, offsets_host, S, k, (knn::Grid *)grids_out))
@@ -214,13 +204,13 @@ extern "C" int64_t mspa_knn_segments_workspace_bytes(const int64_t *offsets_host
     int64_t cells = 0;
     for (int64_t s = 0; s < S; ++s)
         if (offsets_host[s + 1] > offsets_host[s]) cells += knn::max_cells(offsets_host[s + 1] - offsets_host[s], k);
-    return segs::align16(N * 24) + segs::align16(N * 8) + segs::align16((cells + S) * 4);
+    return align16(N * 24) + align16(N * 8) + align16((cells + S) * 4);
 }
 
 extern "C" int mspa_knn_segments_cells_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, const void *grids_host,
                                               const int64_t *offsets_dev, const void *grids_dev, const int64_t *cell_base_dev,
                                               int64_t *keys_dev, void *stream) {
-    const int64_t N = segs::checked_batch("mspa_knn_segments_cells_device", offsets_host, S);
+    const int64_t N = segs::checked_rows("mspa_knn_segments_cells_device", offsets_host, S);
     if (N < 0) return MSPA_EINVAL;
     if (N == 0) return MSPA_OK;
     if (!xyz_dev || !grids_host || !offsets_dev || !grids_dev || !cell_base_dev || !keys_dev)
@@ -237,7 +227,7 @@ extern "C" int mspa_knn_segments_mean_distance_device(const double *xyz_dev, con
                                                       const int64_t *cell_base_dev, const int64_t *order_dev, double *mean_dev,
                                                       int32_t *evals_dev, void *workspace, int64_t workspace_bytes, void *stream) {
     if (k < 1 || k > knn::kMaxK) return fail(MSPA_EINVAL, "mspa_knn_segments_mean_distance_device: k outside [1, 64]");
-    const int64_t N = segs::checked_batch("mspa_knn_segments_mean_distance_device", offsets_host, S);
+    const int64_t N = segs::checked_rows("mspa_knn_segments_mean_distance_device", offsets_host, S);
     if (N < 0) return MSPA_EINVAL;
     if (N == 0) return MSPA_OK;
     if (!xyz_dev || !grids_host || !offsets_dev || !grids_dev || !cell_base_dev || !order_dev || !mean_dev || !workspace)
@@ -253,8 +243,8 @@ extern "C" int mspa_knn_segments_mean_distance_device(const double *xyz_dev, con
     hipStream_t st = (hipStream_t)stream;
     const knn::Grid *grids = (const knn::Grid *)grids_dev;
     double *pts = (double *)workspace;
-    int64_t *sorted_keys = (int64_t *)((uint8_t *)workspace + segs::align16(N * 24));
-    int32_t *starts = (int32_t *)((uint8_t *)sorted_keys + segs::align16(N * 8));
+    int64_t *sorted_keys = (int64_t *)((uint8_t *)workspace + align16(N * 24));
+    int32_t *starts = (int32_t *)((uint8_t *)sorted_keys + align16(N * 8));
     hipLaunchKernelGGL(segs::seg_gather_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, xyz_dev, offsets_dev, S, grids, cell_base_dev,
                        order_dev, pts, sorted_keys);
     hipLaunchKernelGGL(segs::seg_starts_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const int64_t *)sorted_keys, offsets_dev,
@@ -268,7 +258,7 @@ extern "C" int mspa_outlier_segments_device(const double *avg_dev, const double 
                                             double std_ratio, const int64_t *offsets_dev, uint8_t *keep_dev, int64_t *kept_dev,
                                             double *mean_dev, double *sd_dev, double *thr_dev, double *lo_dev, double *hi_dev, void *stream) {
     if (!(fabs(std_ratio) < INFINITY)) return fail(MSPA_EINVAL, "mspa_outlier_segments_device: std_ratio must be finite");
-    const int64_t N = segs::checked_batch("mspa_outlier_segments_device", offsets_host, S);
+    const int64_t N = segs::checked_rows("mspa_outlier_segments_device", offsets_host, S);
     if (N < 0) return MSPA_EINVAL;
     if (S == 0) return MSPA_OK;
     if (!offsets_dev || !kept_dev || !mean_dev || !sd_dev || !thr_dev || !lo_dev || !hi_dev || (N > 0 && (!avg_dev || !xyz_dev || !keep_dev)))
@@ -281,7 +271,7 @@ extern "C" int mspa_outlier_segments_device(const double *avg_dev, const double 
 extern "C" int mspa_knn_segments_mean_distance_host(const double *xyz_host, const int64_t *offsets_host, int64_t S, int32_t k,
                                                     double *mean_host, int32_t *evals_host) {
     if (k < 1 || k > knn::kMaxK) return fail(MSPA_EINVAL, "mspa_knn_segments_mean_distance_host: k outside [1, 64]");
-    const int64_t N = segs::checked_batch("mspa_knn_segments_mean_distance_host", offsets_host, S);
+    const int64_t N = segs::checked_rows("mspa_knn_segments_mean_distance_host", offsets_host, S);
     if (N < 0) return MSPA_EINVAL;
     if (N == 0) return MSPA_OK;
     if (!xyz_host || !mean_host) return fail(MSPA_EINVAL, "mspa_knn_segments_mean_distance_host: null pointer");
@@ -296,7 +286,7 @@ extern "C" int mspa_outlier_segments_host(const double *avg_host, const double *
                                           double std_ratio, uint8_t *keep_host, int64_t *kept_host, double *mean_host, double *sd_host,
                                           double *thr_host, double *lo_host, double *hi_host) {
     if (!(fabs(std_ratio) < INFINITY)) return fail(MSPA_EINVAL, "mspa_outlier_segments_host: std_ratio must be finite");
-    const int64_t N = segs::checked_batch("mspa_outlier_segments_host", offsets_host, S);
+    const int64_t N = segs::checked_rows("mspa_outlier_segments_host", offsets_host, S);
     if (N < 0) return MSPA_EINVAL;
     if (S == 0) return MSPA_OK;
     if (!kept_host || !mean_host || !sd_host || !thr_host || !lo_host || !hi_host || (N > 0 && (!avg_host || !xyz_host || !keep_host)))

@@ -62,6 +62,14 @@ MSPA_HD int64_t segment_of(const int64_t *__restrict__ offsets, int64_t S, int64
     return lo;
 }
 
+// The extents pass cuts every segment into tiles of kExtentTile rows: tile_base [S + 1] is the exclusive prefix of the tiles.
+constexpr int64_t kExtentTile = 4096;                            // rows one workgroup of the extents pass takes
+MSPA_HD int64_t tiles_of(int64_t n) { return (n + kExtentTile - 1) / kExtentTile; }
+inline void tile_table(const int64_t *offsets, int64_t S, int64_t *tile_base) {
+    tile_base[0] = 0;
+    for (int64_t s = 0; s < S; ++s) tile_base[s + 1] = tile_base[s] + tiles_of(offsets[s + 1] - offsets[s]);
+}
+
 // cell_base [S + 1]: the exclusive prefix of max_cells(n_s, k) over the non-empty segments.
 inline void cell_tables(const int64_t *offsets, int64_t S, int32_t k, int64_t *cell_base) {
     cell_base[0] = 0;

@@ -1,7 +1,8 @@
 // DBSCAN of a RAGGED BATCH of clouds ON the MI355X: a label per row of every segment, the per-segment cluster counts and, where
 // asked, the rows of each segment's largest cluster, in a number of launches that does not depend on the number of segments and
 // with labels that are the same values on every run.  The rule and its two floating-point arguments are csrc/dbscan_core.h; this
-// file holds the kernels, the host twin's entry point and the C ABI.
+// file holds the op's own kernels, the host twin's entry point and the C ABI; the compaction and the extents pass are the batch's
+// shared passes (csrc/segments_device.h).
 //
 // The cells are section 0.24's: the caller runs mspa_voxel_segments_keys_device at voxel size mspa_dbscan_cell_side(eps) (the
 // segments' extents, the 63-bit keys, the flag word) and sorts the keys stably by (segment, key), exactly as for the down-sample.
@@ -15,8 +16,8 @@
 //        by compare-and-swap, the larger root under the smaller; agent-scope atomic loads; capped loops, no lane waits).
 //     4. db_roots_kernel      one thread per row, a launch of its own after the linking: root[row], the lowest core row of its
 //        component (-1 for a row that is not core).
-//     5. db_rep_count_kernel, db_tile_scan_kernel, db_rep_place_kernel   the representatives (root[row] == row) in input row order,
-//        compacted with the down-sample's pattern: per tile a count from wave ballots, one workgroup's scan, positions from ballots.
+//     5. flag_count_kernel<RepFlag>, tile_scan_kernel, flag_place_kernel<RepFlag>   the representatives (root[row] == row) in input
+//        row order (compact(): per tile a count from wave ballots, one workgroup's scan, positions from ballots).
 //        The rank of a representative in that list, less the rank of its segment's first, is the cluster's number.
 //     6. db_segment_clusters_kernel   one thread per segment: its clusters, by two binary searches in the list.
 //     7. db_labels_kernel     one thread per sorted slot: a core row's root, or for any other row the lowest root among the near
@@ -24,20 +25,19 @@
 //        integer add: no order changes a count).
 //     8. db_largest_kernel    one wave per segment: the cluster with the most rows, a tie to the lowest number -> best, kept.
 //     9. db_keep_kernel       one thread per row: keep = the row's label is its segment's best.
-//    10. db_kept_extent_tiles_kernel, db_kept_extent_fold_kernel   the extents of the kept rows per segment, in the form of the
-//        down-sample's extents pass: one workgroup per tile of 4 096 rows of ONE segment, then one wave per segment over its tiles
-//        (min and max are order-independent) -> kept_lo, kept_hi [S, 3], +inf / -inf where nothing is kept.
+//    10. extent_tiles_kernel<2, KeptFlag>, extent_fold_kernel<2>   the extents of the kept rows per segment by the down-sample's
+//        extents pass: one workgroup per tile of 4 096 rows of ONE segment, then one wave per segment over its tiles (min and max
+//        are order-independent) -> kept_lo, kept_hi [S, 3], +inf / -inf where nothing is kept.
 // Steps 8 to 10 run only where the caller passes keep_dev.
 #include "mspa_common.h"
 #include "dbscan_core.h"
+#include "segments_device.h"
 
 namespace mspa {
 namespace dbscan {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kRounds = 8;
-constexpr int64_t kFlagTile = (int64_t)kBlock * kRounds;         // rows one workgroup of the compaction takes
+using segs::kBlock;
+using segs::kFlagTile;
 
 // parent through agent-scope atomics: a load sees what any workgroup of the launch has stored.
 struct DeviceMemory {
@@ -103,75 +103,6 @@ __global__ void __launch_bounds__(kBlock) db_roots_kernel(int32_t *parent, const
     }
     root[r] = top;
     if (capped) atomicOr(flag_word, kCapReached);
-}
-
-__global__ void __launch_bounds__(kBlock) db_rep_count_kernel(const int32_t *__restrict__ root, int64_t n, int32_t *__restrict__ tile_counts) {
-    __shared__ int32_t wcnt[kWaves];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int32_t count = 0;
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * kFlagTile + (int64_t)r * kBlock + tid;
-        count += __popcll(__ballot(i < n && root[i] == i));
-    }
-    if (lane == 0) wcnt[w] = count;
-    __syncthreads();
-    if (tid == 0) {
-        int32_t all = 0;
-#pragma unroll
-        for (int e = 0; e < kWaves; ++e) all += wcnt[e];
-        tile_counts[blockIdx.x] = all;
-    }
-}
-
-// One workgroup: tile_counts [T] -> their exclusive prefix, in place; the total to *total.
-__global__ void __launch_bounds__(kBlock) db_tile_scan_kernel(int32_t *__restrict__ tile_counts, int64_t T, int64_t *__restrict__ total) {
-    __shared__ int64_t chunk_sum[kBlock];
-    const int tid = (int)threadIdx.x;
-    const int64_t per = (T + kBlock - 1) / kBlock;
-    const int64_t a = tid * per < T ? tid * per : T, b = a + per < T ? a + per : T;
-    int64_t sum = 0;
-    for (int64_t t = a; t < b; ++t) sum += tile_counts[t];
-    chunk_sum[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int e = 0; e < kBlock; ++e) {
-            const int64_t c = chunk_sum[e];
-            chunk_sum[e] = run;
-            run += c;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    int64_t run = chunk_sum[tid];
-    for (int64_t t = a; t < b; ++t) {
-        const int32_t c = tile_counts[t];
-        tile_counts[t] = (int32_t)run;
-        run += c;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) db_rep_place_kernel(const int32_t *__restrict__ root, int64_t n, const int32_t *__restrict__ tile_base,
-                                                              int64_t *__restrict__ reps) {
-    __shared__ int32_t wcnt[kWaves];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int64_t run = tile_base[blockIdx.x];
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * kFlagTile + (int64_t)r * kBlock + tid;
-        const bool set = i < n && root[i] == i;
-        const uint64_t m = __ballot(set);
-        if (lane == 0) wcnt[w] = __popcll(m);
-        __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int e = 0; e < kWaves; ++e) {
-            before += e < w ? wcnt[e] : 0;
-            all += wcnt[e];
-        }
-        if (set) reps[run + before + __popcll(m & (((uint64_t)1 << lane) - 1))] = i;
-        run += all;
-        __syncthreads();
-    }
 }
 
 __global__ void __launch_bounds__(kBlock) db_segment_clusters_kernel(const int64_t *__restrict__ reps, const int64_t *__restrict__ total,
@@ -241,73 +172,15 @@ __global__ void __launch_bounds__(kBlock) db_keep_kernel(const int32_t *__restri
     keep[r] = label >= 0 && label == best[segment_of(offsets, S, r)] ? 1 : 0;
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double o = __shfl_xor(v, s, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
+struct RepFlag {                                                 // row i is its component's representative
+    const int32_t *root;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return root[i] == i; }
+};
 
-// part [T, 6]: per tile the minimum of the kept rows' x, y, z and the minimum of their negations (so one fold serves both ends).
-__global__ void __launch_bounds__(kBlock) db_kept_extent_tiles_kernel(const double *__restrict__ rows, int64_t C, const int64_t *__restrict__ offsets,
-                                                                      const int64_t *__restrict__ tile_base, int64_t S,
-                                                                      const uint8_t *__restrict__ keep, double *__restrict__ part) {
-    __shared__ double mins[kWaves][6];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t t = blockIdx.x;
-    const int64_t s = segment_of(tile_base, S, t);
-    const int64_t a = offsets[s] + (t - tile_base[s]) * voxel::kExtentTile;
-    const int64_t end = offsets[s + 1], b = a + voxel::kExtentTile < end ? a + voxel::kExtentTile : end;
-    double m[6] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
-    for (int64_t i = a + tid; i < b; i += kBlock) {
-        if (!keep[i]) continue;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-            const double x = rows[i * C + ax];
-            m[ax] = x < m[ax] ? x : m[ax];
-            m[3 + ax] = -x < m[3 + ax] ? -x : m[3 + ax];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const double v = wave_min(m[e]);
-        if (lane == 0) mins[w][e] = v;
-    }
-    __syncthreads();
-    if (tid < 6) {
-        double v = mins[0][tid];
-#pragma unroll
-        for (int e = 1; e < kWaves; ++e) v = mins[e][tid] < v ? mins[e][tid] : v;
-        part[t * 6 + tid] = v;
-    }
-}
-
-__global__ void __launch_bounds__(kWave) db_kept_extent_fold_kernel(const double *__restrict__ part, const int64_t *__restrict__ tile_base,
-                                                                    double *__restrict__ lo, double *__restrict__ hi) {
-    const int lane = (int)threadIdx.x;
-    const int64_t s = blockIdx.x;
-    const int64_t a = tile_base[s], b = tile_base[s + 1];
-    double m[6] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY};
-    for (int64_t t = a + lane; t < b; t += kWave) {
-#pragma unroll
-        for (int e = 0; e < 6; ++e) m[e] = part[t * 6 + e] < m[e] ? part[t * 6 + e] : m[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-        const double v = wave_min(m[e]);
-        if (lane == e) (e < 3 ? lo : hi)[s * 3 + e % 3] = e < 3 ? v : -v;
-    }
-}
-
-int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
-
-int64_t extent_tiles(const int64_t *offsets, int64_t S) {
-    int64_t T = 0;
-    for (int64_t s = 0; s < S; ++s) T += voxel::tiles_of(offsets[s + 1] - offsets[s]);
-    return T;
-}
+struct KeptFlag {                                                // row i is kept
+    const uint8_t *keep;
+    __device__ __forceinline__ bool operator()(int64_t i) const { return keep[i] != 0; }
+};
 
 // The workspace of a batch of N rows in S segments, cut into its parts.
 struct Workspace {
@@ -332,11 +205,8 @@ struct Workspace {
 // N of a batch the entry points take with their parameters, or -1 with the error text set.
 int64_t checked_batch(const char *who, const int64_t *offsets_host, int64_t S, int64_t C, double eps, int64_t min_points) {
     const std::string name(who);
-    const int64_t N = batch_rows(offsets_host, S);
-    if (N < 0) {
-        fail(MSPA_EINVAL, name + ": offsets must be [S + 1] with offsets[0] = 0, ascending, at most 2^30 rows and 2^24 segments");
-        return -1;
-    }
+    const int64_t N = segs::checked_rows(who, offsets_host, S);
+    if (N < 0) return -1;
     if (C < 3 || C > MSPA_VOXEL_MAX_COLUMNS) {
         fail(MSPA_EINVAL, name + ": C must be between 3 and 65536 columns");
         return -1;
@@ -352,8 +222,6 @@ int64_t checked_batch(const char *who, const int64_t *offsets_host, int64_t S, i
     return N;
 }
 
-bool misaligned(const void *p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
-
 }  // namespace dbscan
 }  // namespace mspa
 
@@ -364,7 +232,7 @@ extern "C" double mspa_dbscan_cell_side(double eps) { return dbscan::eps_ok(eps)
 extern "C" int64_t mspa_dbscan_segments_workspace_bytes(const int64_t *offsets_host, int64_t S) {
     const int64_t N = dbscan::batch_rows(offsets_host, S);
     if (N < 0) return -1;
-    return dbscan::Workspace(N, S, dbscan::extent_tiles(offsets_host, S)).bytes;
+    return dbscan::Workspace(N, S, segs::extent_tiles(offsets_host, S)).bytes;
 }
 
 extern "C" int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, double eps,
@@ -377,13 +245,13 @@ extern "C" int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, co
     if (!seg_dev || (N > 0 && (!rows_dev || !offsets_dev || !keys_dev || !order_dev || !labels_dev)) ||
         (keep_dev && S > 0 && (!kept_lo_dev || !kept_hi_dev || (N > 0 && !tile_base_dev))))
         return fail(MSPA_EINVAL, std::string(who) + ": null pointer");
-    const int64_t T = dbscan::extent_tiles(offsets_host, S);
+    const int64_t T = segs::extent_tiles(offsets_host, S);
     if (N > 0 && (!workspace || workspace_bytes < dbscan::Workspace(N, S, T).bytes))
         return fail(MSPA_EINVAL, std::string(who) + ": workspace null or smaller than mspa_dbscan_segments_workspace_bytes()");
     if (N > 0 && ((uintptr_t)workspace & 15u)) return fail(MSPA_EINVAL, std::string(who) + ": workspace must be 16-byte aligned");
-    if (dbscan::misaligned(rows_dev, 8) || dbscan::misaligned(offsets_dev, 8) || dbscan::misaligned(keys_dev, 8) ||
-        dbscan::misaligned(order_dev, 8) || dbscan::misaligned(labels_dev, 4) || dbscan::misaligned(seg_dev, 4) ||
-        dbscan::misaligned(tile_base_dev, 8) || dbscan::misaligned(kept_lo_dev, 8) || dbscan::misaligned(kept_hi_dev, 8))
+    if (segs::misaligned(rows_dev, 8) || segs::misaligned(offsets_dev, 8) || segs::misaligned(keys_dev, 8) ||
+        segs::misaligned(order_dev, 8) || segs::misaligned(labels_dev, 4) || segs::misaligned(seg_dev, 4) ||
+        segs::misaligned(tile_base_dev, 8) || segs::misaligned(kept_lo_dev, 8) || segs::misaligned(kept_hi_dev, 8))
         return fail(MSPA_EINVAL, std::string(who) + ": a buffer is not aligned to its element");
     hipStream_t st = (hipStream_t)stream;
     if (S > 0 && check_hip(hipMemsetAsync(seg_dev, 0, (size_t)S * 8, st), who) != MSPA_OK) return MSPA_EHIP;   // kept and clusters; not the flag word
@@ -399,7 +267,6 @@ extern "C" int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, co
     const double eps_sq = eps * eps;
     const dim3 per_row((unsigned)((N + dbscan::kBlock - 1) / dbscan::kBlock)), per_segment((unsigned)((S + dbscan::kBlock - 1) / dbscan::kBlock));
     const dim3 block(dbscan::kBlock);
-    const int64_t flag_tiles = (N + dbscan::kFlagTile - 1) / dbscan::kFlagTile;
     // sizes from 0; parent and labels from -1, so that an order_dev that is no permutation leaves "not core" and "noise", not stale bytes
     if (check_hip(hipMemsetAsync(sizes, 0, (size_t)N * 4, st), who) != MSPA_OK ||
         check_hip(hipMemsetAsync(parent, 0xff, (size_t)N * 4, st), who) != MSPA_OK ||
@@ -411,9 +278,7 @@ extern "C" int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, co
     hipLaunchKernelGGL(dbscan::db_link_kernel, per_row, block, 0, st, (const double *)pts, (const int64_t *)keys, (const int32_t *)row,
                        (const uint8_t *)core, offsets_dev, S, N, eps_sq, parent, flag_word);
     hipLaunchKernelGGL(dbscan::db_roots_kernel, per_row, block, 0, st, parent, offsets_dev, S, N, root, flag_word);
-    hipLaunchKernelGGL(dbscan::db_rep_count_kernel, dim3((unsigned)flag_tiles), block, 0, st, (const int32_t *)root, N, tile_counts);
-    hipLaunchKernelGGL(dbscan::db_tile_scan_kernel, dim3(1), block, 0, st, tile_counts, flag_tiles, totals);
-    hipLaunchKernelGGL(dbscan::db_rep_place_kernel, dim3((unsigned)flag_tiles), block, 0, st, (const int32_t *)root, N, (const int32_t *)tile_counts, reps);
+    segs::compact(dbscan::RepFlag{root}, N, tile_counts, totals, reps, false, st);
     hipLaunchKernelGGL(dbscan::db_segment_clusters_kernel, per_segment, block, 0, st, (const int64_t *)reps, (const int64_t *)totals, offsets_dev, S,
                        seg_clusters);
     hipLaunchKernelGGL(dbscan::db_labels_kernel, per_row, block, 0, st, (const double *)pts, (const int64_t *)keys, (const int32_t *)row,
@@ -425,9 +290,9 @@ extern "C" int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, co
         hipLaunchKernelGGL(dbscan::db_keep_kernel, per_row, block, 0, st, (const int32_t *)labels_dev, (const int32_t *)best, offsets_dev, S, N,
                            keep_dev);
         double *part = (double *)(base + ws.part);
-        hipLaunchKernelGGL(dbscan::db_kept_extent_tiles_kernel, dim3((unsigned)T), block, 0, st, rows_dev, C, offsets_dev, tile_base_dev, S,
-                           (const uint8_t *)keep_dev, part);
-        hipLaunchKernelGGL(dbscan::db_kept_extent_fold_kernel, dim3((unsigned)S), dim3(kWave), 0, st, (const double *)part, tile_base_dev, kept_lo_dev,
+        hipLaunchKernelGGL((segs::extent_tiles_kernel<2, dbscan::KeptFlag>), dim3((unsigned)T), block, 0, st, rows_dev, C, offsets_dev,
+                           tile_base_dev, S, part, dbscan::KeptFlag{keep_dev});
+        hipLaunchKernelGGL(segs::extent_fold_kernel<2>, dim3((unsigned)S), dim3(kWave), 0, st, (const double *)part, tile_base_dev, kept_lo_dev,
                            kept_hi_dev);
     }
     return check_hip(hipGetLastError(), who);

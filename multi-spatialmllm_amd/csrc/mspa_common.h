@@ -25,6 +25,19 @@ int png_pack_idat_files(const char *who, int bit_depth, const char *const *paths
                         void *dst_host, int64_t dst_capacity, int64_t *offsets_host, int64_t *bytes_host, int32_t *status_host,
                         int64_t *capacity_needed, int32_t n_threads);
 
+// A byte count rounded up to the 16-byte boundary every part of a workspace starts on.
+inline int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
+
+// The minimum of v over the 64 lanes of a wave, in every lane.
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double o = __shfl_xor(v, s, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // Lanes of one wave exchange data through LDS (every lane stores its slot, then loads another lane's).  The hardware executes a
 // wave's LDS operations in order, so no instruction is needed -- but the compiler must not move the loads above the stores
 // either, and under the HIP memory model nothing but a fence says so: a wavefront-scope release / acquire pair plus a wave

@@ -102,15 +102,6 @@ __global__ __launch_bounds__(256) void objects_init_kernel(double *__restrict__ 
     if (k < n_scenes) zero_count[k] = 0;
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double o = __shfl_xor(v, d, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {

@@ -37,26 +37,21 @@ constexpr int32_t kAxisBits = 21;
 constexpr int64_t kAxisLimit = (int64_t)1 << kAxisBits;           // every per-axis index is below it
 constexpr int32_t kSequential = 64;                              // the longest run summed sequentially
 constexpr int32_t kLanes = 64;                                   // lanes of the strided order
-constexpr int64_t kExtentTile = 4096;                            // rows one workgroup of the extents pass takes
 enum : int32_t { kNonFinite = 1, kOutOfRange = 2 };              // bits of the flag word
 
 // ---- the batch ----------------------------------------------------------------------------------------------------------------
 
 // The batch is cloud_segments_core.h's, with its checks and its clamps: batch_rows (N, or -1 for offsets that are no batch),
 // segment_of (the segment of a row; empty segments in front of it are passed over -- used for the extents tiles as well, with
-// tile_base as the table), row_in_segment (a caller's order entry clamped into [0, N) and then into the slot's own segment) and
-// first_at_or_above.
+// tile_base as the table), row_in_segment (a caller's order entry clamped into [0, N) and then into the slot's own segment),
+// first_at_or_above, and the extents pass's tiles (kExtentTile, tiles_of, tile_table).
 using segs::batch_rows;
 using segs::first_at_or_above;
+using segs::kExtentTile;
 using segs::row_in_segment;
 using segs::segment_of;
-
-// The extents pass cuts every segment into tiles of kExtentTile rows: tile_base [S + 1] is the exclusive prefix of the tiles.
-MSPA_HD int64_t tiles_of(int64_t n) { return (n + kExtentTile - 1) / kExtentTile; }
-inline void tile_table(const int64_t *offsets, int64_t S, int64_t *tile_base) {
-    tile_base[0] = 0;
-    for (int64_t s = 0; s < S; ++s) tile_base[s + 1] = tile_base[s] + tiles_of(offsets[s + 1] - offsets[s]);
-}
+using segs::tile_table;
+using segs::tiles_of;
 
 // ---- the grid -----------------------------------------------------------------------------------------------------------------
 

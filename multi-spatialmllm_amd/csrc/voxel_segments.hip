@@ -1,21 +1,21 @@
 // Voxel-grid down-sampling of a RAGGED BATCH of clouds ON the MI355X: one output row per occupied voxel of every segment, the mean
 // of each column over the voxel's rows, in a number of launches that does not depend on the number of segments and with results
 // that are the same bits on every run.  The rule -- grid origin, index, key, the order of the sums -- is csrc/voxel_grid_core.h;
-// this file holds the kernels, the host twin's entry point and the C ABI.
+// this file holds the op's own kernels, the host twin's entry point and the C ABI; the extents pass and the compaction are the
+// batch's shared passes (csrc/segments_device.h).
 //
 // Three entry points around two torch.sorts (plumbing: stably by key, then stably by segment) and one read-back:
 //   mspa_voxel_segments_keys_device
-//     1. vox_extent_tiles_kernel  one workgroup per tile of 4 096 rows of ONE segment (tile_base: the host's prefix of the segments'
-//        tiles): the per-axis minimum of the tile.  A segment of 1.5 M rows is 367 workgroups, not one.
-//     2. vox_extent_fold_kernel   one wave per segment: the minimum over its tiles -> lo [S, 3] (min is order-independent).
+//     1. extent_tiles_kernel<1, TakeAll>  one workgroup per tile of 4 096 rows of ONE segment (tile_base: the host's prefix of the
+//        segments' tiles): the per-axis minimum of the tile.  A segment of 1.5 M rows is 367 workgroups, not one.
+//     2. extent_fold_kernel<1>    one wave per segment: the minimum over its tiles -> lo [S, 3] (min is order-independent).
 //     3. vox_keys_kernel          one thread per row: its segment (binary search in the offsets), its 63-bit key, its segment id
 //        beside it; a non-finite or out-of-range row ORs its bit into the flag word (an integer OR does not depend on arrival order).
 //   mspa_voxel_segments_heads_device
 //     4. vox_heads_kernel         one thread per sorted slot: the slot opens a voxel when it is the first of its segment or its key
 //        differs from its predecessor's.  Order entries are clamped into [0, N) and into the slot's segment.
-//     5. flag_count_kernel, tile_scan_kernel, flag_place_kernel   the flagged slots' indices, compacted in ascending order: per tile of
-//        2 048 slots a count (wave ballots), one workgroup's exclusive scan over the tiles, then every flagged slot's position = tile
-//        base + rounds before + waves before + its rank below in the wave's ballot.  No atomic hands out a position.
+//     5. flag_count_kernel<HeadFlag>, tile_scan_kernel, flag_place_kernel<HeadFlag>   the heads' slots, compacted in ascending order
+//        (compact(): per tile of 2 048 slots a count, one workgroup's exclusive scan, positions from ballots; no atomics)
 //        -> run_start [M + 1] (run_start[M] = N), so run v has run_start[v + 1] - run_start[v] rows.
 //     6. vox_segment_counts_kernel  one thread per segment: its voxels, by two binary searches in run_start.
 //   mspa_voxel_segments_means_device  (after the read-back of the counts: M is the host's)
@@ -24,72 +24,16 @@
 //     9. vox_long_means_kernel    one wave per long run, waves striding over the list: 64 lane sums, folded by strides 32 .. 1.
 #include "mspa_common.h"
 #include "voxel_grid_core.h"
+#include "segments_device.h"
 
 namespace mspa {
 namespace voxel {
 
+using segs::kBlock;
+using segs::kFlagTile;
+using segs::kWaves;
+
 static_assert(kLanes == kWave, "the strided order has one lane per lane of a wave");
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kRounds = 8;
-constexpr int64_t kFlagTile = (int64_t)kBlock * kRounds;         // slots one workgroup of the compaction takes
-
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double o = __shfl_xor(v, s, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__global__ void __launch_bounds__(kBlock) vox_extent_tiles_kernel(const double *__restrict__ rows, int64_t C, const int64_t *__restrict__ offsets,
-                                                                  const int64_t *__restrict__ tile_base, int64_t S, double *__restrict__ part) {
-    __shared__ double mins[kWaves][3];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int64_t t = blockIdx.x;
-    const int64_t s = segment_of(tile_base, S, t);
-    const int64_t a = offsets[s] + (t - tile_base[s]) * kExtentTile;
-    const int64_t end = offsets[s + 1], b = a + kExtentTile < end ? a + kExtentTile : end;
-    double lo[3] = {INFINITY, INFINITY, INFINITY};
-    for (int64_t i = a + tid; i < b; i += kBlock) {
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-            const double x = rows[i * C + ax];
-            lo[ax] = x < lo[ax] ? x : lo[ax];
-        }
-    }
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const double m = wave_min(lo[ax]);
-        if (lane == 0) mins[w][ax] = m;
-    }
-    __syncthreads();
-    if (tid < 3) {
-        double m = mins[0][tid];
-#pragma unroll
-        for (int e = 1; e < kWaves; ++e) m = mins[e][tid] < m ? mins[e][tid] : m;
-        part[t * 3 + tid] = m;
-    }
-}
-
-__global__ void __launch_bounds__(kWave) vox_extent_fold_kernel(const double *__restrict__ part, const int64_t *__restrict__ tile_base,
-                                                                double *__restrict__ lo) {
-    const int lane = (int)threadIdx.x;
-    const int64_t s = blockIdx.x;
-    const int64_t a = tile_base[s], b = tile_base[s + 1];
-    double m[3] = {INFINITY, INFINITY, INFINITY};
-    for (int64_t t = a + lane; t < b; t += kWave) {
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) m[ax] = part[t * 3 + ax] < m[ax] ? part[t * 3 + ax] : m[ax];
-    }
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const double v = wave_min(m[ax]);
-        if (lane == ax) lo[s * 3 + ax] = v;
-    }
-}
 
 __global__ void __launch_bounds__(kBlock) vox_keys_kernel(const double *__restrict__ rows, int64_t C, const int64_t *__restrict__ offsets, int64_t S,
                                                           int64_t N, const double *__restrict__ lo, double voxel_size, int64_t *__restrict__ keys,
@@ -129,78 +73,6 @@ struct LongFlag {                                                // voxel v of t
     const int64_t *run_start, *total;
     __device__ __forceinline__ bool operator()(int64_t v) const { return v < *total && is_long(run_start[v + 1] - run_start[v]); }
 };
-
-template <typename Flag>
-__global__ void __launch_bounds__(kBlock) flag_count_kernel(Flag flag, int64_t n, int32_t *__restrict__ tile_counts) {
-    __shared__ int32_t wcnt[kWaves];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int32_t count = 0;
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * kFlagTile + (int64_t)r * kBlock + tid;
-        count += __popcll(__ballot(i < n && flag(i)));
-    }
-    if (lane == 0) wcnt[w] = count;
-    __syncthreads();
-    if (tid == 0) {
-        int32_t all = 0;
-#pragma unroll
-        for (int e = 0; e < kWaves; ++e) all += wcnt[e];
-        tile_counts[blockIdx.x] = all;
-    }
-}
-
-// One workgroup: tile_counts [T] -> their exclusive prefix, in place; the total to *total and, where list is given, list[total] = end.
-__global__ void __launch_bounds__(kBlock) tile_scan_kernel(int32_t *__restrict__ tile_counts, int64_t T, int64_t *__restrict__ total,
-                                                           int64_t *__restrict__ list, int64_t end) {
-    __shared__ int64_t chunk_sum[kBlock];
-    const int tid = (int)threadIdx.x;
-    const int64_t per = (T + kBlock - 1) / kBlock;
-    const int64_t a = tid * per < T ? tid * per : T, b = a + per < T ? a + per : T;
-    int64_t sum = 0;
-    for (int64_t t = a; t < b; ++t) sum += tile_counts[t];
-    chunk_sum[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int e = 0; e < kBlock; ++e) {
-            const int64_t c = chunk_sum[e];
-            chunk_sum[e] = run;
-            run += c;
-        }
-        *total = run;
-        if (list) list[run] = end;
-    }
-    __syncthreads();
-    int64_t run = chunk_sum[tid];
-    for (int64_t t = a; t < b; ++t) {
-        const int32_t c = tile_counts[t];
-        tile_counts[t] = (int32_t)run;
-        run += c;
-    }
-}
-
-template <typename Flag>
-__global__ void __launch_bounds__(kBlock) flag_place_kernel(Flag flag, int64_t n, const int32_t *__restrict__ tile_base, int64_t *__restrict__ list) {
-    __shared__ int32_t wcnt[kWaves];
-    const int tid = (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
-    int64_t run = tile_base[blockIdx.x];
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * kFlagTile + (int64_t)r * kBlock + tid;
-        const bool set = i < n && flag(i);
-        const uint64_t m = __ballot(set);
-        if (lane == 0) wcnt[w] = __popcll(m);
-        __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int e = 0; e < kWaves; ++e) {
-            before += e < w ? wcnt[e] : 0;
-            all += wcnt[e];
-        }
-        if (set) list[run + before + __popcll(m & (((uint64_t)1 << lane) - 1))] = i;
-        run += all;
-        __syncthreads();
-    }
-}
 
 __global__ void __launch_bounds__(kBlock) vox_segment_counts_kernel(const int64_t *__restrict__ run_start, const int64_t *__restrict__ total,
                                                                     const int64_t *__restrict__ offsets, int64_t S, int32_t *__restrict__ seg_voxels) {
@@ -257,8 +129,6 @@ __global__ void __launch_bounds__(kBlock) vox_long_means_kernel(const double *__
     }
 }
 
-int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
-
 // The workspace of a batch of N rows in S segments whose extents pass has T tiles, cut into its parts.
 struct Workspace {
     int64_t lo, part, head, run_start, tile_counts, totals, long_list, bytes;
@@ -274,27 +144,18 @@ struct Workspace {
     }
 };
 
-int64_t extent_tiles(const int64_t *offsets, int64_t S) {
-    int64_t T = 0;
-    for (int64_t s = 0; s < S; ++s) T += tiles_of(offsets[s + 1] - offsets[s]);
-    return T;
-}
-
 // N of a batch the entry points take with their column count and workspace, or -1 with the error text set.
 int64_t checked_batch(const char *who, const int64_t *offsets_host, int64_t S, int64_t C, bool with_workspace, const void *workspace,
                       int64_t workspace_bytes) {
     const std::string name(who);
-    const int64_t N = batch_rows(offsets_host, S);
-    if (N < 0) {
-        fail(MSPA_EINVAL, name + ": offsets must be [S + 1] with offsets[0] = 0, ascending, at most 2^30 rows and 2^24 segments");
-        return -1;
-    }
+    const int64_t N = segs::checked_rows(who, offsets_host, S);
+    if (N < 0) return -1;
     if (C < 3 || C > MSPA_VOXEL_MAX_COLUMNS) {
         fail(MSPA_EINVAL, name + ": C must be between 3 and 65536 columns");
         return -1;
     }
     if (with_workspace && N > 0) {
-        if (!workspace || workspace_bytes < Workspace(N, S, extent_tiles(offsets_host, S)).bytes) {
+        if (!workspace || workspace_bytes < Workspace(N, S, segs::extent_tiles(offsets_host, S)).bytes) {
             fail(MSPA_EINVAL, name + ": workspace null or smaller than mspa_voxel_segments_workspace_bytes()");
             return -1;
         }
@@ -304,16 +165,6 @@ int64_t checked_batch(const char *who, const int64_t *offsets_host, int64_t S, i
         }
     }
     return N;
-}
-
-bool misaligned(const void *p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
-
-template <typename Flag>
-void compact(Flag flag, int64_t n, int32_t *tile_counts, int64_t *total, int64_t *list, bool with_end, hipStream_t st) {
-    const int64_t T = (n + kFlagTile - 1) / kFlagTile;
-    hipLaunchKernelGGL(flag_count_kernel<Flag>, dim3((unsigned)T), dim3(kBlock), 0, st, flag, n, tile_counts);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, tile_counts, T, total, with_end ? list : (int64_t *)nullptr, n);
-    hipLaunchKernelGGL(flag_place_kernel<Flag>, dim3((unsigned)T), dim3(kBlock), 0, st, flag, n, (const int32_t *)tile_counts, list);
 }
 
 }  // namespace voxel
@@ -331,7 +182,7 @@ extern "C" int mspa_voxel_segments_tables_host(const int64_t *offsets_host, int6
 extern "C" int64_t mspa_voxel_segments_workspace_bytes(const int64_t *offsets_host, int64_t S) {
     const int64_t N = voxel::batch_rows(offsets_host, S);
     if (N < 0) return -1;
-    return voxel::Workspace(N, S, voxel::extent_tiles(offsets_host, S)).bytes;
+    return voxel::Workspace(N, S, segs::extent_tiles(offsets_host, S)).bytes;
 }
 
 extern "C" int mspa_voxel_segments_keys_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, double voxel_size,
@@ -344,17 +195,19 @@ extern "C" int mspa_voxel_segments_keys_device(const double *rows_dev, int64_t C
     if (N < 0) return MSPA_EINVAL;
     if (!seg_voxels_dev || (N > 0 && (!rows_dev || !offsets_dev || !tile_base_dev || !keys_dev || !segment_dev)))
         return fail(MSPA_EINVAL, std::string(who) + ": null pointer");
-    if (voxel::misaligned(rows_dev, 8) || voxel::misaligned(offsets_dev, 8) || voxel::misaligned(tile_base_dev, 8) ||
-        voxel::misaligned(keys_dev, 8) || voxel::misaligned(segment_dev, 4) || voxel::misaligned(seg_voxels_dev, 4))
+    if (segs::misaligned(rows_dev, 8) || segs::misaligned(offsets_dev, 8) || segs::misaligned(tile_base_dev, 8) ||
+        segs::misaligned(keys_dev, 8) || segs::misaligned(segment_dev, 4) || segs::misaligned(seg_voxels_dev, 4))
         return fail(MSPA_EINVAL, std::string(who) + ": a buffer is not aligned to its element");
     hipStream_t st = (hipStream_t)stream;
     if (check_hip(hipMemsetAsync(seg_voxels_dev, 0, (size_t)(S + 1) * 4, st), who) != MSPA_OK) return MSPA_EHIP;
     if (N == 0) return MSPA_OK;
-    const int64_t T = voxel::extent_tiles(offsets_host, S);
+    const int64_t T = segs::extent_tiles(offsets_host, S);
     const voxel::Workspace ws(N, S, T);
     double *lo = (double *)((uint8_t *)workspace + ws.lo), *part = (double *)((uint8_t *)workspace + ws.part);
-    hipLaunchKernelGGL(voxel::vox_extent_tiles_kernel, dim3((unsigned)T), dim3(voxel::kBlock), 0, st, rows_dev, C, offsets_dev, tile_base_dev, S, part);
-    hipLaunchKernelGGL(voxel::vox_extent_fold_kernel, dim3((unsigned)S), dim3(kWave), 0, st, (const double *)part, tile_base_dev, lo);
+    hipLaunchKernelGGL((segs::extent_tiles_kernel<1, segs::TakeAll>), dim3((unsigned)T), dim3(segs::kBlock), 0, st, rows_dev, C, offsets_dev,
+                       tile_base_dev, S, part, segs::TakeAll{});
+    hipLaunchKernelGGL(segs::extent_fold_kernel<1>, dim3((unsigned)S), dim3(kWave), 0, st, (const double *)part, tile_base_dev, lo,
+                       (double *)nullptr);
     hipLaunchKernelGGL(voxel::vox_keys_kernel, dim3((unsigned)((N + voxel::kBlock - 1) / voxel::kBlock)), dim3(voxel::kBlock), 0, st, rows_dev, C,
                        offsets_dev, S, N, (const double *)lo, voxel_size, keys_dev, segment_dev, seg_voxels_dev + S);
     return check_hip(hipGetLastError(), who);
@@ -368,17 +221,17 @@ extern "C" int mspa_voxel_segments_heads_device(const int64_t *offsets_host, int
     if (N < 0) return MSPA_EINVAL;
     if (N == 0) return MSPA_OK;
     if (!offsets_dev || !keys_dev || !order_dev || !seg_voxels_dev) return fail(MSPA_EINVAL, std::string(who) + ": null pointer");
-    if (voxel::misaligned(offsets_dev, 8) || voxel::misaligned(keys_dev, 8) || voxel::misaligned(order_dev, 8) ||
-        voxel::misaligned(seg_voxels_dev, 4))
+    if (segs::misaligned(offsets_dev, 8) || segs::misaligned(keys_dev, 8) || segs::misaligned(order_dev, 8) ||
+        segs::misaligned(seg_voxels_dev, 4))
         return fail(MSPA_EINVAL, std::string(who) + ": a buffer is not aligned to its element");
     hipStream_t st = (hipStream_t)stream;
-    const voxel::Workspace ws(N, S, voxel::extent_tiles(offsets_host, S));
+    const voxel::Workspace ws(N, S, segs::extent_tiles(offsets_host, S));
     uint8_t *base = (uint8_t *)workspace;
     uint8_t *head = base + ws.head;
     int64_t *run_start = (int64_t *)(base + ws.run_start), *totals = (int64_t *)(base + ws.totals);
     hipLaunchKernelGGL(voxel::vox_heads_kernel, dim3((unsigned)((N + voxel::kBlock - 1) / voxel::kBlock)), dim3(voxel::kBlock), 0, st, keys_dev,
                        order_dev, offsets_dev, S, N, head);
-    voxel::compact(voxel::HeadFlag{head}, N, (int32_t *)(base + ws.tile_counts), totals, run_start, true, st);
+    segs::compact(voxel::HeadFlag{head}, N, (int32_t *)(base + ws.tile_counts), totals, run_start, true, st);
     hipLaunchKernelGGL(voxel::vox_segment_counts_kernel, dim3((unsigned)((S + voxel::kBlock - 1) / voxel::kBlock)), dim3(voxel::kBlock), 0, st,
                        (const int64_t *)run_start, (const int64_t *)totals, offsets_dev, S, seg_voxels_dev);
     return check_hip(hipGetLastError(), who);
@@ -393,15 +246,15 @@ extern "C" int mspa_voxel_segments_means_device(const double *rows_dev, int64_t 
     if (M < 0 || M > N) return fail(MSPA_EINVAL, std::string(who) + ": M must be between 0 and the number of rows");
     if (M == 0) return MSPA_OK;
     if (!rows_dev || !offsets_dev || !order_dev || !out_rows_dev || !out_counts_dev) return fail(MSPA_EINVAL, std::string(who) + ": null pointer");
-    if (voxel::misaligned(rows_dev, 8) || voxel::misaligned(offsets_dev, 8) || voxel::misaligned(order_dev, 8) ||
-        voxel::misaligned(out_rows_dev, 8) || voxel::misaligned(out_counts_dev, 4))
+    if (segs::misaligned(rows_dev, 8) || segs::misaligned(offsets_dev, 8) || segs::misaligned(order_dev, 8) ||
+        segs::misaligned(out_rows_dev, 8) || segs::misaligned(out_counts_dev, 4))
         return fail(MSPA_EINVAL, std::string(who) + ": a buffer is not aligned to its element");
     hipStream_t st = (hipStream_t)stream;
-    const voxel::Workspace ws(N, S, voxel::extent_tiles(offsets_host, S));
+    const voxel::Workspace ws(N, S, segs::extent_tiles(offsets_host, S));
     uint8_t *base = (uint8_t *)workspace;
     const int64_t *run_start = (const int64_t *)(base + ws.run_start);
     int64_t *totals = (int64_t *)(base + ws.totals), *long_list = (int64_t *)(base + ws.long_list);
-    voxel::compact(voxel::LongFlag{run_start, totals}, M, (int32_t *)(base + ws.tile_counts), totals + 1, long_list, false, st);
+    segs::compact(voxel::LongFlag{run_start, totals}, M, (int32_t *)(base + ws.tile_counts), totals + 1, long_list, false, st);
     hipLaunchKernelGGL(voxel::vox_short_means_kernel, dim3((unsigned)((M + voxel::kBlock - 1) / voxel::kBlock)), dim3(voxel::kBlock), 0, st, rows_dev,
                        C, offsets_dev, S, N, order_dev, run_start, (const int64_t *)totals, M, out_rows_dev, out_counts_dev);
     const int64_t most_long = N / (voxel::kSequential + 1);

@@ -54,6 +54,13 @@ def _upload(*arrays, device) -> list:
             for a, at in zip(arrays, starts)]
 
 
+def _offsets_of(counts) -> np.ndarray:
+    """Per-segment counts [S] -> the offsets [S + 1] of the rows they count, back to back: a host int64 array from 0."""
+    offsets = np.zeros((len(counts) + 1,), dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return offsets
+
+
 def _knn_check(k: int) -> int:
     k = int(k)
     _require(1 <= k <= _lib.KNN_MAX_K, f"k: between 1 and {_lib.KNN_MAX_K}, got {k}")
@@ -172,8 +179,7 @@ def clean_segments(rows: torch.Tensor, offsets, nb_neighbors=20, std_ratio=1.0):
         raise
     stats = outlier_stats_segments(avg, off, std_ratio, xyz)
     kept = stats["kept"].cpu().numpy()                                                      # THE second read-back
-    kept_offsets = np.zeros((off.size,), dtype=np.int64)
-    np.cumsum(kept, out=kept_offsets[1:])
+    kept_offsets = _offsets_of(kept)
     index = torch.nonzero_static(stats["keep"], size=int(kept_offsets[-1])).flatten()       # its size is known: no read-back of its own
     return rows.index_select(0, index), kept_offsets, stats["lo"], stats["hi"], index
 
@@ -231,8 +237,7 @@ def remove_statistical_outliers_segments_host(rows, offsets, nb_neighbors=20, st
     if not np.isfinite(xyz).all():
         raise ValueError("remove_statistical_outliers: the cloud has non-finite coordinates")
     stats = outlier_stats_segments_host(knn_mean_distance_segments_host(xyz, off, int(nb_neighbors)), off, std_ratio, xyz)
-    kept_offsets = np.zeros((off.size,), dtype=np.int64)
-    np.cumsum(stats["kept"], out=kept_offsets[1:])
+    kept_offsets = _offsets_of(stats["kept"])
     return rows[stats["keep"]], kept_offsets, stats["lo"], stats["hi"]
 
 
@@ -256,6 +261,27 @@ def _raise_voxel_flags(flags: int, voxel_size: float) -> None:
     if flags & VOXEL_OUT_OF_RANGE:
         raise ValueError(f"voxel_down_sample: voxel_size {voxel_size} is too small for a segment's extent "
                          f"(a voxel index reaches 2^{_lib.VOXEL_AXIS_BITS} on an axis)")
+
+
+def _cell_keys(rows: torch.Tensor, C: int, off: np.ndarray, side: float, seg_out: torch.Tensor):
+    """The cell keys of a non-empty batch ``rows`` [N, C] float64 on a grid of ``side``, sorted: ``seg_out`` [S + 1] int32 (device) has
+    its first S entries zeroed and takes the flag word in its last.  -> ``(off_dev, base_dev, keys, order, work)``: the offsets and
+    the extents pass's tile table on the device, the keys [N] int64 in row order, the rows' order [N] int64 by (segment, key) with
+    ties in row order, and the workspace of ``mspa_voxel_segments_workspace_bytes`` the keys pass used.  Enqueues only."""
+    lib = _lib.load()
+    N, S, dev = int(rows.shape[0]), off.size - 1, rows.device
+    tile_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
+    off_dev, base_dev = _upload(off, tile_base, device=dev)
+    keys = torch.empty((N,), dtype=torch.int64, device=dev)
+    segment = torch.empty((N,), dtype=torch.int32, device=dev)
+    work = _workspace(int(lib.mspa_voxel_segments_workspace_bytes(off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_voxel_segments_keys_device(_ptr(rows), C, off.ctypes.data, S, side, _ptr(off_dev), _ptr(base_dev), _ptr(keys),
+                                                   _ptr(segment), _ptr(seg_out), _ptr(work), int(work.numel()), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    if S > 1:                                              # stably by segment behind stably by key: (segment, key), ties in row order
+        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    return off_dev, base_dev, keys, order, work
 
 
 def voxel_down_sample_segments(rows: torch.Tensor, offsets, voxel_size):
@@ -283,24 +309,13 @@ def voxel_down_sample_segments(rows: torch.Tensor, offsets, voxel_size):
         return (torch.empty((0, C), dtype=torch.float64, device=dev), np.zeros((S + 1,), dtype=np.int64),
                 torch.empty((0,), dtype=torch.int32, device=dev))
     lib = _lib.load()
-    tile_base = np.zeros((S + 1,), dtype=np.int64)
-    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
-    off_dev, base_dev = _upload(off, tile_base, device=dev)
-    keys = torch.empty((N,), dtype=torch.int64, device=dev)
-    segment = torch.empty((N,), dtype=torch.int32, device=dev)
     seg_voxels = torch.empty((S + 1,), dtype=torch.int32, device=dev)
-    work = _workspace(int(lib.mspa_voxel_segments_workspace_bytes(off.ctypes.data, S)), dev)
-    _lib.check(lib.mspa_voxel_segments_keys_device(_ptr(rows), C, off.ctypes.data, S, size, _ptr(off_dev), _ptr(base_dev), _ptr(keys),
-                                                   _ptr(segment), _ptr(seg_voxels), _ptr(work), int(work.numel()), _stream_ptr()))
-    order = torch.sort(keys, stable=True).indices
-    if S > 1:                                              # stably by segment behind stably by key: (segment, key), ties in row order
-        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    off_dev, _base_dev, keys, order, work = _cell_keys(rows, C, off, size, seg_voxels)
     _lib.check(lib.mspa_voxel_segments_heads_device(off.ctypes.data, S, _ptr(off_dev), _ptr(keys), _ptr(order), _ptr(seg_voxels), _ptr(work),
                                                     int(work.numel()), _stream_ptr()))
     back = seg_voxels.cpu().numpy()                        # THE read-back
     _raise_voxel_flags(int(back[S]), size)
-    out_offsets = np.zeros((S + 1,), dtype=np.int64)
-    np.cumsum(back[:S], out=out_offsets[1:])
+    out_offsets = _offsets_of(back[:S])
     M = int(out_offsets[-1])
     out_rows = torch.empty((M, C), dtype=torch.float64, device=dev)
     counts = torch.empty((M,), dtype=torch.int32, device=dev)
@@ -375,18 +390,8 @@ def _dbscan_device(rows: torch.Tensor, offsets, eps, min_points, want_keep: bool
     if N == 0:
         return labels, keep, np.zeros((2 * S + 1,), dtype=np.int32), lo, hi
     lib = _lib.load()
-    tile_base = np.zeros((S + 1,), dtype=np.int64)
-    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
-    off_dev, base_dev = _upload(off, tile_base, device=dev)
-    keys = torch.empty((N,), dtype=torch.int64, device=dev)
-    segment = torch.empty((N,), dtype=torch.int32, device=dev)
     seg = torch.empty((2 * S + 1,), dtype=torch.int32, device=dev)
-    cells_work = _workspace(int(lib.mspa_voxel_segments_workspace_bytes(off.ctypes.data, S)), dev)
-    _lib.check(lib.mspa_voxel_segments_keys_device(_ptr(xyz), 3, off.ctypes.data, S, side, _ptr(off_dev), _ptr(base_dev), _ptr(keys),
-                                                   _ptr(segment), _ptr(seg[S:]), _ptr(cells_work), int(cells_work.numel()), _stream_ptr()))
-    order = torch.sort(keys, stable=True).indices
-    if S > 1:                                              # stably by segment behind stably by key, as the down-sample sorts
-        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    off_dev, base_dev, keys, order, _cells_work = _cell_keys(xyz, 3, off, side, seg[S:])     # as the down-sample sorts
     work = _workspace(int(lib.mspa_dbscan_segments_workspace_bytes(off.ctypes.data, S)), dev)
     _lib.check(lib.mspa_dbscan_segments_device(_ptr(xyz), 3, off.ctypes.data, S, e, m, _ptr(off_dev), _ptr(keys), _ptr(order), _ptr(base_dev),
                                                _ptr(labels), _ptr(keep), _ptr(lo), _ptr(hi), _ptr(seg), _ptr(work), int(work.numel()),
@@ -422,8 +427,7 @@ def largest_cluster_segments(rows: torch.Tensor, offsets, eps, min_points):
     ``dbscan_segments``'."""
     _labels, keep, back, lo, hi = _dbscan_device(rows, offsets, eps, min_points, True)
     S = (back.size - 1) // 2
-    kept_offsets = np.zeros((S + 1,), dtype=np.int64)
-    np.cumsum(back[:S], out=kept_offsets[1:])
+    kept_offsets = _offsets_of(back[:S])
     index = torch.nonzero_static(keep.view(torch.bool), size=int(kept_offsets[-1])).flatten()    # its size is known: no read-back of its own
     return rows.index_select(0, index), kept_offsets, lo, hi, index
 
@@ -459,8 +463,7 @@ def largest_cluster_segments_host(rows, offsets, eps, min_points):
     """``largest_cluster_segments`` on the CPU for NumPy input, through the same header: NumPy arrays out, the same exceptions."""
     rows, off, _labels, _clusters, keep, kept = _dbscan_host(rows, offsets, eps, min_points, True)
     S = off.size - 1
-    kept_offsets = np.zeros((S + 1,), dtype=np.int64)
-    np.cumsum(kept, out=kept_offsets[1:])
+    kept_offsets = _offsets_of(kept)
     index = np.nonzero(keep)[0].astype(np.int64)
     out = rows[index]
     lo, hi = np.full((S, 3), np.inf), np.full((S, 3), -np.inf)

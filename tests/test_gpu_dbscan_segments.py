@@ -14,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dbscan_segments_util as D  # noqa: E402
+import voxel_segments_util as V  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 CASES = [(eps, m) for eps in D.eps_values() for m in D.MIN_POINTS]
@@ -60,6 +61,22 @@ def test_the_largest_cluster_equals_the_host_twins(eps, min_points):
         assert kept.is_cuda and index.dtype == torch.int64 and isinstance(kept_offsets, np.ndarray) and kept_offsets.dtype == np.int64
         assert np.array_equal(index.cpu().numpy(), want[4]) and np.array_equal(kept_offsets, want[1])
         assert np.array_equal(kept.cpu().numpy(), want[0]) and np.array_equal(lo.cpu().numpy(), want[2]) and np.array_equal(hi.cpu().numpy(), want[3])
+
+
+def test_more_than_256_compaction_tiles_so_that_the_scan_takes_two_tiles_per_thread():
+    """tests/voxel_segments_util.scan_batch() at (eps 0.4, min_points 1): every distinct point is its own cluster, so 526 400 of the
+    526 750 rows are representatives; the compaction has 258 tiles of 2 048 rows and the one workgroup's scan gives each thread two."""
+    from mspa import cloud_segments as CS
+    host_rows, offsets = V.scan_batch()
+    rows = torch.from_numpy(host_rows.copy()).cuda()
+    want_labels, want_clusters = CS.dbscan_segments_host(host_rows, offsets, 0.4, 1)
+    assert int(want_clusters.sum()) == 526400 > V.SCAN_SLOTS and want_labels.min() == 0
+    labels, clusters = CS.dbscan_segments(rows, offsets, 0.4, 1)
+    assert np.array_equal(labels.cpu().numpy(), want_labels) and np.array_equal(clusters, want_clusters) and clusters.dtype == np.int64
+    want = CS.largest_cluster_segments_host(host_rows, offsets, 0.4, 1)
+    kept, kept_offsets, lo, hi, index = CS.largest_cluster_segments(rows, offsets, 0.4, 1)
+    assert np.array_equal(index.cpu().numpy(), want[4]) and np.array_equal(kept_offsets, want[1]) and kept_offsets[-1] == 1 + 1 + 71
+    assert np.array_equal(kept.cpu().numpy(), want[0]) and np.array_equal(lo.cpu().numpy(), want[2]) and np.array_equal(hi.cpu().numpy(), want[3])
 
 
 def test_extra_columns_and_float32_rows_are_carried_and_widened():

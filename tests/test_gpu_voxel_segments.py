@@ -39,6 +39,16 @@ def test_the_device_equals_the_host_twin_bit_for_bit_and_itself_on_a_second_run(
     assert all(np.array_equal(a, b) for a, b in zip(first, second)) and np.array_equal(V.bits(first[0]), V.bits(second[0]))
 
 
+def test_more_than_256_compaction_tiles_so_that_the_scan_takes_two_tiles_per_thread():
+    """V.scan_batch(): 526 750 slots, 526 400 voxels (five of them runs of 71 rows), so both compactions -- the heads over the slots
+    and the long runs over the voxels -- have 258 tiles of 2 048 and the one workgroup's scan gives each thread two."""
+    from mspa import cloud_segments as CS
+    rows, offsets = V.scan_batch()
+    want = CS.voxel_down_sample_segments_host(rows, offsets, 0.5)
+    assert len(want[0]) == 526400 > V.SCAN_SLOTS and int((want[2] == 71).sum()) == 5 and int((want[2] == 1).sum()) == 526395
+    V.assert_same(_np(CS.voxel_down_sample_segments(torch.from_numpy(rows.copy()).cuda(), offsets, 0.5)), want)
+
+
 def test_a_float32_origin_input_widened_to_float64():
     from mspa import cloud_segments as CS
     rows, offsets, _names = V.batch(6)

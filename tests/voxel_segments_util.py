@@ -50,6 +50,30 @@ def batch(columns=3):
     return rows, off, names
 
 
+SCAN_SLOTS = 256 * 2048                          # the compaction's scan: 256 threads, a tile of 2 048 slots each up to here
+
+
+@functools.lru_cache(maxsize=None)
+def scan_batch():
+    """(rows [N, 4] float64, offsets [5] int64) for the compaction's scan with TWO tiles per thread: more than 256 tiles of 2 048 slots.
+    The first 526 400 points of the integer lattice 81^3 (spacing 1.0) in three segments with an empty one between them, the
+    first boundary (200 003) no multiple of a tile; the last segment also holds five of its lattice points 70 more times each, so
+    five voxels are runs of 71 rows.  Every lattice point is its own voxel at size 0.5 and its own cluster at eps 0.4, so the heads,
+    the voxels and the representatives all pass 256 tiles.  The fourth column is a row-dependent integer.  Built once, never written."""
+    n = 526400
+    i = np.arange(n, dtype=np.int64)
+    lattice = np.stack([i // 6561, i // 81 % 81, i % 81], axis=1).astype(np.float64)
+    repeated = lattice[[400000, 411111, 450007, 500000, n - 1]].repeat(70, axis=0)
+    xyz = np.concatenate([lattice, repeated])
+    r = np.arange(len(xyz), dtype=np.int64)
+    rows = np.ascontiguousarray(np.concatenate([xyz, ((r * 7) % 1000)[:, None].astype(np.float64)], axis=1))
+    off = np.array([0, 200003, 200003, 400000, len(rows)], dtype=np.int64)
+    assert len(rows) > SCAN_SLOTS and n > SCAN_SLOTS and off[1] % 2048 and off[1] % 4096
+    rows.setflags(write=False)
+    off.setflags(write=False)
+    return rows, off
+
+
 def small_batches():
     """tests/cloud_segments_util.py's further cases (one segment, every segment empty, no segment at all) and one row."""
     out = dict(U.small_batches())

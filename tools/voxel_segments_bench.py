@@ -152,7 +152,7 @@ def main():
         print()
         print("| stage of the op, alone with a synchronise behind it | median (ms) | passes (ms) |")
         print("|---|---|---|")
-        names = ("extents and keys (vox_extent_tiles / vox_extent_fold / vox_keys kernels)", "sorts (torch.sort by key, then by segment, gathers)",
+        names = ("extents and keys (extent_tiles<1, TakeAll> / extent_fold<1> / vox_keys kernels)", "sorts (torch.sort by key, then by segment, gathers)",
                  "heads (vox_heads, count / scan / place, vox_segment_counts kernels)", "the read-back of the counts and the flag word",
                  "means (long-run list, vox_short_means / vox_long_means kernels)")
         stage_med = []
