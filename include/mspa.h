@@ -1296,6 +1296,62 @@ int mspa_dbscan_segments_device(const double *rows_dev, int64_t C, const int64_t
 int mspa_dbscan_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, double eps, int64_t min_points,
                               int32_t *labels_host, int32_t *clusters_host, uint8_t *keep_host, int32_t *kept_host, int32_t *flags_out);
 
+/*
+ * The UPRIGHT MINIMAL BOX of every cloud of a RAGGED BATCH (csrc/upright_segments.hip, rule in csrc/upright_box_core.h): per segment
+ * the strict convex hull of its distinct (x, y) pairs -- counter-clockwise from the lexicographically smallest vertex, collinear
+ * boundary points left out, a vertex reported as the lowest row that holds its coordinates, the orientation test EXACT (a floating
+ * filter, then the six products as error-free pairs summed as an expansion) -- the minimum-area rectangle around it by the
+ * all-edges rule (m_k = (along_k * across_k) / (d . d), the lowest k with the smallest m_k) and the z extent, as 8 f64:
+ * [cx, cy, cz, length, width, height, ux, uy], length >= width, (ux, uy) the unit direction of the length with ux > 0, or ux == 0
+ * and uy > 0; no hull vertex: eight NaN; one: sizes 0 and axis (1, 0).  The batch is the down-sample's: rows [N, C] f64 (xyz
+ * first, 3 <= C <= MSPA_VOXEL_MAX_COLUMNS) plus offsets [S + 1].  The same bits on every run: minima, maxima and an integer minimum
+ * over row indices only; no atomic places a row or takes part in a floating-point operation.
+ * FLAGS (a flag word that is not zero refuses the call): bit 0 a non-finite x, y or z; bit 1 a non-zero |x| or |y| outside
+ * [2^-200, 2^200] (the window that keeps the rule's products clear of overflow and underflow); bit 2 a hull chain that popped more
+ * often than its segment has survivors.
+ * Three device stages, because the caller sorts between them; each takes its offsets TWICE (host and device) and checks every
+ * argument from the host copy before anything is enqueued (MSPA_EINVAL: null pointer, offsets that descend or do not start at 0,
+ * more than 2^30 rows, S > 2^24, C out of range, more hull vertices than survivors in a segment, workspace too small or
+ * misaligned).  Twelve launches in all, whatever S is.  ALIGNMENT: workspace 16 bytes; every other buffer its element's size
+ * (f64 and int64: 8, int32: 4).
+ *   mspa_upright_filter_workspace_bytes   the workspace of the filter stage (-1 for offsets that are no batch).
+ *   mspa_upright_filter_device         8 launches.  -> list_dev [N] int64: in front the SURVIVORS' rows, ascending (a row is dropped only
+ *                                      where a floating test with its error bound proves it strictly inside a triangle of three
+ *                                      rows of its segment, so no hull vertex is ever dropped); ext_dev [S, 10] f64: the minima
+ *                                      of the negated supports in the 8 directions k * 45 degrees, then min z and min -z; seg_dev
+ *                                      [S + 1] int32: the survivors of each segment and the flag word (bits 0 and 1).
+ *                                      tile_base_dev is mspa_voxel_segments_tables_host's table on the device.
+ *   mspa_upright_hull_device           1 launch.  pts_dev [M, 2] f64: the survivors' (x, y) sorted by (segment, x, y), ties in row
+ *                                      order; kept_offsets [S + 1]: the survivors' offsets.  -> stack_dev [2, M] int32: the lower and
+ *                                      the upper chain of each segment (slots), seg_dev [2 S + 1] int32: the two chains' lengths
+ *                                      per segment (lower, upper) and the flag word (bit 2).  A segment's hull has 0 vertices
+ *                                      without survivors, 1 where the lower chain holds one slot, else lower + upper - 2.
+ *   mspa_upright_boxes_workspace_bytes the workspace of the boxes stage (-1 for hull offsets that are no batch).
+ *   mspa_upright_boxes_device          3 launches.  row_dev [M] int64: the input row of each sorted survivor; hull_offsets [S + 1]: the
+ *                                      hull vertices' offsets; edge_base_dev [S + 1] int64: the exclusive prefix of
+ *                                      ceil(vertices / 256) per segment; counts_dev: the hull stage's seg_dev.  -> hull_index_dev
+ *                                      [H] int64 the hull rows, edge_dev [S] int32 the chosen edge (-1 without a vertex),
+ *                                      boxes_dev [S, 8] f64.  Slots read from stack_dev are clamped into their segment: arguments
+ *                                      that are not the hull stage's give wrong boxes, never an access outside the buffers.
+ *   mspa_upright_segments_host         the whole op on the CPU through the same header: the device's twin for tests and for
+ *                                      NumPy input, not a fallback.  hull_index_host has room for N rows, hull_offsets_host
+ *                                      [S + 1], edges_host [S] int32, boxes_host [S, 8], *flags_out the flag word.
+ */
+int64_t mspa_upright_filter_workspace_bytes(const int64_t *offsets_host, int64_t S);
+int mspa_upright_filter_device(const double *rows_dev, int64_t C, const int64_t *offsets_host, int64_t S, const int64_t *offsets_dev,
+                               const int64_t *tile_base_dev, int64_t *list_dev, double *ext_dev, int32_t *seg_dev, void *workspace,
+                               int64_t workspace_bytes, mspa_stream_t stream);
+int mspa_upright_hull_device(const double *pts_dev, const int64_t *kept_offsets_host, int64_t S, const int64_t *kept_offsets_dev,
+                             int32_t *stack_dev, int32_t *seg_dev, mspa_stream_t stream);
+int64_t mspa_upright_boxes_workspace_bytes(const int64_t *hull_offsets_host, int64_t S);
+int mspa_upright_boxes_device(const double *pts_dev, const int64_t *row_dev, const int64_t *kept_offsets_host,
+                              const int64_t *hull_offsets_host, int64_t S, const int64_t *kept_offsets_dev, const int64_t *hull_offsets_dev,
+                              const int64_t *edge_base_dev, const int32_t *stack_dev, const int32_t *counts_dev, const double *ext_dev,
+                              int64_t *hull_index_dev, int32_t *edge_dev, double *boxes_dev, void *workspace, int64_t workspace_bytes,
+                              mspa_stream_t stream);
+int mspa_upright_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, int64_t *hull_index_host,
+                               int64_t *hull_offsets_host, int32_t *edges_host, double *boxes_host, int32_t *flags_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,14 @@ _SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mspa_dbscan_segments_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
+    "mspa_upright_filter_workspace_bytes": (c_int64, [c_void_p, c_int64]),
+    "mspa_upright_filter_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int64, c_void_p]),
+    "mspa_upright_hull_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_upright_boxes_workspace_bytes": (c_int64, [c_void_p, c_int64]),
+    "mspa_upright_boxes_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_upright_segments_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -12,7 +12,9 @@ torch is plumbing, as in ``mspa.engine``: the segmented order statistics (two so
 
 Two further ops take the same batch: ``voxel_down_sample_segments`` (csrc/voxel_segments.hip) thins every segment on a voxel grid,
 and ``dbscan_segments`` / ``largest_cluster_segments`` (csrc/dbscan_segments.hip, rule in csrc/dbscan_core.h) label every segment
-as scikit-learn's DBSCAN does and keep its largest cluster.
+as scikit-learn's DBSCAN does and keep its largest cluster.  ``footprint_hull_segments`` / ``upright_boxes_segments``
+(csrc/upright_segments.hip, rule in csrc/upright_box_core.h) give every segment the exact convex hull of its (x, y) footprint and
+its upright minimal box: the z extent times the minimum-area rectangle around that hull.
 """
 from __future__ import annotations
 
@@ -472,6 +474,160 @@ def largest_cluster_segments_host(rows, offsets, eps, min_points):
         if len(part):
             lo[s], hi[s] = part.min(axis=0), part.max(axis=0)
     return out, kept_offsets, lo, hi, index
+
+
+UPRIGHT_NON_FINITE, UPRIGHT_OUT_OF_WINDOW, UPRIGHT_CAP_REACHED = 1, 2, 4      # csrc/upright_box_core.h: the bits of the flag word
+UPRIGHT_EDGE_TILE = 256                                                      # csrc/upright_segments.hip: edges one workgroup takes
+
+
+def _raise_upright_flags(flags: int) -> None:
+    if flags & UPRIGHT_NON_FINITE:
+        raise ValueError("upright_boxes: the cloud has non-finite coordinates")
+    if flags & UPRIGHT_OUT_OF_WINDOW:
+        raise ValueError("upright_boxes: a non-zero |x| or |y| lies outside [2^-200, 2^200] (csrc/upright_box_core.h)")
+    if flags & UPRIGHT_CAP_REACHED:
+        raise RuntimeError("upright_boxes: a hull chain reached its iteration cap (csrc/upright_box_core.h)")
+
+
+def _upright_device(rows: torch.Tensor, offsets):
+    """The device op: (boxes [S, 8] float64, hull index [H] int64, hull_offsets [S + 1] host, chosen edges [S] int32, survivors [S]
+    host int64).  Holds THE two read-backs of ``upright_boxes_segments`` and ``footprint_hull_segments``."""
+    _require(isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[1] >= 3, "rows: a device tensor [N, C >= 3]")
+    xyz = _check("rows", rows[:, :3].to(torch.float64).contiguous(), torch.float64, (None, 3))
+    N = int(xyz.shape[0])
+    off = _offsets(offsets, N)
+    _require(N <= 1 << 30, f"rows: at most 2^30 rows, got {N}")
+    S = off.size - 1
+    dev = rows.device
+    boxes = torch.full((S, 8), float("nan"), dtype=torch.float64, device=dev)
+    edges = torch.full((S,), -1, dtype=torch.int32, device=dev)
+    if N == 0:
+        return boxes, torch.empty((0,), dtype=torch.int64, device=dev), np.zeros((S + 1,), dtype=np.int64), edges, np.zeros((S,), dtype=np.int64)
+    lib = _lib.load()
+    tile_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_voxel_segments_tables_host(off.ctypes.data, S, tile_base.ctypes.data))
+    off_dev, base_dev = _upload(off, tile_base, device=dev)
+    rows_list = torch.empty((N,), dtype=torch.int64, device=dev)
+    ext = torch.empty((S, 10), dtype=torch.float64, device=dev)
+    seg = torch.empty((S + 1,), dtype=torch.int32, device=dev)
+    work = _workspace(int(lib.mspa_upright_filter_workspace_bytes(off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_upright_filter_device(_ptr(xyz), 3, off.ctypes.data, S, _ptr(off_dev), _ptr(base_dev), _ptr(rows_list), _ptr(ext), _ptr(seg),
+                                              _ptr(work), int(work.numel()), _stream_ptr()))
+    back = seg.cpu().numpy()                               # THE first read-back
+    _raise_upright_flags(int(back[S]))
+    survivors = back[:S].astype(np.int64)
+    kept_off = _offsets_of(survivors)
+    M = int(kept_off[-1])
+    kept_dev, = _upload(kept_off, device=dev)
+    index = rows_list[:M]
+    xy = xyz.index_select(0, index)[:, :2]
+    order = torch.sort(xy[:, 1], stable=True).indices      # stably by y, by x, by segment: (segment, x, y), ties in row order
+    order = order.gather(0, torch.sort(xy[:, 0].gather(0, order), stable=True).indices)
+    if S > 1:
+        segment = torch.searchsorted(kept_dev[1:], torch.arange(M, dtype=torch.int64, device=dev), right=True)
+        order = order.gather(0, torch.sort(segment.gather(0, order), stable=True).indices)
+    pts = xy.index_select(0, order).contiguous()
+    row = index.gather(0, order)
+    stack = torch.empty((2, M), dtype=torch.int32, device=dev)
+    counts = torch.empty((2 * S + 1,), dtype=torch.int32, device=dev)
+    _lib.check(lib.mspa_upright_hull_device(_ptr(pts), kept_off.ctypes.data, S, _ptr(kept_dev), _ptr(stack), _ptr(counts), _stream_ptr()))
+    back = counts.cpu().numpy()                            # THE second read-back
+    _raise_upright_flags(int(back[2 * S]))
+    lower, upper = back[0:2 * S:2].astype(np.int64), back[1:2 * S:2].astype(np.int64)
+    hull_off = _offsets_of(np.where(lower <= 0, 0, np.where((lower == 1) | (upper <= 1), 1, lower + upper - 2)))
+    H = int(hull_off[-1])
+    edge_base = _offsets_of((np.diff(hull_off) + UPRIGHT_EDGE_TILE - 1) // UPRIGHT_EDGE_TILE)
+    hull_dev, edge_base_dev = _upload(hull_off, edge_base, device=dev)
+    hull_index = torch.empty((H,), dtype=torch.int64, device=dev)
+    work = _workspace(int(lib.mspa_upright_boxes_workspace_bytes(hull_off.ctypes.data, S)), dev)
+    _lib.check(lib.mspa_upright_boxes_device(_ptr(pts), _ptr(row), kept_off.ctypes.data, hull_off.ctypes.data, S, _ptr(kept_dev), _ptr(hull_dev),
+                                             _ptr(edge_base_dev), _ptr(stack), _ptr(counts), _ptr(ext), _ptr(hull_index), _ptr(edges), _ptr(boxes),
+                                             _ptr(work), int(work.numel()), _stream_ptr()))
+    return boxes, hull_index, hull_off, edges, survivors
+
+
+def upright_boxes_segments(rows: torch.Tensor, offsets, want_hull: bool = False, want_edges: bool = False, want_survivors: bool = False):
+    """A batch ``rows`` [N, C >= 3] (device; xyz in front, float64 or a dtype that widens to it exactly; extra columns are not read)
+    and host ``offsets`` [S + 1] -> ``boxes`` [S, 8] float64 (device): per segment the upright minimal box
+    ``[cx, cy, cz, length, width, height, ux, uy]`` -- the z extent of the segment (``cz`` and ``height`` are ``calculate_aabb``'s) times
+    the minimum-area rectangle around the convex hull of its (x, y) footprint; ``length >= width``, ``(ux, uy)`` the unit direction of
+    the length with ``ux > 0``, or ``ux == 0`` and ``uy > 0``.  An empty segment gives eight NaN; one distinct (x, y) gives sizes 0 and the
+    axis (1, 0).  The rule is csrc/upright_box_core.h's: the hull is the exact one (``footprint_hull_segments``), the rectangle is
+    the all-edges one -- for every hull edge the spans of the hull along and across it, ``m = (along * across) / (d . d)``, the lowest
+    edge with the smallest ``m`` -- and every step is one float64 operation in the header's order, so the boxes are the host twin's
+    bit for bit and the same bits on every run.  ``want_hull`` adds ``(index, hull_offsets)``, ``want_edges`` the chosen edges [S]
+    int32 (device; -1 for an empty segment), ``want_survivors`` the rows per segment [S] (host int64) that the device's filter left
+    for the hull.  At most two read-backs per call, whatever S is: the survivor counts with the flag word, and the hull counts with
+    the flag word.  A non-finite x, y or z, or a non-zero ``|x|`` or ``|y|`` outside [2^-200, 2^200], raises ValueError.  torch is
+    plumbing: the three stable sorts of the survivors (two when S = 1)."""
+    boxes, index, hull_offsets, edges, survivors = _upright_device(rows, offsets)
+    out = (boxes,) + ((index, hull_offsets) if want_hull else ()) + ((edges,) if want_edges else ()) + ((survivors,) if want_survivors else ())
+    return out[0] if len(out) == 1 else out
+
+
+def footprint_hull_segments(rows: torch.Tensor, offsets):
+    """A batch ``rows`` [N, C >= 3] (device) and host ``offsets`` [S + 1] -> ``(index [H] int64 device, hull_offsets [S + 1] host
+    int64)``: per segment the strict convex hull of its distinct (x, y) pairs as indices into ``rows``, counter-clockwise from the
+    lexicographically smallest vertex (x, then y); collinear boundary points are not vertices; a vertex is the lowest row that holds
+    its coordinates; 0 vertices for an empty segment, 1 for one distinct point, 2 for collinear points.  The orientation test is
+    exact (csrc/upright_box_core.h), so the hull is the mathematical one and does not depend on the order of the rows.  At most two
+    read-backs per call, whatever S is: the survivor counts with the flag word, and the hull counts with the flag word.  The
+    exceptions are ``upright_boxes_segments``'."""
+    _boxes, index, hull_offsets, _edges, _survivors = _upright_device(rows, offsets)
+    return index, hull_offsets
+
+
+def _upright_host(rows, offsets):
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < 3:
+        raise ValueError(f"mspa.cloud_segments: rows: expected [N, C >= 3], got {list(rows.shape)}")
+    xyz = np.ascontiguousarray(rows[:, :3], dtype=np.float64)
+    N = xyz.shape[0]
+    off = _offsets(offsets, N)
+    S = off.size - 1
+    index = np.zeros((max(N, 1),), dtype=np.int64)
+    hull_off = np.zeros((S + 1,), dtype=np.int64)
+    edges = np.full((max(S, 1),), -1, dtype=np.int32)
+    boxes = np.full((max(S, 1), 8), np.nan)
+    flags = np.zeros((1,), dtype=np.int32)
+    _lib.check(_lib.load().mspa_upright_segments_host(xyz.ctypes.data, 3, off.ctypes.data, S, index.ctypes.data, hull_off.ctypes.data,
+                                                      edges.ctypes.data, boxes.ctypes.data, flags.ctypes.data))
+    _raise_upright_flags(int(flags[0]))
+    return boxes[:S], index[:int(hull_off[-1])].copy(), hull_off, edges[:S]
+
+
+def upright_boxes_segments_host(rows, offsets, want_hull: bool = False, want_edges: bool = False):
+    """``upright_boxes_segments`` on the CPU for NumPy input, through the same header (mspa_upright_segments_host): NumPy arrays out,
+    the same exceptions.  It runs no filter in front of the hull (none can change it).  The device's twin for tests and for input
+    that has no device, not a fallback."""
+    boxes, index, hull_offsets, edges = _upright_host(rows, offsets)
+    out = (boxes,) + ((index, hull_offsets) if want_hull else ()) + ((edges,) if want_edges else ())
+    return out[0] if len(out) == 1 else out
+
+
+def footprint_hull_segments_host(rows, offsets):
+    """``footprint_hull_segments`` on the CPU for NumPy input, through the same header: NumPy arrays out, the same exceptions.  The
+    device's twin, not a fallback."""
+    _boxes, index, hull_offsets, _edges = _upright_host(rows, offsets)
+    return index, hull_offsets
+
+
+def upright_corners(boxes: torch.Tensor) -> torch.Tensor:
+    """Upright boxes [..., 8] -> their corners [..., 8, 3]: the four footprint corners counter-clockwise from
+    ``centre - length / 2 * u - width / 2 * n`` (``n = (-uy, ux)``) at the lower z, then the same four at the upper z.  Enqueue only."""
+    zero = torch.zeros_like(boxes[..., 0])
+    centre = boxes[..., :3]
+    u = torch.stack([boxes[..., 6], boxes[..., 7], zero], dim=-1) * (boxes[..., 3:4] / 2)          # half the length along the axis
+    n = torch.stack([-boxes[..., 7], boxes[..., 6], zero], dim=-1) * (boxes[..., 4:5] / 2)         # half the width across it
+    up = torch.stack([zero, zero, boxes[..., 5] / 2], dim=-1)
+    foot = [centre - u - n, centre + u - n, centre + u + n, centre - u + n]
+    return torch.stack([c - up for c in foot] + [c + up for c in foot], dim=-2)
+
+
+def upright_yaw(boxes: torch.Tensor) -> torch.Tensor:
+    """Upright boxes [..., 8] -> the angle of the length's direction against +x, ``atan2(uy, ux)``, in (-pi / 2, pi / 2].  Enqueue
+    only.  Its last bits are torch's ``atan2``, not pinned by the rule: the rule itself carries the axis, not an angle."""
+    return torch.atan2(boxes[..., 7], boxes[..., 6])
 
 
 def boxes_of(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:

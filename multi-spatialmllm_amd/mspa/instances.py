@@ -105,6 +105,14 @@ class InstanceClouds:
         from . import cloud_segments
         return cloud_segments.boxes_of(self.lo, self.hi)
 
+    def upright_boxes(self) -> torch.Tensor:
+        """[F, L, 8] float64 on the device: the upright minimal box ``[cx, cy, cz, length, width, height, ux, uy]`` of every (image,
+        label) at once -- ``ops.calculate_upright_box(cloud(image, object))`` bit for bit; NaN where the segment is empty.  One
+        batched pass (``cloud_segments.upright_boxes_segments``: at most two read-backs, its exceptions); it needs the rows on the
+        device."""
+        from . import cloud_segments
+        return cloud_segments.upright_boxes_segments(self.rows, self.offsets).reshape(self.counts.shape + (8,))
+
     def _object_runs(self):
         """(shift [O * F], lengths [O * F], offsets [O + 1], object_ids [O]) as host int64 arrays: run (j, k) of the regrouped rows is
         object ``object_ids[j]`` = label ``object_ids[j] + 1`` in frame k; regrouped row p of that run is row p + shift of ``rows``.  The
@@ -142,20 +150,22 @@ class InstanceClouds:
             rows, offsets, _counts = cloud_segments.voxel_down_sample_segments(rows, offsets, voxel_size)
         return rows, offsets, object_ids
 
-    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None, cluster=None):
+    def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None, cluster=None, upright=False):
         """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
         ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``
         [O + 1]; ``boxes`` [O, 6] float64 (device) their ``calculate_aabb``, NaN where nothing is kept.  With a ``voxel_size`` each
         fused cloud is down-sampled first (``by_object(voxel_size)``), then cleaned: the neighbours of a point are then other
         places of the surface, not its own copies from other frames.  With ``cluster=(eps, min_points)`` each cleaned cloud is then
         cut down to its largest DBSCAN cluster (``cloud_segments.largest_cluster_segments``), and the boxes are those of what is
-        kept."""
+        kept.  With ``upright=True`` one more element follows: [O, 8] float64 (device), the upright minimal boxes of what is kept
+        (``cloud_segments.upright_boxes_segments``: at most two more read-backs, its exceptions), NaN where nothing is kept."""
         from . import cloud_segments
         rows, offsets, object_ids = self.by_object(voxel_size)
         kept, kept_offsets, lo, hi = cloud_segments.remove_statistical_outliers_segments(rows, offsets, nb_neighbors, std_ratio)
         if cluster is not None:
             kept, kept_offsets, lo, hi, _index = cloud_segments.largest_cluster_segments(kept, kept_offsets, *cluster)
-        return kept, kept_offsets, object_ids, cloud_segments.boxes_of(lo, hi)
+        out = (kept, kept_offsets, object_ids, cloud_segments.boxes_of(lo, hi))
+        return out + (cloud_segments.upright_boxes_segments(kept, kept_offsets),) if upright else out
 
 
 def _mask_path(handler, scene_id, image_id) -> str:

@@ -291,7 +291,7 @@ class SceneInfoHandler:
         return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
 
     def instance_boxes(self, scene_id, image_ids=None, nb_neighbors=20, std_ratio=1.0, per="image", device="cuda", num_workers=8,
-                       voxel_size=None, cluster=None):
+                       voxel_size=None, cluster=None, upright=False):
         """The rest of the tool chain for every object of a scene at once: ``instance_clouds`` -> cleaned clouds
         (``remove_statistical_outliers(cloud, nb_neighbors, std_ratio)`` per segment) -> boxes (``calculate_aabb``) -> IoU against
         ``get_object_gt_bbox(scene_id, target_id, axis_aligned=True)[:6]`` (``calculate_iou_3d``), in a number of launches and
@@ -307,7 +307,10 @@ class SceneInfoHandler:
         With ``per="object"`` a ``voxel_size`` down-samples each fused cloud on a voxel grid before it is cleaned
         (``InstanceClouds.cleaned_objects(voxel_size=...)``); with ``per="image"`` a size raises ValueError: a single view's cloud
         is already one sample per pixel.  ``cluster=(eps, min_points)`` keeps, after the cleaning, each cloud's largest DBSCAN
-        cluster (``mspa.cloud_segments.largest_cluster_segments``): boxes, ``kept`` and IoU are taken from what is kept."""
+        cluster (``mspa.cloud_segments.largest_cluster_segments``): boxes, ``kept`` and IoU are taken from what is kept.
+        ``upright=True`` adds the key ``upright``: [F, L, 8] or [O, 8] float64 (device), the upright minimal boxes
+        ``[cx, cy, cz, length, width, height, ux, uy]`` of what is kept (``mspa.cloud_segments.upright_boxes_segments``: at most two
+        more read-backs), NaN where nothing is kept.  ``iou`` stays the axis-aligned boxes'."""
         from mspa import cloud_segments
         if per not in ("image", "object"):
             raise ValueError(f"instance_boxes: per must be 'image' or 'object', got {per!r}")
@@ -319,10 +322,14 @@ class SceneInfoHandler:
             cleaned = clouds.cleaned(nb_neighbors, std_ratio, cluster)
             boxes, kept, targets = cleaned.boxes(), cleaned.counts, np.arange(clouds.n_labels, dtype=np.int64) - 1
             out = {"image_ids": list(clouds.image_ids)}
+            if upright:
+                out["upright"] = cleaned.upright_boxes()
         else:
-            _rows, offsets, targets, boxes = clouds.cleaned_objects(nb_neighbors, std_ratio, voxel_size, cluster)
+            _rows, offsets, targets, boxes, *more = clouds.cleaned_objects(nb_neighbors, std_ratio, voxel_size, cluster, upright)
             kept = np.diff(offsets)
             out = {"object_ids": targets}
+            if upright:
+                out["upright"] = more[0]
         gt = np.full((len(targets), 6), np.nan)
         for j, t in enumerate(targets):
             if 0 <= t < n_objects:

@@ -16,8 +16,8 @@ from ._images import read_color_rgb, read_depth
 
 __all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
            "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
-# (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample`` and ``cluster_dbscan`` below are this
-# project's own and are reached as ``ops.voxel_down_sample`` and ``ops.cluster_dbscan``)
+# (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample``, ``cluster_dbscan`` and
+# ``calculate_upright_box`` below are this project's own and are reached as ``ops.voxel_down_sample`` and so on)
 
 
 def _same_device(a, b):
@@ -159,6 +159,26 @@ def cluster_dbscan(point_cloud_data, eps, min_points):
         return cloud_segments.dbscan_segments(data, offsets, eps, min_points)[0]
     out = cloud_segments.dbscan_segments_host(data.numpy() if is_tensor else data, offsets, eps, min_points)[0]
     return torch.from_numpy(out) if is_tensor else out
+
+
+def calculate_upright_box(point_cloud_data):
+    """[N, C >= 3] cloud -> its upright minimal box [8] float64: ``[cx, cy, cz, length, width, height, ux, uy]``, the z extent of
+    the cloud (``cz`` and ``height`` are ``calculate_aabb``'s) times the minimum-area rectangle around the convex hull of its (x, y)
+    footprint; ``length >= width``, and ``(ux, uy)`` is the unit direction of the length with ``ux > 0``, or ``ux == 0`` and ``uy > 0``.
+    Where ``calculate_aabb`` gives a couch standing at 30 degrees in its room a box that is far longer and wider than the couch,
+    this box has the couch's own length and width.  It is the S = 1 case of ``mspa.cloud_segments.upright_boxes_segments`` (rule in
+    csrc/upright_box_core.h: an exact hull, the all-edges rectangle, every step one float64 operation), the same bits on every run
+    and the same bits on the device as on the host.  NumPy in gives NumPy out (the host twin of the kernels), a device tensor in
+    gives a device tensor out; N = 0 returns eight NaN.  Non-finite coordinates, or a non-zero ``|x|`` or ``|y|`` outside
+    [2^-200, 2^200], raise ValueError.  No reference counterpart: upstream's lengths and widths are those of the axis-aligned box."""
+    from mspa import cloud_segments
+    is_tensor = isinstance(point_cloud_data, torch.Tensor)
+    data = point_cloud_data if is_tensor else np.asarray(point_cloud_data)
+    offsets = np.array([0, int(data.shape[0])], dtype=np.int64)
+    if is_tensor and data.is_cuda:
+        return cloud_segments.upright_boxes_segments(data, offsets)[0]
+    out = cloud_segments.upright_boxes_segments_host(data.numpy() if is_tensor else data, offsets)[0]
+    return torch.from_numpy(out.copy()) if is_tensor else out.copy()
 
 
 def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
