@@ -1352,6 +1352,36 @@ int mspa_upright_boxes_device(const double *pts_dev, const int64_t *row_dev, con
 int mspa_upright_segments_host(const double *rows_host, int64_t C, const int64_t *offsets_host, int64_t S, int64_t *hull_index_host,
                                int64_t *hull_offsets_host, int32_t *edges_host, double *boxes_host, int32_t *flags_out);
 
+/*
+ * The INTERSECTION OVER UNION of UPRIGHT BOXES (csrc/upright_iou.hip, rule in csrc/upright_iou_core.h): boxes are 8 f64
+ * [cx, cy, cz, length, width, height, ux, uy] as the upright block above emits them; a pair gives one f64, the volume of the
+ * intersection over that of the union, the footprints (rectangles c +- (length / 2) u +- (width / 2) n, n = (-uy, ux)) clipped by
+ * Sutherland-Hodgman in the frame of the box with the larger length * width.  Every step is one rounded f64 operation in the
+ * header's order: the device gives the host twin's bits, the same bits on every run, and iou(a, b) and iou(b, a) are the same
+ * bits.  A box with a non-finite value, a negative size, |ux^2 + uy^2 - 1| > 2^-20, or a non-zero centre or size outside
+ * [2^-200, 2^200] is REFUSED: its pairs give NaN; no flag word is kept and nothing is read back.  Two boxes equal in all eight
+ * values give exactly 1.0 (NaN with zero volume).  Otherwise 0 <= IoU <= 1, or NaN where both volumes are zero.
+ *   mode MSPA_UPRIGHT_IOU_PAIRS    a [Pa, 8], b [Pb, 8] with Pa == Pb, or either of them 1 (one box against many); G = A = B = 0;
+ *                                  out [P], P the larger count (0 if either is 0).
+ *   mode MSPA_UPRIGHT_IOU_MATRIX   a [G, A, 8], b [G, B, 8] (Pa == G * A, Pb == G * B); out [G, A, B].
+ * parts (may be null) [.., 2] takes per output the footprint intersection area and the z overlap (zero or negative where the boxes
+ * do not overlap in z).  One launch on the caller's stream; every argument is checked before anything is enqueued (MSPA_EINVAL:
+ * a null pointer where a count is positive, a negative count, counts that do not fit the mode, more than 2^31 outputs, a
+ * misaligned buffer); a call with zero outputs enqueues nothing.  This entry point only enqueues.  ALIGNMENT: every buffer its
+ * element's size (f64: 8).
+ *   mspa_upright_iou_host          the same op on the CPU through the same header: the device's twin for tests and for NumPy
+ *                                  input, not a fallback.
+ *   mspa_upright_iou_bound_host    a [P, 8], b [P, 8] -> per pair the header's forward-error bounds of the footprint area and of
+ *                                  the IoU against the exact rational values (NaN for a refused pair).
+ */
+#define MSPA_UPRIGHT_IOU_PAIRS 0
+#define MSPA_UPRIGHT_IOU_MATRIX 1
+int mspa_upright_iou_device(const double *a_dev, int64_t Pa, const double *b_dev, int64_t Pb, int64_t G, int64_t A, int64_t B, int32_t mode,
+                            double *out_dev, double *parts_dev, mspa_stream_t stream);
+int mspa_upright_iou_host(const double *a_host, int64_t Pa, const double *b_host, int64_t Pb, int64_t G, int64_t A, int64_t B, int32_t mode,
+                          double *out_host, double *parts_host);
+int mspa_upright_iou_bound_host(const double *a_host, const double *b_host, int64_t P, double *area_bound_out, double *iou_bound_out);
+
 #ifdef __cplusplus
 }
 #endif

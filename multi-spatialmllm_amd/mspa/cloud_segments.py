@@ -14,7 +14,8 @@ Two further ops take the same batch: ``voxel_down_sample_segments`` (csrc/voxel_
 and ``dbscan_segments`` / ``largest_cluster_segments`` (csrc/dbscan_segments.hip, rule in csrc/dbscan_core.h) label every segment
 as scikit-learn's DBSCAN does and keep its largest cluster.  ``footprint_hull_segments`` / ``upright_boxes_segments``
 (csrc/upright_segments.hip, rule in csrc/upright_box_core.h) give every segment the exact convex hull of its (x, y) footprint and
-its upright minimal box: the z extent times the minimum-area rectangle around that hull.
+its upright minimal box: the z extent times the minimum-area rectangle around that hull.  ``upright_iou`` / ``upright_iou_matrix``
+(csrc/upright_iou.hip, rule in csrc/upright_iou_core.h) score such boxes against each other, pair by pair or set against set.
 """
 from __future__ import annotations
 
@@ -644,3 +645,121 @@ def iou_3d(boxes: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
         torch.maximum(boxes[..., :3] - boxes[..., 3:] / 2, gt[..., :3] - gt[..., 3:] / 2)
     inter = torch.where((dim > 0).all(dim=-1), dim.prod(dim=-1), torch.zeros((), dtype=dim.dtype, device=dim.device))
     return inter / (boxes[..., 3:].prod(dim=-1) + gt[..., 3:].prod(dim=-1) - inter)
+
+
+def _iou_boxes(name: str, boxes, trailing: int) -> torch.Tensor:
+    """A box argument of the upright IoU, checked: a float64 device tensor [..., 8] with at least ``trailing`` axes -> itself."""
+    ok = isinstance(boxes, torch.Tensor) and boxes.dim() >= trailing and boxes.shape[-1] == 8 and boxes.dtype == torch.float64
+    if not ok or not boxes.is_cuda:                        # _check words the refusal (and says so where there is no device at all)
+        _check(name, boxes, torch.float64, (None,) * (trailing - 1) + (8,))
+        _require(False, f"{name}: a float64 device tensor [..., 8]")
+    return boxes
+
+
+def _iou_launch(a2: torch.Tensor, b2: torch.Tensor, G: int, A: int, B: int, mode: int, shape, want_parts: bool):
+    a2 = _check("a", a2.contiguous(), torch.float64, (None, 8))
+    b2 = _check("b", b2.contiguous(), torch.float64, (None, 8))
+    out = torch.empty(tuple(shape), dtype=torch.float64, device=a2.device)
+    parts = torch.empty(tuple(shape) + (2,), dtype=torch.float64, device=a2.device) if want_parts else None
+    _lib.check(_lib.load().mspa_upright_iou_device(_ptr(a2), int(a2.shape[0]), _ptr(b2), int(b2.shape[0]), G, A, B, mode, _ptr(out), _ptr(parts),
+                                                   _stream_ptr()))
+    return (out, parts) if want_parts else out
+
+
+def _pair_shapes(a_shape, b_shape):
+    """The leading shapes of two pair arguments -> the output's shape; equal, or one of them a single box."""
+    a_lead, b_lead = tuple(a_shape[:-1]), tuple(b_shape[:-1])
+    a_single, b_single = int(np.prod(a_lead)) == 1 and len(a_lead) <= 1, int(np.prod(b_lead)) == 1 and len(b_lead) <= 1
+    _require(a_lead == b_lead or a_single or b_single, f"a and b: equal leading shapes, or one of them a single box; got {list(a_shape)} and {list(b_shape)}")
+    return a_lead if a_lead == b_lead or b_single else b_lead
+
+
+def upright_iou(a: torch.Tensor, b: torch.Tensor, want_parts: bool = False):
+    """Upright boxes ``a`` [..., 8] against ``b`` [..., 8] (float64 device tensors ``[cx, cy, cz, length, width, height, ux, uy]`` with
+    equal leading shapes, or one of them a single box [8] / [1, 8] against all of the other) -> [...] float64 (device): per pair the
+    volume of the intersection over that of the union.  The rule is csrc/upright_iou_core.h's: the footprints are the rectangles
+    ``upright_corners`` draws, the one of the smaller ``length * width`` is clipped against the other by Sutherland-Hodgman in that
+    one's frame, the area is a shoelace sum, ``inter = area * dz`` with ``iou_3d``'s z overlap, and ``iou = inter / (va + vb - inter)``
+    with ``v = (length * width) * height``.  Every step is one float64 operation in the header's order, so the values are the host
+    twin's bit for bit, the same bits on every run, and ``upright_iou(a, b)`` and ``upright_iou(b, a)`` are the same bits.  A box
+    with a non-finite value (the eight NaN of an empty segment), a negative size, an axis with ``|ux^2 + uy^2 - 1| > 2^-20`` or a
+    non-zero centre or size outside [2^-200, 2^200] gives NaN, not an exception; two boxes equal in all eight values give exactly
+    1.0 (NaN with zero volume); otherwise ``0 <= iou <= 1``, or NaN where both volumes are zero.  ``want_parts`` adds [..., 2]: the
+    footprint intersection area and the z overlap.  Enqueue only: one launch on the current stream and nothing is read back.  A dtype
+    other than float64 or a last axis other than 8 raises ValueError."""
+    a, b = _iou_boxes("a", a, 1), _iou_boxes("b", b, 1)
+    shape = _pair_shapes(a.shape, b.shape)
+    return _iou_launch(a.reshape(-1, 8), b.reshape(-1, 8), 0, 0, 0, _lib.UPRIGHT_IOU_PAIRS, shape, want_parts)
+
+
+def upright_iou_matrix(a: torch.Tensor, b: torch.Tensor, want_parts: bool = False):
+    """Upright boxes ``a`` [..., A, 8] against ``b`` [..., B, 8] (float64 device tensors with equal leading shapes) -> [..., A, B]
+    float64 (device): entry (i, j) is ``upright_iou(a[..., i, :], b[..., j, :])``, bit for bit; the matrix of a set against itself
+    equals its transpose byte for byte and has 1.0 on its diagonal (NaN for a refused or zero-volume box).  ``want_parts`` adds
+    [..., A, B, 2].  Enqueue only: one launch on the current stream and nothing is read back.  The exceptions are ``upright_iou``'s."""
+    a, b = _iou_boxes("a", a, 2), _iou_boxes("b", b, 2)
+    _require(a.shape[:-2] == b.shape[:-2], f"a and b: equal leading shapes in front of [A, 8] and [B, 8]; got {list(a.shape)} and {list(b.shape)}")
+    G, A, B = int(np.prod(a.shape[:-2])), int(a.shape[-2]), int(b.shape[-2])
+    return _iou_launch(a.reshape(-1, 8), b.reshape(-1, 8), G, A, B, _lib.UPRIGHT_IOU_MATRIX, tuple(a.shape[:-2]) + (A, B), want_parts)
+
+
+def _iou_boxes_host(name: str, boxes, trailing: int) -> np.ndarray:
+    boxes = np.asarray(boxes)
+    if boxes.dtype != np.float64 or boxes.ndim < trailing or boxes.shape[-1] != 8:
+        raise ValueError(f"mspa.cloud_segments: {name}: expected float64 [..., 8], got {boxes.dtype} {list(boxes.shape)}")
+    return boxes
+
+
+def _iou_host(a2, b2, G, A, B, mode, shape, want_parts):
+    a2, b2 = np.ascontiguousarray(a2), np.ascontiguousarray(b2)
+    out = np.empty(tuple(shape), dtype=np.float64)
+    parts = np.empty(tuple(shape) + (2,), dtype=np.float64) if want_parts else None
+    _lib.check(_lib.load().mspa_upright_iou_host(a2.ctypes.data, a2.shape[0], b2.ctypes.data, b2.shape[0], G, A, B, mode, out.ctypes.data,
+                                                 parts.ctypes.data if want_parts else None))
+    return (out, parts) if want_parts else out
+
+
+def upright_iou_host(a, b, want_parts: bool = False):
+    """``upright_iou`` on the CPU for NumPy input, through the same header (mspa_upright_iou_host): NumPy arrays out, the same
+    ValueErrors.  The device's twin for tests and for input that has no device, not a fallback."""
+    a, b = _iou_boxes_host("a", a, 1), _iou_boxes_host("b", b, 1)
+    try:
+        shape = _pair_shapes(a.shape, b.shape)
+    except ValueError as e:
+        raise ValueError(str(e).replace("mspa.engine", "mspa.cloud_segments")) from None
+    return _iou_host(a.reshape(-1, 8), b.reshape(-1, 8), 0, 0, 0, _lib.UPRIGHT_IOU_PAIRS, shape, want_parts)
+
+
+def upright_iou_matrix_host(a, b, want_parts: bool = False):
+    """``upright_iou_matrix`` on the CPU for NumPy input, through the same header: NumPy arrays out, the same ValueErrors.  The
+    device's twin, not a fallback."""
+    a, b = _iou_boxes_host("a", a, 2), _iou_boxes_host("b", b, 2)
+    if a.shape[:-2] != b.shape[:-2]:
+        raise ValueError(f"mspa.cloud_segments: a and b: equal leading shapes in front of [A, 8] and [B, 8]; got {list(a.shape)} and {list(b.shape)}")
+    G, A, B = int(np.prod(a.shape[:-2])), int(a.shape[-2]), int(b.shape[-2])
+    return _iou_host(a.reshape(-1, 8), b.reshape(-1, 8), G, A, B, _lib.UPRIGHT_IOU_MATRIX, tuple(a.shape[:-2]) + (A, B), want_parts)
+
+
+def upright_iou_bound_host(a, b):
+    """Pairs ``a`` [P, 8] and ``b`` [P, 8] (NumPy float64) -> ``(area_bound [P], iou_bound [P])``: csrc/upright_iou_core.h's
+    forward-error bounds of ``upright_iou``'s footprint area and IoU against the exact rational values for the same doubles; NaN for
+    a refused pair, and an IoU bound of NaN where the IoU is."""
+    a, b = _iou_boxes_host("a", a, 2), _iou_boxes_host("b", b, 2)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise ValueError(f"mspa.cloud_segments: a and b: [P, 8] each, got {list(a.shape)} and {list(b.shape)}")
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    area, iou = np.empty((a.shape[0],)), np.empty((a.shape[0],))
+    _lib.check(_lib.load().mspa_upright_iou_bound_host(a.ctypes.data, b.ctypes.data, a.shape[0], area.ctypes.data, iou.ctypes.data))
+    return area, iou
+
+
+def upright_of_aabb(boxes6: torch.Tensor) -> torch.Tensor:
+    """``calculate_aabb`` boxes [..., 6] ``[cx, cy, cz, dx, dy, dz]`` -> the same boxes as upright ones [..., 8]: length = max(dx, dy),
+    width = min(dx, dy), height = dz, the axis (1, 0) where dx >= dy and (0, 1) where dy > dx.  A box with a NaN is eight NaN.
+    torch operations only.  Enqueue only."""
+    dx, dy = boxes6[..., 3], boxes6[..., 4]
+    turned = dy > dx
+    one, zero = torch.ones_like(dx), torch.zeros_like(dx)
+    out = torch.stack([boxes6[..., 0], boxes6[..., 1], boxes6[..., 2], torch.maximum(dx, dy), torch.minimum(dx, dy), boxes6[..., 5],
+                       torch.where(turned, zero, one), torch.where(turned, one, zero)], dim=-1)
+    return torch.where(torch.isnan(boxes6).any(dim=-1, keepdim=True), torch.full_like(out, float("nan")), out)

@@ -291,7 +291,7 @@ class SceneInfoHandler:
         return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
 
     def instance_boxes(self, scene_id, image_ids=None, nb_neighbors=20, std_ratio=1.0, per="image", device="cuda", num_workers=8,
-                       voxel_size=None, cluster=None, upright=False):
+                       voxel_size=None, cluster=None, upright=False, upright_iou=False):
         """The rest of the tool chain for every object of a scene at once: ``instance_clouds`` -> cleaned clouds
         (``remove_statistical_outliers(cloud, nb_neighbors, std_ratio)`` per segment) -> boxes (``calculate_aabb``) -> IoU against
         ``get_object_gt_bbox(scene_id, target_id, axis_aligned=True)[:6]`` (``calculate_iou_3d``), in a number of launches and
@@ -310,10 +310,15 @@ class SceneInfoHandler:
         cluster (``mspa.cloud_segments.largest_cluster_segments``): boxes, ``kept`` and IoU are taken from what is kept.
         ``upright=True`` adds the key ``upright``: [F, L, 8] or [O, 8] float64 (device), the upright minimal boxes
         ``[cx, cy, cz, length, width, height, ux, uy]`` of what is kept (``mspa.cloud_segments.upright_boxes_segments``: at most two
-        more read-backs), NaN where nothing is kept.  ``iou`` stays the axis-aligned boxes'."""
+        more read-backs), NaN where nothing is kept.  ``iou`` stays the axis-aligned boxes'.
+        ``upright_iou=True`` (with ``upright=True``; ValueError without it) adds the key ``iou_upright``: [F, L] or [O] float64
+        (device), ``mspa.cloud_segments.upright_iou`` of the upright box against ``upright_of_aabb`` of the same ground-truth box the
+        ``iou`` column uses (one more launch, no read-back); NaN where ``iou`` is NaN."""
         from mspa import cloud_segments
         if per not in ("image", "object"):
             raise ValueError(f"instance_boxes: per must be 'image' or 'object', got {per!r}")
+        if upright_iou and not upright:
+            raise ValueError("instance_boxes: upright_iou=True scores the upright boxes: it goes with upright=True")
         if per == "image" and voxel_size is not None:
             raise ValueError("instance_boxes: voxel_size goes with per='object' (a single view's cloud is already one sample per pixel)")
         clouds = self.instance_clouds(scene_id, image_ids, False, device, num_workers)
@@ -334,7 +339,10 @@ class SceneInfoHandler:
         for j, t in enumerate(targets):
             if 0 <= t < n_objects:
                 gt[j] = np.asarray(self.get_object_gt_bbox(scene_id, int(t), axis_aligned=True), dtype=np.float64)[:6]
-        out.update(boxes=boxes, kept=kept, iou=cloud_segments.iou_3d(boxes, torch.from_numpy(gt).to(boxes.device)))
+        gt_dev = torch.from_numpy(gt).to(boxes.device)
+        out.update(boxes=boxes, kept=kept, iou=cloud_segments.iou_3d(boxes, gt_dev))
+        if upright_iou:
+            out["iou_upright"] = cloud_segments.upright_iou(out["upright"], cloud_segments.upright_of_aabb(gt_dev).expand_as(out["upright"]))
         return out
 
     # ---- resident scene (what the per-scene scripts use) -----------------------------------------

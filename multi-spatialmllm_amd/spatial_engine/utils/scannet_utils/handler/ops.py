@@ -17,7 +17,8 @@ from ._images import read_color_rgb, read_depth
 __all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
            "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
 # (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample``, ``cluster_dbscan`` and
-# ``calculate_upright_box`` below are this project's own and are reached as ``ops.voxel_down_sample`` and so on)
+# ``calculate_upright_box`` and ``calculate_iou_upright`` below are this project's own and are reached as ``ops.voxel_down_sample``
+# and so on)
 
 
 def _same_device(a, b):
@@ -81,6 +82,24 @@ def calculate_iou_3d(box1, box2):
     dim = np.minimum(box1[:3] + box1[3:] / 2, box2[:3] + box2[3:] / 2) - np.maximum(box1[:3] - box1[3:] / 2, box2[:3] - box2[3:] / 2)
     inter = np.prod(dim) if np.all(dim > 0) else 0
     return inter / (np.prod(box1[3:]) + np.prod(box2[3:]) - inter)
+
+
+def calculate_iou_upright(box1, box2):
+    """Intersection over union of two upright boxes ``[cx, cy, cz, length, width, height, ux, uy]`` (``calculate_upright_box``'s):
+    where ``calculate_iou_3d`` of the axis-aligned boxes ignores the couch's own length and width, this one scores the boxes as they
+    stand.  It is the one-pair case of ``mspa.cloud_segments.upright_iou`` (rule in csrc/upright_iou_core.h: the footprints clipped by
+    Sutherland-Hodgman, every step one float64 operation), symmetric in its arguments bit for bit, the same bits on the device as on
+    the host.  NumPy in gives a Python float (the host twin of the kernel); device tensors in give a device scalar, and nothing is
+    read back.  A box the rule refuses (a non-finite value, a negative size, an axis that is no unit vector) gives NaN.  No
+    reference counterpart."""
+    from mspa import cloud_segments
+    if isinstance(box1, torch.Tensor) or isinstance(box2, torch.Tensor):
+        box1, box2 = _same_device(box1, box2)
+        if box1.is_cuda:
+            return cloud_segments.upright_iou(box1.to(torch.float64).reshape(8), box2.to(torch.float64).reshape(8))
+        box1, box2 = box1.numpy(), box2.numpy()
+    one = cloud_segments.upright_iou_host(np.asarray(box1, dtype=np.float64).reshape(8), np.asarray(box2, dtype=np.float64).reshape(8))
+    return float(one)
 
 
 def remove_statistical_outliers(point_cloud_data, nb_neighbors=20, std_ratio=1.0):
