@@ -1149,6 +1149,67 @@ int mspa_outlier_segments_host(const double *avg_host, const double *xyz_host, c
                                double *lo_host, double *hi_host);
 
 /*
+ * NEAREST-POINT DISTANCES BETWEEN THE CLOUDS OF TWO RAGGED BATCHES -- csrc/cloud_distance.hip, rule in csrc/cloud_distance_core.h on top
+ * of csrc/cloud_segments_core.h and csrc/knn_grid_core.h.  The targets are one batch (t_xyz [Nt, 3] f64, t_offsets [St + 1]), the
+ * queries another (q_xyz [Nq, 3] f64, q_offsets [Sq + 1]); pairs [P, 2] int64 names, per pair, the query segment and the target
+ * segment it is searched in (null: Sq == St == P and pair s is (s, s)); a segment may stand in any number of pairs.  The output rows
+ * lie back to back by pair: out_offsets [P + 1] with out_offsets[p + 1] - out_offsets[p] = the rows of query segment pairs[p][0], at
+ * most MSPA_CLOUD_DISTANCE_MAX_ROWS rows and MSPA_CLOUD_DISTANCE_MAX_PAIRS pairs.  Per output row: distance = sqrt(min over the target
+ * segment of (dx * dx + dy * dy) + dz * dz), index = the row of t_xyz that attains it, the lowest among equal ones; +inf and -1 for an
+ * empty target segment; NaN and -1 for a query row with a non-finite coordinate.  max_distance (finite, > 0; +inf: no cap): a row
+ * whose minimum squared distance exceeds max_distance * max_distance reports +inf and -1, every other row what it reports without a
+ * cap.  The bits are those of a brute force over all rows.  Every device entry point takes each host table TWICE, as the entries
+ * above do, and checks all arguments before it enqueues anything; zero output rows enqueue nothing.
+ *   mspa_knn_segments_index_device   the search structure of a batch, in caller-owned buffers: pts_dev [N, 3] (the rows by key),
+ *                                    sorted_keys_dev [N] and starts_dev [starts_slots] int32, starts_slots >= the batch's cell_base[S] +
+ *                                    S.  order_dev is the stable sort of mspa_knn_segments_cells_device's keys; the grids are
+ *                                    mspa_knn_segments_grids_host's for k.  The gather and the starts launches of
+ *                                    mspa_knn_segments_mean_distance_device, nothing else.
+ *   mspa_cloud_distance_device       -> distance_dev [M] f64 and, where not null, index_dev [M] int64 and evals_dev [M] int32 (the
+ *                                    distances each row evaluated).  t_pts_dev, t_starts_dev [t_starts_slots], t_order_dev: an index built with grid_k
+ *                                    (MSPA_CLOUD_DISTANCE_GRID_K is the library's choice; results do not depend on it).  MSPA_EINVAL
+ *                                    for a null pointer where a count is positive, bad offsets, a pair outside [0, Sq) x [0, St),
+ *                                    out_offsets that do not follow from the pairs, grids that are not grids_host's, a cap outside
+ *                                    its domain or a misaligned buffer.  Every device table entry a lane indexes with is clamped:
+ *                                    corrupt device tables give wrong distances, never an access outside the buffers.
+ *                                    perm_dev [M] (null: lane i takes output row i): a permutation of the output rows, the sort
+ *                                    of mspa_cloud_distance_keys_device's keys; it decides which lane computes a row, never what the
+ *                                    row holds.  Its entries are clamped into [0, M).
+ *   mspa_cloud_distance_keys_device  -> keys_dev [M] int64: (pair << 31) + the query row's cell in its target segment's grid.
+ *   mspa_cloud_distance_fit_device   distance_dev [M], out_offsets [P + 1] -> per pair rows_dev, finite_dev (d < inf), within_dev
+ *                                    (d <= tau; tau finite, >= 0) [P] int64 and sum_dev, sum_sq_dev (of d and d * d over the finite
+ *                                    rows, in the order csrc/cloud_segments_core.h states: 256 lane sums folded by halving strides),
+ *                                    max_dev (the largest finite d, -inf where none) [P] f64.  One workgroup per pair, no atomics.
+ *   mspa_cloud_distance_host,
+ *   mspa_cloud_distance_fit_host     the same two steps on the CPU through the same headers, from the unsorted targets: the device's
+ *                                    twins for tests on a machine without a GPU, not a fallback.
+ */
+#define MSPA_CLOUD_DISTANCE_MAX_ROWS (1 << 30)
+#define MSPA_CLOUD_DISTANCE_MAX_PAIRS (1 << 24)
+#define MSPA_CLOUD_DISTANCE_GRID_K 1
+int mspa_knn_segments_index_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, int32_t k, const void *grids_host,
+                                   const int64_t *offsets_dev, const void *grids_dev, const int64_t *cell_base_dev, const int64_t *order_dev,
+                                   double *pts_dev, int64_t *sorted_keys_dev, int32_t *starts_dev, int64_t starts_slots, mspa_stream_t stream);
+int mspa_cloud_distance_device(const double *t_pts_dev, const int32_t *t_starts_dev, int64_t t_starts_slots, const int64_t *t_order_dev,
+                               const int64_t *t_offsets_host, int64_t St, int32_t grid_k, const void *grids_host, const int64_t *t_offsets_dev, const void *grids_dev,
+                               const int64_t *cell_base_dev, const double *q_xyz_dev, const int64_t *q_offsets_host, int64_t Sq,
+                               const int64_t *q_offsets_dev, const int64_t *pairs_host, const int64_t *pairs_dev, int64_t P,
+                               const int64_t *out_offsets_host, const int64_t *out_offsets_dev, const int64_t *perm_dev, double max_distance,
+                               double *distance_dev, int64_t *index_dev, int32_t *evals_dev, mspa_stream_t stream);
+int mspa_cloud_distance_keys_device(const int64_t *t_offsets_host, int64_t St, int32_t grid_k, const void *grids_host, const void *grids_dev,
+                                    const double *q_xyz_dev, const int64_t *q_offsets_host, int64_t Sq, const int64_t *q_offsets_dev,
+                                    const int64_t *pairs_host, const int64_t *pairs_dev, int64_t P, const int64_t *out_offsets_host,
+                                    const int64_t *out_offsets_dev, int64_t *keys_dev, mspa_stream_t stream);
+int mspa_cloud_distance_fit_device(const double *distance_dev, const int64_t *out_offsets_host, int64_t P, double tau,
+                                   const int64_t *out_offsets_dev, int64_t *rows_dev, int64_t *finite_dev, int64_t *within_dev, double *sum_dev,
+                                   double *sum_sq_dev, double *max_dev, mspa_stream_t stream);
+int mspa_cloud_distance_host(const double *t_xyz_host, const int64_t *t_offsets_host, int64_t St, int32_t grid_k, const double *q_xyz_host,
+                             const int64_t *q_offsets_host, int64_t Sq, const int64_t *pairs_host, int64_t P, const int64_t *out_offsets_host,
+                             double max_distance, double *distance_host, int64_t *index_host, int32_t *evals_host);
+int mspa_cloud_distance_fit_host(const double *distance_host, const int64_t *out_offsets_host, int64_t P, double tau, int64_t *rows_host,
+                                 int64_t *finite_host, int64_t *within_host, double *sum_host, double *sum_sq_host, double *max_host);
+
+/*
  * Instance-mask decode ON THE DEVICE (csrc/mask_ingest.hip, rule in csrc/png_unfilter8_core.h): the 8-bit twin of the depth-frame
  * decode above, for ScanNet's `instance-filt/<image>.png` label images (`cv2.imread(path, -1)` per (image, object) in the
  * reference's get_instance_mask).  The inflate in front of the un-filter is mspa_inflate_blocks_device with block_bytes = h * (w + 1).

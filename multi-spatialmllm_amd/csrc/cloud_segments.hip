@@ -15,6 +15,8 @@
 //      several segments.  The k best squared distances are an ascending list in LDS, interleaved by lane, as in knn_kernel.
 //   5. seg_stats_kernel  -- one workgroup of 256 per segment, three passes over its avg: sum -> mean, squared deviations -> sd and
 //      thr, keep flags with the kept count and the kept rows' extents.  No atomics: lane sums, then folds through LDS.
+// Kernels 2 and 3 alone, into caller-owned buffers, are mspa_knn_segments_index_device: the search structure csrc/cloud_distance.hip
+// queries from another batch.
 #include "mspa_common.h"
 #include "segments_device.h"
 
@@ -222,6 +224,47 @@ extern "C" int mspa_knn_segments_cells_device(const double *xyz_dev, const int64
     return check_hip(hipGetLastError(), "mspa_knn_segments_cells_device");
 }
 
+// The slots of a batch's table of starts: one more than its cells per segment, also for an empty one.
+static int64_t index_slots(const int64_t *offsets_host, int64_t S, int32_t k) {
+    int64_t slots = S;
+    for (int64_t s = 0; s < S; ++s)
+        if (offsets_host[s + 1] > offsets_host[s]) slots += knn::max_cells(offsets_host[s + 1] - offsets_host[s], k);
+    return slots;
+}
+
+// The gather and the starts of a sorted batch of N >= 1 rows: the two launches every search of a batch is built on.
+static void launch_index(const double *xyz_dev, int64_t N, int64_t S, int64_t slots, const int64_t *offsets_dev, const knn::Grid *grids,
+                         const int64_t *cell_base_dev, const int64_t *order_dev, double *pts, int64_t *sorted_keys, int32_t *starts,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(segs::seg_gather_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, xyz_dev, offsets_dev, S, grids, cell_base_dev,
+                       order_dev, pts, sorted_keys);
+    hipLaunchKernelGGL(segs::seg_starts_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const int64_t *)sorted_keys, offsets_dev,
+                       S, grids, cell_base_dev, starts);
+}
+
+extern "C" int mspa_knn_segments_index_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, int32_t k, const void *grids_host,
+                                              const int64_t *offsets_dev, const void *grids_dev, const int64_t *cell_base_dev,
+                                              const int64_t *order_dev, double *pts_dev, int64_t *sorted_keys_dev, int32_t *starts_dev,
+                                              int64_t starts_slots, void *stream) {
+    const char *who = "mspa_knn_segments_index_device";
+    if (k < 1 || k > knn::kMaxK) return fail(MSPA_EINVAL, std::string(who) + ": k outside [1, 64]");
+    const int64_t N = segs::checked_rows(who, offsets_host, S);
+    if (N < 0) return MSPA_EINVAL;
+    if (N == 0) return MSPA_OK;
+    if (!xyz_dev || !grids_host || !offsets_dev || !grids_dev || !cell_base_dev || !order_dev || !pts_dev || !sorted_keys_dev || !starts_dev)
+        return fail(MSPA_EINVAL, std::string(who) + ": null pointer");
+    if (!segs::grids_ok((const knn::Grid *)grids_host, offsets_host, S, k))
+        return fail(MSPA_EINVAL, std::string(who) + ": not the grids of mspa_knn_segments_grids_host for these offsets and k");
+    const int64_t slots = index_slots(offsets_host, S, k);
+    if (starts_slots < slots) return fail(MSPA_EINVAL, std::string(who) + ": starts_dev holds fewer slots than the batch's cells plus S");
+    if (segs::misaligned(xyz_dev, 8) || segs::misaligned(pts_dev, 8) || segs::misaligned(sorted_keys_dev, 8) || segs::misaligned(order_dev, 8) ||
+        segs::misaligned(starts_dev, 4))
+        return fail(MSPA_EINVAL, std::string(who) + ": a buffer is not aligned to its element");
+    launch_index(xyz_dev, N, S, slots, offsets_dev, (const knn::Grid *)grids_dev, cell_base_dev, order_dev, pts_dev, sorted_keys_dev, starts_dev,
+                 (hipStream_t)stream);
+    return check_hip(hipGetLastError(), who);
+}
+
 extern "C" int mspa_knn_segments_mean_distance_device(const double *xyz_dev, const int64_t *offsets_host, int64_t S, int32_t k,
                                                       const void *grids_host, const int64_t *offsets_dev, const void *grids_dev,
                                                       const int64_t *cell_base_dev, const int64_t *order_dev, double *mean_dev,
@@ -237,18 +280,13 @@ extern "C" int mspa_knn_segments_mean_distance_device(const double *xyz_dev, con
     if (workspace_bytes < mspa_knn_segments_workspace_bytes(offsets_host, S, k))
         return fail(MSPA_EINVAL, "mspa_knn_segments_mean_distance_device: workspace smaller than mspa_knn_segments_workspace_bytes()");
     if ((uintptr_t)workspace & 15u) return fail(MSPA_EINVAL, "mspa_knn_segments_mean_distance_device: workspace must be 16-byte aligned");
-    int64_t slots = S;
-    for (int64_t s = 0; s < S; ++s)
-        if (offsets_host[s + 1] > offsets_host[s]) slots += knn::max_cells(offsets_host[s + 1] - offsets_host[s], k);
+    const int64_t slots = index_slots(offsets_host, S, k);
     hipStream_t st = (hipStream_t)stream;
     const knn::Grid *grids = (const knn::Grid *)grids_dev;
     double *pts = (double *)workspace;
     int64_t *sorted_keys = (int64_t *)((uint8_t *)workspace + align16(N * 24));
     int32_t *starts = (int32_t *)((uint8_t *)sorted_keys + align16(N * 8));
-    hipLaunchKernelGGL(segs::seg_gather_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, xyz_dev, offsets_dev, S, grids, cell_base_dev,
-                       order_dev, pts, sorted_keys);
-    hipLaunchKernelGGL(segs::seg_starts_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, (const int64_t *)sorted_keys, offsets_dev,
-                       S, grids, cell_base_dev, starts);
+    launch_index(xyz_dev, N, S, slots, offsets_dev, grids, cell_base_dev, order_dev, pts, sorted_keys, starts, st);
     hipLaunchKernelGGL(segs::seg_knn_kernel, dim3((unsigned)((N + kWave - 1) / kWave)), dim3(kWave), (size_t)k * kWave * sizeof(double), st,
                        (const double *)pts, (const int32_t *)starts, offsets_dev, S, grids, cell_base_dev, order_dev, k, mean_dev, evals_dev);
     return check_hip(hipGetLastError(), "mspa_knn_segments_mean_distance_device");

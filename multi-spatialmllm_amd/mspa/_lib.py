@@ -21,6 +21,7 @@ KNN_GRID_BYTES, KNN_MAX_K = 112, 64      # csrc/knn_grid_core.h: sizeof(Grid), k
 SEGMENTS_MAX = 1 << 24                   # csrc/cloud_segments_core.h: kMaxSegments
 VOXEL_AXIS_BITS, VOXEL_MAX_COLUMNS = 21, 65536   # csrc/voxel_grid_core.h: kAxisBits; include/mspa.h: MSPA_VOXEL_MAX_COLUMNS
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3     # Pillow's Image.Resampling numbers
+CLOUD_DISTANCE_GRID_K, CLOUD_DISTANCE_MAX_ROWS, CLOUD_DISTANCE_MAX_PAIRS = 1, 1 << 30, 1 << 24   # csrc/cloud_distance_core.h
 UPRIGHT_IOU_PAIRS, UPRIGHT_IOU_MATRIX = 0, 1   # include/mspa.h: the two launch shapes of mspa_upright_iou_device
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
@@ -267,6 +268,18 @@ _SIGNATURES = {
     "mspa_upright_iou_device": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "mspa_upright_iou_host": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "mspa_upright_iou_bound_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mspa_knn_segments_index_device": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int64, c_void_p]),
+    "mspa_cloud_distance_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_cloud_distance_keys_device": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_cloud_distance_fit_device": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    "mspa_cloud_distance_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_double,
+                                         c_void_p, c_void_p, c_void_p]),
+    "mspa_cloud_distance_fit_host": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

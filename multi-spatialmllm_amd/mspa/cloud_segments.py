@@ -16,6 +16,9 @@ as scikit-learn's DBSCAN does and keep its largest cluster.  ``footprint_hull_se
 (csrc/upright_segments.hip, rule in csrc/upright_box_core.h) give every segment the exact convex hull of its (x, y) footprint and
 its upright minimal box: the z extent times the minimum-area rectangle around that hull.  ``upright_iou`` / ``upright_iou_matrix``
 (csrc/upright_iou.hip, rule in csrc/upright_iou_core.h) score such boxes against each other, pair by pair or set against set.
+``target_index`` / ``TargetIndex.nearest`` / ``fit_segments`` / ``cloud_fit_segments`` (csrc/cloud_distance.hip, rule in
+csrc/cloud_distance_core.h) compare the clouds of one batch with those of another: per row the distance to, and the row of, the nearest
+point of the segment its pair names, and a per-pair summary of those distances.
 """
 from __future__ import annotations
 
@@ -763,3 +766,243 @@ def upright_of_aabb(boxes6: torch.Tensor) -> torch.Tensor:
     out = torch.stack([boxes6[..., 0], boxes6[..., 1], boxes6[..., 2], torch.maximum(dx, dy), torch.minimum(dx, dy), boxes6[..., 5],
                        torch.where(turned, zero, one), torch.where(turned, one, zero)], dim=-1)
     return torch.where(torch.isnan(boxes6).any(dim=-1, keepdim=True), torch.full_like(out, float("nan")), out)
+
+
+# ---- nearest-point distances between the clouds of two batches (csrc/cloud_distance.hip, rule in csrc/cloud_distance_core.h) ------------
+
+FIT_KEYS = ("rows", "finite", "within", "sum", "sum_sq", "max")
+ORDER_QUERIES = True                              # TargetIndex.nearest: lanes take the output rows in the order of their cells (measured)
+
+
+def _grid_k_of(_grid_k) -> int:
+    return _lib.CLOUD_DISTANCE_GRID_K if _grid_k is None else _knn_check(_grid_k)
+
+
+def _cap_of(max_distance) -> float:
+    """``max_distance`` (None: no cap) -> what the entry points take: finite and > 0, or +inf for none."""
+    if max_distance is None:
+        return float("inf")
+    cap = float(max_distance)
+    _require(0.0 < cap < float("inf"), f"max_distance: finite and > 0, got {max_distance}")
+    return cap
+
+
+def _tau_of(tau) -> float:
+    tau = float(tau)
+    _require(0.0 <= tau < float("inf"), f"tau: finite and >= 0, got {tau}")
+    return tau
+
+
+def _pair_tables(q_off: np.ndarray, St: int, pairs):
+    """``(pairs [P, 2] host int64, out_offsets [P + 1] host int64)`` of a query batch's offsets, the number of target segments and a
+    caller's pair table (None: pair s is (s, s), which needs as many segments on either side)."""
+    Sq = q_off.size - 1
+    if pairs is None:
+        _require(Sq == St, f"pairs: none needs as many query segments as target segments, got {Sq} and {St}")
+        pairs = np.repeat(np.arange(Sq, dtype=np.int64), 2).reshape(Sq, 2)
+    else:
+        if isinstance(pairs, torch.Tensor):
+            _require(not pairs.is_cuda, "pairs: a host array (the launch shapes come from it)")
+            pairs = pairs.numpy()
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2) if np.size(pairs) == 0 else np.ascontiguousarray(pairs, dtype=np.int64)
+        _require(pairs.ndim == 2 and pairs.shape[1] == 2, f"pairs: [P, 2], got {list(pairs.shape)}")
+        _require(pairs.shape[0] <= _lib.CLOUD_DISTANCE_MAX_PAIRS, f"pairs: at most 2^24 pairs, got {pairs.shape[0]}")
+        _require(bool(((pairs >= 0) & (pairs < np.array([Sq, St]))).all()),
+                 f"pairs: (query segment, target segment) inside [0, {Sq}) x [0, {St})")
+    out_offsets = _offsets_of(np.diff(q_off)[pairs[:, 0]])
+    _require(int(out_offsets[-1]) <= _lib.CLOUD_DISTANCE_MAX_ROWS, f"pairs: at most 2^30 output rows, got {int(out_offsets[-1])}")
+    return pairs, out_offsets
+
+
+def _xyz_of(name: str, rows) -> torch.Tensor:
+    _require(isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[1] >= 3, f"{name}: a device tensor [N, C >= 3]")
+    return _check(name, rows[:, :3].to(torch.float64).contiguous(), torch.float64, (None, 3))
+
+
+class TargetIndex:
+    """The search structure of a batch of target clouds on the device (``target_index``): the rows sorted by grid cell per segment
+    (``pts`` [N, 3] float64), their original rows (``order`` [N] int64), the first sorted row of every cell (``starts`` int32), the
+    grid records and the offsets -- on the device, with the host copies the entry points check.  Build it once, query it any number
+    of times."""
+
+    def __init__(self, offsets, grid_k, grids, off_dev, grids_dev, base_dev, pts, order, starts, device):
+        self.offsets, self.grid_k, self.grids, self.device = offsets, grid_k, grids, device
+        self.off_dev, self.grids_dev, self.base_dev, self.pts, self.order, self.starts = off_dev, grids_dev, base_dev, pts, order, starts
+
+    def nearest(self, queries: torch.Tensor, q_offsets, pairs=None, max_distance=None, want_index: bool = True, want_evals: bool = False,
+                _ordered=None) -> dict:
+        """A batch ``queries`` [Nq, C >= 3] (device; xyz in front, float64 or a dtype that widens to it exactly) with host ``q_offsets``
+        [Sq + 1] and a host pair table ``pairs`` [P, 2] int64 -- pair p searches the rows of query segment ``pairs[p, 0]`` in target
+        segment ``pairs[p, 1]``; None: pair s is (s, s) -- -> a dict: ``distance`` [M] float64 (device), per output row the distance to
+        the nearest row of the pair's target segment; ``index`` [M] int64 (device; with ``want_index``), that row's index into the
+        targets the index was built from, the lowest among equally near ones; ``offsets`` [P + 1] host int64, the output rows of pair
+        p are ``offsets[p]:offsets[p + 1]``, as many as the query segment has; ``evals`` [M] int32 (with ``want_evals``), the distances
+        each row evaluated.  The rule is csrc/cloud_distance_core.h's: ``d2 = (dx*dx + dy*dy) + dz*dz`` in float64 and
+        ``distance = sqrt(min d2)``, the bits of a brute force over all rows; an empty target segment gives +inf and -1, a query row
+        with a non-finite coordinate NaN and -1 (no exception); with ``max_distance`` (finite, > 0) a row farther than that gives +inf
+        and -1 and every other row is unchanged -- without it a query far from its target walks the target's whole grid.  The lanes
+        take the output rows in the order of their cell in the target's grid (a keys pass and one ``torch.sort`` in front of the
+        search; ``_ordered=False``: in input order); the outputs are the same bytes either way.  Enqueue only: the keys pass, the sort
+        and the search on the current stream, the host tables go up through pinned memory and nothing is read back."""
+        xyz = _xyz_of("queries", queries)
+        q_off = _offsets(q_offsets, int(xyz.shape[0]))
+        St = self.offsets.size - 1
+        pairs, out_offsets = _pair_tables(q_off, St, pairs)
+        cap = _cap_of(max_distance)
+        P, M, dev = pairs.shape[0], int(out_offsets[-1]), self.device
+        _require(xyz.device == dev, f"queries: on the index's device {dev}, got {xyz.device}")
+        out = {"distance": torch.empty((M,), dtype=torch.float64, device=dev), "offsets": out_offsets}
+        if want_index:
+            out["index"] = torch.empty((M,), dtype=torch.int64, device=dev)
+        if want_evals:
+            out["evals"] = torch.empty((M,), dtype=torch.int32, device=dev)
+        if M:
+            lib = _lib.load()
+            q_dev, pairs_dev, out_dev = _upload(q_off, pairs, out_offsets, device=dev)
+            perm = None
+            if ORDER_QUERIES if _ordered is None else _ordered:             # lanes of a wave then walk neighbouring cells: the same bytes out
+                keys = torch.empty((M,), dtype=torch.int64, device=dev)
+                _lib.check(lib.mspa_cloud_distance_keys_device(self.offsets.ctypes.data, St, self.grid_k, self.grids.ctypes.data, _ptr(self.grids_dev),
+                                                               _ptr(xyz), q_off.ctypes.data, q_off.size - 1, _ptr(q_dev), pairs.ctypes.data,
+                                                               _ptr(pairs_dev), P, out_offsets.ctypes.data, _ptr(out_dev), _ptr(keys), _stream_ptr()))
+                perm = torch.sort(keys).indices
+            _lib.check(lib.mspa_cloud_distance_device(
+                _ptr(self.pts), _ptr(self.starts), int(self.starts.numel()), _ptr(self.order), self.offsets.ctypes.data, St, self.grid_k, self.grids.ctypes.data,
+                _ptr(self.off_dev), _ptr(self.grids_dev), _ptr(self.base_dev), _ptr(xyz), q_off.ctypes.data, q_off.size - 1, _ptr(q_dev),
+                pairs.ctypes.data, _ptr(pairs_dev), P, out_offsets.ctypes.data, _ptr(out_dev), _ptr(perm), cap, _ptr(out["distance"]), _ptr(out.get("index")),
+                _ptr(out.get("evals")), _stream_ptr()))
+        return out
+
+
+def target_index(targets: torch.Tensor, offsets, _grid_k=None) -> TargetIndex:
+    """A batch ``targets`` [N, C >= 3] (device; xyz in front, float64 or a dtype that widens to it exactly) with host ``offsets``
+    [S + 1] -> its ``TargetIndex``: per segment the grid ``knn_mean_distance_segments`` builds (the box of the per-axis order
+    statistics of rank n_s // 100 and n_s - 1 - n_s // 100), the rows sorted by cell with ONE sort of the whole batch, and the first
+    sorted row of every cell.  One read-back per call, whatever S is: the boxes of all segments with the flag that every coordinate
+    is finite (``knn_mean_distance_segments``'); non-finite coordinates raise its ValueError.  ``_grid_k`` sizes the cells; results
+    do not depend on it."""
+    xyz = _xyz_of("targets", targets)
+    N, dev = int(xyz.shape[0]), xyz.device
+    off = _offsets(offsets, N)
+    _require(N <= 1 << 30, f"targets: at most 2^30 rows, got {N}")
+    k, S = _grid_k_of(_grid_k), off.size - 1
+    lib = _lib.load()
+    cell_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_knn_segments_tables_host(off.ctypes.data, S, k, cell_base.ctypes.data))
+    slots = int(cell_base[S]) + S
+    starts = torch.zeros((max(slots, 1),), dtype=torch.int32, device=dev)      # the slots behind a segment's cells are never written
+    pts = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    if N == 0:
+        grids = np.zeros((S, _lib.KNN_GRID_BYTES), dtype=np.uint8)
+        off_dev, grids_dev, base_dev = _upload(off, grids, cell_base, device=dev)
+        return TargetIndex(off, k, grids, off_dev, grids_dev, base_dev, pts, torch.empty((0,), dtype=torch.int64, device=dev), starts, dev)
+    grids, off_dev, grids_dev, base_dev = _search_tables(xyz, off, k)
+    keys = torch.empty((N,), dtype=torch.int64, device=dev)
+    _lib.check(lib.mspa_knn_segments_cells_device(_ptr(xyz), off.ctypes.data, S, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev),
+                                                  _ptr(base_dev), _ptr(keys), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    _lib.check(lib.mspa_knn_segments_index_device(_ptr(xyz), off.ctypes.data, S, k, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev), _ptr(base_dev),
+                                                  _ptr(order), _ptr(pts), _ptr(keys), _ptr(starts), int(starts.numel()), _stream_ptr()))
+    return TargetIndex(off, k, grids, off_dev, grids_dev, base_dev, pts, order, starts, dev)
+
+
+def nearest_segments(queries: torch.Tensor, q_offsets, targets: torch.Tensor, t_offsets, pairs=None, max_distance=None, want_index: bool = True,
+                     want_evals: bool = False, _grid_k=None) -> dict:
+    """``target_index(targets, t_offsets).nearest(queries, q_offsets, ...)``: per row of a query segment the distance to, and the row
+    of, the nearest point of the target segment its pair names.  ``target_index``' one read-back and its ValueError."""
+    return target_index(targets, t_offsets, _grid_k).nearest(queries, q_offsets, pairs, max_distance, want_index, want_evals)
+
+
+def fit_segments(distance: torch.Tensor, offsets, tau) -> dict:
+    """``distance`` [M] float64 (device; ``TargetIndex.nearest``'s) with its host ``offsets`` [P + 1] and a threshold ``tau`` (finite,
+    >= 0) -> a dict of six device tensors [P]: ``rows`` int64, the rows of the pair; ``finite`` int64, those with d < inf; ``within``
+    int64, those with d <= tau (NaN counts nowhere); ``sum`` and ``sum_sq`` float64, the sums of d and of d * d over the finite rows
+    in the order csrc/cloud_segments_core.h states (256 lane sums folded by halving strides; not ``torch.sum``'s); ``max`` float64,
+    the largest finite d, -inf where there is none.  Means and shares are one division each and left to the caller.  Enqueue only:
+    one launch on the current stream, the offsets go up through pinned memory and nothing is read back."""
+    M = _check("distance", distance, torch.float64, (None,)).shape[0]
+    off = _offsets(offsets, M)
+    tau = _tau_of(tau)
+    P, dev = off.size - 1, distance.device
+    out = {name: torch.empty((P,), dtype=torch.int64 if name in FIT_KEYS[:3] else torch.float64, device=dev) for name in FIT_KEYS}
+    if P:
+        off_dev, = _upload(off, device=dev)
+        _lib.check(_lib.load().mspa_cloud_distance_fit_device(_ptr(distance), off.ctypes.data, P, tau, _ptr(off_dev),
+                                                              *(_ptr(out[name]) for name in FIT_KEYS), _stream_ptr()))
+    return out
+
+
+def cloud_fit_segments(a: torch.Tensor, a_offsets, b: torch.Tensor, b_offsets, tau, max_distance=None) -> dict:
+    """Two batches of as many segments, segment s of ``a`` against segment s of ``b``, in both directions -> a dict: ``a_to_b`` and
+    ``b_to_a``, the ``fit_segments`` summaries of ``a``'s rows searched in ``b`` and of ``b``'s rows searched in ``a``, and four
+    float64 device tensors [S] as torch expressions of the two: ``precision`` = within / rows of a_to_b, ``recall`` = within / rows of
+    b_to_a, ``fscore`` = 2 precision recall / (precision + recall) (0 where both are 0), ``chamfer`` = sum / finite of a_to_b plus
+    sum / finite of b_to_a, the two mean nearest distances.  NaN where a side is empty.  Two read-backs: one ``target_index`` per
+    side."""
+    tau = _tau_of(tau)
+    ab = nearest_segments(a, a_offsets, b, b_offsets, None, max_distance, want_index=False)
+    ba = nearest_segments(b, b_offsets, a, a_offsets, None, max_distance, want_index=False)
+    out = {"a_to_b": fit_segments(ab["distance"], ab["offsets"], tau), "b_to_a": fit_segments(ba["distance"], ba["offsets"], tau)}
+    out.update(_fit_scores(out["a_to_b"], out["b_to_a"], torch))
+    return out
+
+
+def _fit_scores(ab: dict, ba: dict, xp) -> dict:
+    """precision, recall, fscore and chamfer of two summaries, with ``xp`` torch or NumPy (the same float64 operations)."""
+    as_f64 = (lambda t: t.to(torch.float64)) if xp is torch else (lambda t: t.astype(np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision, recall = as_f64(ab["within"]) / as_f64(ab["rows"]), as_f64(ba["within"]) / as_f64(ba["rows"])
+        both = precision + recall
+        fscore = xp.where(both == 0, both, (2 * precision * recall) / both)
+        chamfer = ab["sum"] / as_f64(ab["finite"]) + ba["sum"] / as_f64(ba["finite"])
+    return {"precision": precision, "recall": recall, "fscore": fscore, "chamfer": chamfer}
+
+
+def nearest_segments_host(queries, q_offsets, targets, t_offsets, pairs=None, max_distance=None, want_evals: bool = False, _grid_k=None) -> dict:
+    """``nearest_segments`` on the CPU for NumPy input, through the same headers (mspa_cloud_distance_host): NumPy arrays out
+    (``distance``, ``index``, ``offsets`` and, when wanted, ``evals``).  Non-finite targets raise ValueError.  The device's twin for
+    tests and for input that has no device, not a fallback."""
+    sides = []
+    for name, rows in (("queries", queries), ("targets", targets)):
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] < 3:
+            raise ValueError(f"mspa.cloud_segments: {name}: expected [N, C >= 3], got {list(rows.shape)}")
+        sides.append(np.ascontiguousarray(rows[:, :3], dtype=np.float64))
+    q, t = sides
+    q_off, t_off = _offsets(q_offsets, q.shape[0]), _offsets(t_offsets, t.shape[0])
+    if not np.isfinite(t).all():
+        raise ValueError("mspa.cloud_segments: requirement not met: xyz: finite coordinates")
+    pairs, out_offsets = _pair_tables(q_off, t_off.size - 1, pairs)
+    cap, k = _cap_of(max_distance), _grid_k_of(_grid_k)
+    M = int(out_offsets[-1])
+    out = {"distance": np.empty((M,), dtype=np.float64), "index": np.empty((M,), dtype=np.int64), "offsets": out_offsets}
+    if want_evals:
+        out["evals"] = np.empty((M,), dtype=np.int32)
+    _lib.check(_lib.load().mspa_cloud_distance_host(t.ctypes.data, t_off.ctypes.data, t_off.size - 1, k, q.ctypes.data, q_off.ctypes.data,
+                                                    q_off.size - 1, pairs.ctypes.data, pairs.shape[0], out_offsets.ctypes.data, cap,
+                                                    out["distance"].ctypes.data, out["index"].ctypes.data,
+                                                    out["evals"].ctypes.data if want_evals else None))
+    return out
+
+
+def fit_segments_host(distance, offsets, tau) -> dict:
+    """``fit_segments`` on the CPU for NumPy input, through the same headers (mspa_cloud_distance_fit_host): the same six keys, NumPy
+    arrays.  The device's twin, not a fallback."""
+    distance = np.ascontiguousarray(distance, dtype=np.float64)
+    if distance.ndim != 1:
+        raise ValueError(f"mspa.cloud_segments: distance: expected [M], got {list(distance.shape)}")
+    off = _offsets(offsets, distance.shape[0])
+    tau = _tau_of(tau)
+    P = off.size - 1
+    out = {name: np.zeros((P,), dtype=np.int64 if name in FIT_KEYS[:3] else np.float64) for name in FIT_KEYS}
+    _lib.check(_lib.load().mspa_cloud_distance_fit_host(distance.ctypes.data, off.ctypes.data, P, tau, *(out[name].ctypes.data for name in FIT_KEYS)))
+    return out
+
+
+def cloud_fit_segments_host(a, a_offsets, b, b_offsets, tau, max_distance=None) -> dict:
+    """``cloud_fit_segments`` over the host twins, NumPy in and out: for tests on a machine without a GPU."""
+    ab = nearest_segments_host(a, a_offsets, b, b_offsets, None, max_distance)
+    ba = nearest_segments_host(b, b_offsets, a, a_offsets, None, max_distance)
+    out = {"a_to_b": fit_segments_host(ab["distance"], ab["offsets"], tau), "b_to_a": fit_segments_host(ba["distance"], ba["offsets"], tau)}
+    out.update(_fit_scores(out["a_to_b"], out["b_to_a"], np))
+    return out

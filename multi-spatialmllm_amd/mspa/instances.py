@@ -150,6 +150,31 @@ class InstanceClouds:
             rows, offsets, _counts = cloud_segments.voxel_down_sample_segments(rows, offsets, voxel_size)
         return rows, offsets, object_ids
 
+    def view_coverage(self, tau, voxel_size=None) -> torch.Tensor:
+        """[F, L] float64 on the device: for every (image, label) with rows, the share of that object's fused cloud
+        (``by_object(voxel_size)``) that lies within ``tau`` of this image's cloud of the object -- how much of the object the frame
+        shows; NaN where the segment is empty.  One index over the per-image batch (``cloud_segments.target_index``: one read-back,
+        its ValueError), one pair table (object run, image segment), one query with ``max_distance=tau`` -- a frame that misses the
+        object walks a bounded block -- and one summary (``cloud_segments.fit_segments``).  ``tau`` finite and > 0.  It needs the
+        rows on the device."""
+        from . import cloud_segments
+        F, L = self.counts.shape
+        fused, fused_offsets, object_ids = self.by_object(voxel_size)
+        frames, labels = np.nonzero(self.counts[:, 1:] if L > 1 else self.counts[:, :0])
+        labels = labels + 1
+        run_of = np.full((L,), -1, dtype=np.int64)
+        run_of[np.asarray(object_ids, dtype=np.int64) + 1] = np.arange(len(object_ids), dtype=np.int64)
+        pairs = np.stack([run_of[labels], frames.astype(np.int64) * L + labels], axis=1).astype(np.int64)
+        out = torch.full((F * L,), float("nan"), dtype=torch.float64, device=self.rows.device)
+        if len(pairs) == 0:
+            return out.reshape(F, L)
+        index = cloud_segments.target_index(self.rows, self.offsets)
+        found = index.nearest(fused, fused_offsets, pairs, max_distance=tau, want_index=False)
+        fit = cloud_segments.fit_segments(found["distance"], found["offsets"], tau)
+        where, = cloud_segments._upload(pairs[:, 1].copy(), device=self.rows.device)
+        out[where] = fit["within"].to(torch.float64) / fit["rows"].to(torch.float64)
+        return out.reshape(F, L)
+
     def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None, cluster=None, upright=False):
         """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
         ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``

@@ -291,7 +291,7 @@ class SceneInfoHandler:
         return instances.build(self, scene_id, image_ids, with_color, device, num_workers, max_dense_bytes, images=_images)
 
     def instance_boxes(self, scene_id, image_ids=None, nb_neighbors=20, std_ratio=1.0, per="image", device="cuda", num_workers=8,
-                       voxel_size=None, cluster=None, upright=False, upright_iou=False):
+                       voxel_size=None, cluster=None, upright=False, upright_iou=False, coverage=None):
         """The rest of the tool chain for every object of a scene at once: ``instance_clouds`` -> cleaned clouds
         (``remove_statistical_outliers(cloud, nb_neighbors, std_ratio)`` per segment) -> boxes (``calculate_aabb``) -> IoU against
         ``get_object_gt_bbox(scene_id, target_id, axis_aligned=True)[:6]`` (``calculate_iou_3d``), in a number of launches and
@@ -313,12 +313,18 @@ class SceneInfoHandler:
         more read-backs), NaN where nothing is kept.  ``iou`` stays the axis-aligned boxes'.
         ``upright_iou=True`` (with ``upright=True``; ValueError without it) adds the key ``iou_upright``: [F, L] or [O] float64
         (device), ``mspa.cloud_segments.upright_iou`` of the upright box against ``upright_of_aabb`` of the same ground-truth box the
-        ``iou`` column uses (one more launch, no read-back); NaN where ``iou`` is NaN."""
+        ``iou`` column uses (one more launch, no read-back); NaN where ``iou`` is NaN.
+        ``coverage=(tau, voxel_size)`` (with ``per="image"``; ValueError with ``per="object"``) adds the key ``coverage``: [F, L]
+        float64 (device), ``InstanceClouds.view_coverage(tau, voxel_size)`` of the clouds as decoded, before the cleaning: the share of
+        each object's fused cloud within ``tau`` of the frame's cloud of it; NaN where the frame does not show the object.  With the
+        keyword at its default the dict, the launches and the read-backs are unchanged."""
         from mspa import cloud_segments
         if per not in ("image", "object"):
             raise ValueError(f"instance_boxes: per must be 'image' or 'object', got {per!r}")
         if upright_iou and not upright:
             raise ValueError("instance_boxes: upright_iou=True scores the upright boxes: it goes with upright=True")
+        if coverage is not None and per != "image":
+            raise ValueError("instance_boxes: coverage=(tau, voxel_size) scores frames: it goes with per='image'")
         if per == "image" and voxel_size is not None:
             raise ValueError("instance_boxes: voxel_size goes with per='object' (a single view's cloud is already one sample per pixel)")
         clouds = self.instance_clouds(scene_id, image_ids, False, device, num_workers)
@@ -329,6 +335,8 @@ class SceneInfoHandler:
             out = {"image_ids": list(clouds.image_ids)}
             if upright:
                 out["upright"] = cleaned.upright_boxes()
+            if coverage is not None:
+                out["coverage"] = clouds.view_coverage(*coverage)
         else:
             _rows, offsets, targets, boxes, *more = clouds.cleaned_objects(nb_neighbors, std_ratio, voxel_size, cluster, upright)
             kept = np.diff(offsets)

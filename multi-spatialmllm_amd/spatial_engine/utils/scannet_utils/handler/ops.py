@@ -17,8 +17,8 @@ from ._images import read_color_rgb, read_depth
 __all__ = ["filter_images_laplacian", "calculate_image_sharpness", "convert_to_corners", "calculate_iou_2d", "calculate_iou_3d",
            "remove_statistical_outliers", "remove_truncated_outliers", "calculate_aabb", "project_mask_to_3d"]
 # (upstream's nine names, which tests/test_handler_ops_cpu.py pins; ``voxel_down_sample``, ``cluster_dbscan`` and
-# ``calculate_upright_box`` and ``calculate_iou_upright`` below are this project's own and are reached as ``ops.voxel_down_sample``
-# and so on)
+# ``calculate_upright_box``, ``calculate_iou_upright`` and ``compute_point_cloud_distance`` below are this project's own and are reached
+# as ``ops.voxel_down_sample`` and so on)
 
 
 def _same_device(a, b):
@@ -198,6 +198,27 @@ def calculate_upright_box(point_cloud_data):
         return cloud_segments.upright_boxes_segments(data, offsets)[0]
     out = cloud_segments.upright_boxes_segments_host(data.numpy() if is_tensor else data, offsets)[0]
     return torch.from_numpy(out.copy()) if is_tensor else out.copy()
+
+
+def compute_point_cloud_distance(source, target):
+    """[n, C >= 3] cloud ``source`` and [m, C >= 3] cloud ``target`` -> [n] float64: for every row of ``source`` the distance to the
+    nearest row of ``target`` -- the primitive behind the Chamfer distance, the one-sided Hausdorff distance and precision / recall at
+    a threshold.  The name is Open3D's ``PointCloud.compute_point_cloud_distance``; the rule restates it (Euclidean distance to the
+    nearest target point) and is not checked against Open3D, which is not a dependency.  It is the one-pair case of
+    ``mspa.cloud_segments.nearest_segments`` (rule in csrc/cloud_distance_core.h): ``sqrt(min((dx*dx + dy*dy) + dz*dz))`` in float64, the
+    bits of a brute force over all rows, the same bits on the device as on the host.  NumPy in gives NumPy out (the host twin of the
+    kernel); a device tensor in gives a device tensor out.  An empty ``target`` gives +inf, a ``source`` row with a non-finite
+    coordinate NaN; a non-finite ``target`` coordinate raises ValueError.  No reference counterpart."""
+    from mspa import cloud_segments
+    if isinstance(source, torch.Tensor) or isinstance(target, torch.Tensor):
+        source, target = _same_device(source, target)
+        if source.is_cuda:
+            return cloud_segments.nearest_segments(source, np.array([0, source.shape[0]], dtype=np.int64), target,
+                                                   np.array([0, target.shape[0]], dtype=np.int64), want_index=False)["distance"]
+        return torch.from_numpy(compute_point_cloud_distance(source.numpy(), target.numpy()))
+    source, target = np.asarray(source), np.asarray(target)
+    return cloud_segments.nearest_segments_host(source, np.array([0, source.shape[0]], dtype=np.int64), target,
+                                                np.array([0, target.shape[0]], dtype=np.int64))["distance"]
 
 
 def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
