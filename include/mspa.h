@@ -1210,6 +1210,50 @@ int mspa_cloud_distance_fit_host(const double *distance_host, const int64_t *out
                                  int64_t *finite_host, int64_t *within_host, double *sum_host, double *sum_sq_host, double *max_host);
 
 /*
+ * RIGID ALIGNMENT OF THE CLOUDS OF TWO RAGGED BATCHES (Kabsch / Horn, and the two steps point-to-point ICP adds to the search above) --
+ * csrc/cloud_align.hip, rule in csrc/cloud_align_core.h on top of csrc/cloud_distance_core.h.  The batches, pairs [P, 2] and out_offsets
+ * [P + 1] are the search's.  A transform is 12 f64: R row-major, then t; y_a = ((R_a0 * x + R_a1 * y) + R_a2 * z) + t_a.  Output row i of
+ * pair p carries index[i], a row of t_xyz [Nt, 3] or -1 (clamped into [-1, Nt) before use); it is used when that is >= 0 and its query
+ * row is finite.  Per pair: the counts and centroids of the used rows, the nine centred sums S_ab (both passes in the order
+ * csrc/cloud_segments_core.h states), Horn's symmetric 4 x 4 matrix, MSPA_CLOUD_ALIGN_SWEEPS cyclic Jacobi sweeps in a fixed pivot
+ * order, R from the unit quaternion of the largest eigenvalue and t = pc - R qc.  status: MSPA_CLOUD_ALIGN_OK; _FEW (fewer than 3 used
+ * rows); _DEGENERATE (l1 - l2 <= 2^MSPA_CLOUD_ALIGN_GAP_EXPONENT * (l1 - l4): collinear or coincident rows).  A pair that is not OK
+ * leaves with the transform of init.  Equal correspondences give equal bits.  Every device entry point takes each host table TWICE
+ * and checks all arguments before it enqueues anything; every device table entry a lane indexes with is clamped.
+ *   mspa_cloud_align_transform_device  -> out_dev [M, 3] f64, the query rows of every pair under transform_dev [P, 12], in output-row
+ *                                      order.  One launch; nothing is enqueued for M == 0.  St only bounds the pairs' second column.
+ *   mspa_cloud_align_fit_device        index_dev [M], init_dev [P, 12] -> transform_dev [P, 12] (may be init_dev), used_dev [P] int64,
+ *                                      status_dev [P] int32 and, where not null, eigen_dev [P, 4] (descending) and converged_dev [P]
+ *                                      int64, in and out: an entry of -1 becomes `iteration` where the transform written equals init
+ *                                      bit for bit.  moments_dev [P, 16] f64 is workspace (used, qc, pc, S afterwards).  Two launches:
+ *                                      one workgroup of 256 per pair for the sums, one lane per pair for the solve; no atomics.
+ *                                      Nothing is enqueued for P == 0.  MSPA_EINVAL for a null pointer where a count is positive,
+ *                                      bad offsets, a pair outside [0, Sq) x [0, St), out_offsets that do not follow from the pairs,
+ *                                      Nt outside [0, 2^30], a negative iteration or a misaligned buffer.
+ *   mspa_cloud_align_transform_host,
+ *   mspa_cloud_align_fit_host          the same on the CPU through the same header: the device's twins for tests, not a fallback.
+ */
+#define MSPA_CLOUD_ALIGN_OK 0
+#define MSPA_CLOUD_ALIGN_FEW 1
+#define MSPA_CLOUD_ALIGN_DEGENERATE 2
+#define MSPA_CLOUD_ALIGN_SWEEPS 12
+#define MSPA_CLOUD_ALIGN_GAP_EXPONENT (-26)
+int mspa_cloud_align_transform_device(const double *q_xyz_dev, const int64_t *q_offsets_host, int64_t Sq, const int64_t *q_offsets_dev, int64_t St,
+                                      const int64_t *pairs_host, const int64_t *pairs_dev, int64_t P, const int64_t *out_offsets_host,
+                                      const int64_t *out_offsets_dev, const double *transform_dev, double *out_dev, mspa_stream_t stream);
+int mspa_cloud_align_fit_device(const double *q_xyz_dev, const int64_t *q_offsets_host, int64_t Sq, const int64_t *q_offsets_dev,
+                                const double *t_xyz_dev, int64_t Nt, int64_t St, const int64_t *pairs_host, const int64_t *pairs_dev, int64_t P,
+                                const int64_t *out_offsets_host, const int64_t *out_offsets_dev, const int64_t *index_dev, const double *init_dev,
+                                int64_t iteration, double *moments_dev, double *transform_dev, int64_t *used_dev, int32_t *status_dev,
+                                double *eigen_dev, int64_t *converged_dev, mspa_stream_t stream);
+int mspa_cloud_align_transform_host(const double *q_xyz_host, const int64_t *q_offsets_host, int64_t Sq, int64_t St, const int64_t *pairs_host,
+                                    int64_t P, const int64_t *out_offsets_host, const double *transform_host, double *out_host);
+int mspa_cloud_align_fit_host(const double *q_xyz_host, const int64_t *q_offsets_host, int64_t Sq, const double *t_xyz_host, int64_t Nt, int64_t St,
+                              const int64_t *pairs_host, int64_t P, const int64_t *out_offsets_host, const int64_t *index_host,
+                              const double *init_host, int64_t iteration, double *transform_host, int64_t *used_host, int32_t *status_host,
+                              double *eigen_host, int64_t *converged_host);
+
+/*
  * Instance-mask decode ON THE DEVICE (csrc/mask_ingest.hip, rule in csrc/png_unfilter8_core.h): the 8-bit twin of the depth-frame
  * decode above, for ScanNet's `instance-filt/<image>.png` label images (`cv2.imread(path, -1)` per (image, object) in the
  * reference's get_instance_mask).  The inflate in front of the un-filter is mspa_inflate_blocks_device with block_bytes = h * (w + 1).

@@ -33,6 +33,23 @@ inline int64_t extent_tiles(const int64_t *offsets, int64_t S) {
 
 inline bool misaligned(const void *p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) != 0; }
 
+// ---- the fold of K sums through LDS -------------------------------------------------------------------------------------------
+
+// partial [K][kLanes] in LDS, every thread j of a workgroup of kLanes has written its own K entries: segs::ordered_sum's fold of all K
+// sums at once -- partial[k][j] += partial[k][j + stride] for every j < stride, strides kLanes / 2, ..., 1, one barrier a stride --
+// with the K totals in every thread afterwards and partial[] free again.
+template <int K>
+__device__ __forceinline__ void fold_sums(double (*partial)[kLanes], int32_t j, double total[K]) {
+    __syncthreads();
+    for (int32_t s = kLanes / 2; s >= 1; s >>= 1) {
+        if (j < s)
+            for (int k = 0; k < K; ++k) partial[k][j] = partial[k][j] + partial[k][j + s];
+        __syncthreads();
+    }
+    for (int k = 0; k < K; ++k) total[k] = partial[k][0];
+    __syncthreads();
+}
+
 // ---- the flag compaction ------------------------------------------------------------------------------------------------------
 
 // The indices i in [0, n) with flag(i), in ascending order: per tile of kFlagTile slots a count (wave ballots), one workgroup's

@@ -18,7 +18,10 @@ its upright minimal box: the z extent times the minimum-area rectangle around th
 (csrc/upright_iou.hip, rule in csrc/upright_iou_core.h) score such boxes against each other, pair by pair or set against set.
 ``target_index`` / ``TargetIndex.nearest`` / ``fit_segments`` / ``cloud_fit_segments`` (csrc/cloud_distance.hip, rule in
 csrc/cloud_distance_core.h) compare the clouds of one batch with those of another: per row the distance to, and the row of, the nearest
-point of the segment its pair names, and a per-pair summary of those distances.
+point of the segment its pair names, and a per-pair summary of those distances.  ``rigid_fit_segments`` / ``transform_segments`` /
+``TargetIndex.register`` / ``register_segments`` (csrc/cloud_align.hip, rule in csrc/cloud_align_core.h) say by which rotation and
+translation one cloud lies off another: the rigid fit of matched rows (Kabsch / Horn) per pair, and point-to-point ICP on top of
+``nearest``.
 """
 from __future__ import annotations
 
@@ -828,6 +831,7 @@ class TargetIndex:
     def __init__(self, offsets, grid_k, grids, off_dev, grids_dev, base_dev, pts, order, starts, device):
         self.offsets, self.grid_k, self.grids, self.device = offsets, grid_k, grids, device
         self.off_dev, self.grids_dev, self.base_dev, self.pts, self.order, self.starts = off_dev, grids_dev, base_dev, pts, order, starts
+        self.xyz = None                                                        # the targets in their own order, once ``targets()`` was asked
 
     def nearest(self, queries: torch.Tensor, q_offsets, pairs=None, max_distance=None, want_index: bool = True, want_evals: bool = False,
                 _ordered=None) -> dict:
@@ -872,6 +876,101 @@ class TargetIndex:
                 pairs.ctypes.data, _ptr(pairs_dev), P, out_offsets.ctypes.data, _ptr(out_dev), _ptr(perm), cap, _ptr(out["distance"]), _ptr(out.get("index")),
                 _ptr(out.get("evals")), _stream_ptr()))
         return out
+
+    def register(self, queries, q_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None, sync_every=None,
+                  want_history: bool = False) -> dict:
+        """Point-to-point ICP of every pair: a batch ``queries`` [Nq, C >= 3] (device) with host ``q_offsets`` and the host pair table of
+        ``nearest`` -> a dict of device tensors: ``R`` [P, 3, 3] and ``t`` [P, 3] float64, the transform that carries pair p's query
+        segment onto its target segment; ``status`` [P] int32 and ``used`` [P] int64 of the last fit (``rigid_fit_segments``');
+        ``converged_at`` [P] int64, the first iteration whose fit returned the transform it started from bit for bit, -1 if none did;
+        ``fitness`` [P] = finite / rows and ``inlier_rmse`` [P] = sqrt(sum_sq / finite) of ``fit_segments`` under the final transform
+        (Open3D's two result fields); ``offsets`` [P + 1] host int64.  With T_0 = ``init`` ([P, 4, 4] or [P, 3, 4], host or device; None:
+        the identity), iteration k transforms the ORIGINAL query rows by T_k, searches them with the cap ``max_distance`` (required,
+        finite, > 0: Open3D's max_correspondence_distance) and fits the original rows to their matches: the fit IS T_(k+1), no
+        transforms are composed, equal correspondences give equal bits, and a pair that has converged reproduces its 12 numbers from
+        then on.  A pair whose fit is not ok keeps its transform.  With ``want_history`` also ``history_used`` [K, P] int64 and
+        ``history_rmse`` [K, P] float64, the rows and the rmse of the correspondences each fit used.  ``iterations + 1`` searches.
+        Enqueue only: every launch on the current stream, the host tables go up once through pinned memory and nothing is read back --
+        zero host synchronisations.  With ``sync_every=n`` instead: ONE read-back of ``converged_at`` (8 P bytes) after every n
+        iterations and after the last, ceil(iterations / n) read-backs at most, and the loop ends at the first that shows no -1; the
+        result is byte for byte the full loop's, because every pair then sits at its fixed point (``all_converged``: what the last
+        read-back showed)."""
+        xyz = _xyz_of("queries", queries)
+        q_off = _offsets(q_offsets, int(xyz.shape[0]))
+        St = self.offsets.size - 1
+        pairs, out_offsets = _pair_tables(q_off, St, pairs)
+        cap = _required_cap(max_distance)
+        K, every = _iterations_of(iterations, sync_every)
+        P, M, dev = pairs.shape[0], int(out_offsets[-1]), self.device
+        _require(xyz.device == dev, f"queries: on the index's device {dev}, got {xyz.device}")
+        T = _transforms_of(init, P, dev)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)     # noqa: E731
+        i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)       # noqa: E731
+        out = {"status": torch.empty((P,), dtype=torch.int32, device=dev), "used": i64(P), "converged_at": torch.full((P,), -1, dtype=torch.int64, device=dev),
+               "offsets": out_offsets}
+        if want_history:
+            out["history_used"], out["history_rmse"] = i64(K, P), f64(K, P)
+        if P == 0:
+            out["R"], out["t"] = _split(T)
+            out["fitness"], out["inlier_rmse"] = f64(0), f64(0)
+            return out
+        lib = _lib.load()
+        tabs = _AlignTables(q_off, pairs, out_offsets, St, dev)
+        targets = self.targets()
+        moved, distance, index, moments, T_next = f64(M, 3), f64(M), i64(M), f64(P, 16), f64(P, 12)
+        summary = {name: (i64(P) if name in FIT_KEYS[:3] else f64(P)) for name in FIT_KEYS}
+
+        def search(T_now):
+            tabs.transform(xyz, T_now, moved)
+            if not M:
+                return
+            perm = None
+            if ORDER_QUERIES:
+                keys = i64(M)
+                _lib.check(lib.mspa_cloud_distance_keys_device(self.offsets.ctypes.data, St, self.grid_k, self.grids.ctypes.data, _ptr(self.grids_dev),
+                                                               _ptr(moved), out_offsets.ctypes.data, P, _ptr(tabs.out_dev), tabs.search_pairs.ctypes.data,
+                                                               _ptr(tabs.search_dev), P, out_offsets.ctypes.data, _ptr(tabs.out_dev), _ptr(keys), _stream_ptr()))
+                perm = torch.sort(keys).indices
+            _lib.check(lib.mspa_cloud_distance_device(
+                _ptr(self.pts), _ptr(self.starts), int(self.starts.numel()), _ptr(self.order), self.offsets.ctypes.data, St, self.grid_k, self.grids.ctypes.data,
+                _ptr(self.off_dev), _ptr(self.grids_dev), _ptr(self.base_dev), _ptr(moved), out_offsets.ctypes.data, P, _ptr(tabs.out_dev),
+                tabs.search_pairs.ctypes.data, _ptr(tabs.search_dev), P, out_offsets.ctypes.data, _ptr(tabs.out_dev), _ptr(perm), cap, _ptr(distance),
+                _ptr(index), None, _stream_ptr()))
+
+        def summarise():
+            _lib.check(lib.mspa_cloud_distance_fit_device(_ptr(distance), out_offsets.ctypes.data, P, 0.0, _ptr(tabs.out_dev),
+                                                          *(_ptr(summary[name]) for name in FIT_KEYS), _stream_ptr()))
+            return summary["finite"].to(torch.float64), torch.sqrt(summary["sum_sq"] / summary["finite"].to(torch.float64))
+
+        done = K
+        for k in range(K):
+            search(T)
+            tabs.fit(xyz, targets, index, T, k, moments, T_next, out["used"], out["status"], None, out["converged_at"])
+            T, T_next = T_next, T
+            if want_history:
+                out["history_used"][k].copy_(out["used"])
+                out["history_rmse"][k].copy_(summarise()[1])
+            if sync_every is not None and ((k + 1) % every == 0 or k + 1 == K):
+                out["all_converged"] = bool((out["converged_at"].cpu() != -1).all())          # THE read-back of sync_every
+                if out["all_converged"]:
+                    done = k + 1
+                    break
+        if want_history and done < K:                                # every pair sits at its fixed point: the full loop repeats this row
+            out["history_used"][done:] = out["history_used"][done - 1]
+            out["history_rmse"][done:] = out["history_rmse"][done - 1]
+        search(T)
+        finite, rmse = summarise()
+        out["fitness"], out["inlier_rmse"] = finite / summary["rows"].to(torch.float64), rmse
+        out["R"], out["t"] = _split(T)
+        return out
+
+    def targets(self) -> torch.Tensor:
+        """The targets the index was built from, [N, 3] float64 in their own order: ``pts`` scattered back through ``order``, once per
+        index (enqueue only)."""
+        if self.xyz is None:
+            self.xyz = torch.empty_like(self.pts)
+            self.xyz[self.order] = self.pts
+        return self.xyz
 
 
 def target_index(targets: torch.Tensor, offsets, _grid_k=None) -> TargetIndex:
@@ -1005,4 +1104,244 @@ def cloud_fit_segments_host(a, a_offsets, b, b_offsets, tau, max_distance=None) 
     ba = nearest_segments_host(b, b_offsets, a, a_offsets, None, max_distance)
     out = {"a_to_b": fit_segments_host(ab["distance"], ab["offsets"], tau), "b_to_a": fit_segments_host(ba["distance"], ba["offsets"], tau)}
     out.update(_fit_scores(out["a_to_b"], out["b_to_a"], np))
+    return out
+
+
+# ---- rigid alignment of the clouds of two batches (csrc/cloud_align.hip, rule in csrc/cloud_align_core.h) -------------------------------
+
+ALIGN_STATUS = {"ok": _lib.CLOUD_ALIGN_OK, "few": _lib.CLOUD_ALIGN_FEW, "degenerate": _lib.CLOUD_ALIGN_DEGENERATE}
+
+
+def _transforms_of(init, P: int, device=None):
+    """``init`` (None: the identity; [P, 4, 4] or [P, 3, 4], host or device) -> [P, 12] float64, R row-major then t: a fresh device
+    tensor on ``device``, or a NumPy array where ``device`` is None.  A host ``init`` must be finite; a device one is not read back
+    (a non-finite transform makes non-finite rows, which the search answers with -1: the pair is FEW and keeps it)."""
+    if init is None:
+        init = np.tile(np.eye(3, 4), (P, 1, 1))
+    on_device = isinstance(init, torch.Tensor) and init.is_cuda
+    if not on_device:
+        init = np.asarray(init.numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+    _require(init.ndim == 3 and tuple(init.shape) in ((P, 4, 4), (P, 3, 4)), f"init: [P, 4, 4] or [P, 3, 4] with P = {P}, got {list(init.shape)}")
+    if on_device:
+        _require(device is not None and init.device == device, "init: on the queries' device")
+        init = init.to(torch.float64)
+        return torch.cat([init[:, :3, :3].reshape(P, 9), init[:, :3, 3]], dim=1).contiguous()
+    _require(bool(np.isfinite(init).all()), "init: finite")
+    flat = np.ascontiguousarray(np.concatenate([init[:, :3, :3].reshape(P, 9), init[:, :3, 3]], axis=1))
+    return flat if device is None else _upload(flat, device=device)[0].clone()
+
+
+def _fit_pairs(q_off: np.ndarray, pairs):
+    """``(pairs, out_offsets, St)`` of a fit or a transform, which name no target batch: the second column only has to be a segment
+    number, and St is one more than its largest."""
+    if pairs is None:
+        return _pair_tables(q_off, q_off.size - 1, None) + (q_off.size - 1,)
+    _require(not (isinstance(pairs, torch.Tensor) and pairs.is_cuda), "pairs: a host array (the launch shapes come from it)")
+    host = np.asarray(pairs, dtype=np.int64)
+    St = int(host[:, 1].max()) + 1 if host.ndim == 2 and host.shape[1:] == (2,) and host.shape[0] else 0
+    return _pair_tables(q_off, St, pairs) + (St,)
+
+
+def _split(T):
+    """[P, 12] -> (R [P, 3, 3], t [P, 3]), views."""
+    return T[:, :9].reshape(-1, 3, 3), T[:, 9:]
+
+
+def _join(R, t, P: int, xp):
+    _require(tuple(R.shape) == (P, 3, 3) and tuple(t.shape) == (P, 3), f"R and t: [P, 3, 3] and [P, 3] with P = {P}, got {list(R.shape)} and {list(t.shape)}")
+    return xp.cat([R.reshape(P, 9), t], dim=1).contiguous() if xp is torch else np.ascontiguousarray(np.concatenate([R.reshape(P, 9), t], axis=1))
+
+
+class _AlignTables:
+    """The host tables of a batch of pairs and their device copies, uploaded once (enqueue only)."""
+
+    def __init__(self, q_off, pairs, out_offsets, St, device):
+        self.q_off, self.pairs, self.out, self.St, self.P, self.M = q_off, pairs, out_offsets, St, pairs.shape[0], int(out_offsets[-1])
+        # the search's pair table: the transformed rows lie in output-row order, so query segment p is pair p itself
+        self.search_pairs = np.ascontiguousarray(np.stack([np.arange(self.P, dtype=np.int64), pairs[:, 1]], axis=1))
+        if device is not None and self.P:
+            self.q_dev, self.pairs_dev, self.out_dev, self.search_dev = _upload(q_off, pairs, out_offsets, self.search_pairs, device=device)
+
+    def transform(self, xyz, T, out):
+        _lib.check(_lib.load().mspa_cloud_align_transform_device(
+            _ptr(xyz), self.q_off.ctypes.data, self.q_off.size - 1, _ptr(self.q_dev), self.St, self.pairs.ctypes.data, _ptr(self.pairs_dev), self.P,
+            self.out.ctypes.data, _ptr(self.out_dev), _ptr(T), _ptr(out), _stream_ptr()))
+
+    def fit(self, xyz, targets, index, init, iteration, moments, T, used, status, eigen=None, converged=None):
+        _lib.check(_lib.load().mspa_cloud_align_fit_device(
+            _ptr(xyz), self.q_off.ctypes.data, self.q_off.size - 1, _ptr(self.q_dev), _ptr(targets), int(targets.shape[0]), self.St,
+            self.pairs.ctypes.data, _ptr(self.pairs_dev), self.P, self.out.ctypes.data, _ptr(self.out_dev), _ptr(index), _ptr(init), iteration,
+            _ptr(moments), _ptr(T), _ptr(used), _ptr(status), _ptr(eigen), _ptr(converged), _stream_ptr()))
+
+
+def _index_of(index, M: int, device) -> torch.Tensor:
+    _require(isinstance(index, torch.Tensor) and index.device == device and index.dtype == torch.int64 and tuple(index.shape) == (M,),
+             f"index: a device int64 tensor [M] with M = {M}")
+    return index.contiguous()
+
+
+def rigid_fit_segments(queries: torch.Tensor, q_offsets, targets: torch.Tensor, index: torch.Tensor, pairs=None, init=None,
+                       want_parts: bool = False) -> dict:
+    """The rigid fit (Kabsch / Horn) of matched rows, pair by pair: a batch ``queries`` [Nq, C >= 3] (device) with host ``q_offsets``
+    [Sq + 1], ``targets`` [Nt, C >= 3] (device), ``index`` [M] int64 (device; per output row a row of ``targets`` or -1 -- what
+    ``TargetIndex.nearest`` returns, or ``arange`` for rows that correspond one to one) and the host pair table of ``nearest`` (only
+    its first column is read; None: pair s is query segment s) -> a dict of device tensors ``R`` [P, 3, 3] and ``t`` [P, 3] float64,
+    the proper rotation and the translation with the least sum of squares of ``R q + t - targets[index]`` over the used rows (index
+    >= 0 and a finite query row); ``used`` [P] int64; ``status`` [P] int32 (``ALIGN_STATUS``: ok, few = fewer than 3 used rows,
+    degenerate = collinear or coincident rows); ``offsets`` [P + 1] host int64; with ``want_parts`` ``eigen`` [P, 4], the eigenvalues
+    of Horn's matrix in descending order.  A pair that is not ok gets the transform of ``init`` ([P, 4, 4] or [P, 3, 4]; None: the
+    identity).  The rule is csrc/cloud_align_core.h's: centred sums in the order csrc/cloud_segments_core.h states, Horn's quaternion
+    by a fixed number of Jacobi sweeps -- the same bits on every run, and equal correspondences give equal bits.  Enqueue only: two
+    launches on the current stream, the host tables go up through pinned memory and nothing is read back."""
+    xyz, tgt = _xyz_of("queries", queries), _xyz_of("targets", targets)
+    q_off = _offsets(q_offsets, int(xyz.shape[0]))
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    P, M, dev = pairs.shape[0], int(out_offsets[-1]), xyz.device
+    _require(tgt.device == dev, "targets: on the queries' device")
+    index = _index_of(index, M, dev)
+    T0 = _transforms_of(init, P, dev)
+    T = torch.empty((P, 12), dtype=torch.float64, device=dev)
+    out = {"used": torch.empty((P,), dtype=torch.int64, device=dev), "status": torch.empty((P,), dtype=torch.int32, device=dev), "offsets": out_offsets}
+    if want_parts:
+        out["eigen"] = torch.empty((P, 4), dtype=torch.float64, device=dev)
+    if P:
+        moments = torch.empty((P, 16), dtype=torch.float64, device=dev)
+        _AlignTables(q_off, pairs, out_offsets, St, dev).fit(xyz, tgt, index, T0, 0, moments, T, out["used"], out["status"], out.get("eigen"))
+    out["R"], out["t"] = _split(T)
+    return out
+
+
+def transform_segments(queries: torch.Tensor, q_offsets, R: torch.Tensor, t: torch.Tensor, pairs=None) -> dict:
+    """A batch ``queries`` [Nq, C >= 3] (device) with host ``q_offsets`` [Sq + 1], per pair ``R`` [P, 3, 3] and ``t`` [P, 3] (device
+    float64) and the host pair table of ``nearest`` (None: pair s is query segment s) -> a dict: ``xyz`` [M, 3] float64 (device), the
+    rows of pair p's query segment as ``y_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a`` at ``offsets[p]:offsets[p + 1]`` -- in output-row
+    order, a batch of P segments -- and ``offsets`` [P + 1] host int64.  Enqueue only: one launch on the current stream, the host
+    tables go up through pinned memory and nothing is read back."""
+    xyz = _xyz_of("queries", queries)
+    q_off = _offsets(q_offsets, int(xyz.shape[0]))
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    P, M, dev = pairs.shape[0], int(out_offsets[-1]), xyz.device
+    _require(isinstance(R, torch.Tensor) and isinstance(t, torch.Tensor) and R.device == dev and t.device == dev and R.dtype == t.dtype == torch.float64,
+             "R and t: float64 tensors on the queries' device")
+    T = _join(R, t, P, torch)
+    out = {"xyz": torch.empty((M, 3), dtype=torch.float64, device=dev), "offsets": out_offsets}
+    if M:
+        _AlignTables(q_off, pairs, out_offsets, St, dev).transform(xyz, T, out["xyz"])
+    return out
+
+
+def _iterations_of(iterations, sync_every):
+    K = int(iterations)
+    _require(K >= 1, f"iterations: at least 1, got {iterations}")
+    if sync_every is not None:
+        _require(int(sync_every) >= 1, f"sync_every: at least 1, got {sync_every}")
+    return K, K if sync_every is None else int(sync_every)
+
+
+def _required_cap(max_distance) -> float:
+    _require(max_distance is not None, "max_distance: required (finite and > 0): without it a far query walks its target's whole grid on every iteration")
+    return _cap_of(max_distance)
+
+
+def register_segments(queries: torch.Tensor, q_offsets, targets: torch.Tensor, t_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None,
+                      sync_every=None, want_history: bool = False, _grid_k=None) -> dict:
+    """``target_index(targets, t_offsets).register(queries, q_offsets, ...)``: point-to-point ICP of every pair's query segment onto
+    its target segment.  ``target_index``' one read-back and its ValueError."""
+    return target_index(targets, t_offsets, _grid_k).register(queries, q_offsets, pairs, max_distance=max_distance, iterations=iterations, init=init,
+                                                              sync_every=sync_every, want_history=want_history)
+
+
+def _host_rows(name: str, rows) -> np.ndarray:
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < 3:
+        raise ValueError(f"mspa.cloud_segments: {name}: expected [N, C >= 3], got {list(rows.shape)}")
+    return np.ascontiguousarray(rows[:, :3], dtype=np.float64)
+
+
+def _transform_host(q, q_off, St, pairs, out_offsets, T):
+    out = np.empty((int(out_offsets[-1]), 3), dtype=np.float64)
+    _lib.check(_lib.load().mspa_cloud_align_transform_host(q.ctypes.data, q_off.ctypes.data, q_off.size - 1, St, pairs.ctypes.data, pairs.shape[0],
+                                                           out_offsets.ctypes.data, T.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _fit_host(q, q_off, t, St, pairs, out_offsets, index, T0, iteration, want_parts=False, converged=None):
+    P = pairs.shape[0]
+    T, used, status = np.zeros((P, 12), dtype=np.float64), np.zeros((P,), dtype=np.int64), np.zeros((P,), dtype=np.int32)
+    eigen = np.zeros((P, 4), dtype=np.float64) if want_parts else None
+    _lib.check(_lib.load().mspa_cloud_align_fit_host(q.ctypes.data, q_off.ctypes.data, q_off.size - 1, t.ctypes.data, t.shape[0], St, pairs.ctypes.data, P,
+                                                     out_offsets.ctypes.data, index.ctypes.data, T0.ctypes.data, iteration, T.ctypes.data,
+                                                     used.ctypes.data, status.ctypes.data, eigen.ctypes.data if want_parts else None,
+                                                     converged.ctypes.data if converged is not None else None))
+    return T, used, status, eigen
+
+
+def rigid_fit_segments_host(queries, q_offsets, targets, index, pairs=None, init=None, want_parts: bool = False) -> dict:
+    """``rigid_fit_segments`` on the CPU for NumPy input, through the same header (mspa_cloud_align_fit_host): NumPy arrays out.  The
+    device's twin for tests and for input that has no device, not a fallback."""
+    q, t = _host_rows("queries", queries), _host_rows("targets", targets)
+    q_off = _offsets(q_offsets, q.shape[0])
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    _require(index.shape == (int(out_offsets[-1]),), f"index: int64 [M] with M = {int(out_offsets[-1])}")
+    T, used, status, eigen = _fit_host(q, q_off, t, St, pairs, out_offsets, index, _transforms_of(init, pairs.shape[0]), 0, want_parts)
+    out = {"R": _split(T)[0], "t": _split(T)[1], "used": used, "status": status, "offsets": out_offsets}
+    if want_parts:
+        out["eigen"] = eigen
+    return out
+
+
+def transform_segments_host(queries, q_offsets, R, t, pairs=None) -> dict:
+    """``transform_segments`` on the CPU for NumPy input (mspa_cloud_align_transform_host).  The device's twin, not a fallback."""
+    q = _host_rows("queries", queries)
+    q_off = _offsets(q_offsets, q.shape[0])
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    T = _join(np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64), pairs.shape[0], np)
+    return {"xyz": _transform_host(q, q_off, St, pairs, out_offsets, T), "offsets": out_offsets}
+
+
+def register_segments_host(queries, q_offsets, targets, t_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None, sync_every=None,
+                           want_history: bool = False, want_index: bool = False, _grid_k=None) -> dict:
+    """``register_segments`` on the CPU for NumPy input: the same loop over the host twins, ``nearest_segments_host`` for its searches.
+    NumPy arrays out; with ``want_index`` also ``history_index`` [K, M], the correspondences of every iteration.  The device's twin,
+    not a fallback."""
+    q, t = _host_rows("queries", queries), _host_rows("targets", targets)
+    q_off, t_off = _offsets(q_offsets, q.shape[0]), _offsets(t_offsets, t.shape[0])
+    St = t_off.size - 1
+    pairs, out_offsets = _pair_tables(q_off, St, pairs)
+    cap = _required_cap(max_distance)
+    K, every = _iterations_of(iterations, sync_every)
+    P, M = pairs.shape[0], int(out_offsets[-1])
+    T = _transforms_of(init, P)
+    tabs = _AlignTables(q_off, pairs, out_offsets, St, None)
+    converged = np.full((P,), -1, dtype=np.int64)
+    out = {"offsets": out_offsets, "converged_at": converged, "used": np.zeros((P,), dtype=np.int64), "status": np.zeros((P,), dtype=np.int32)}
+    hist_used, hist_rmse, hist_index = np.zeros((K, P), dtype=np.int64), np.zeros((K, P)), np.zeros((K, M), dtype=np.int64)
+
+    def search(T_now):
+        moved = _transform_host(q, q_off, St, pairs, out_offsets, T_now)
+        found = nearest_segments_host(moved, out_offsets, t, t_off, tabs.search_pairs, cap, _grid_k=_grid_k)
+        fit = fit_segments_host(found["distance"], out_offsets, 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return found["index"], fit, np.sqrt(fit["sum_sq"] / fit["finite"].astype(np.float64))
+
+    done = K
+    for k in range(K):
+        index, _fit, rmse = search(T)
+        T, out["used"], out["status"], _ = _fit_host(q, q_off, t, St, pairs, out_offsets, index, T, k, False, converged)
+        hist_used[k], hist_rmse[k], hist_index[k] = out["used"], rmse, index
+        if sync_every is not None and ((k + 1) % every == 0 or k + 1 == K):
+            out["all_converged"] = bool((converged != -1).all())
+            if out["all_converged"]:
+                done = k + 1
+                break
+    hist_used[done:], hist_rmse[done:], hist_index[done:] = hist_used[done - 1], hist_rmse[done - 1], hist_index[done - 1]
+    _index, fit, rmse = search(T)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["fitness"], out["inlier_rmse"] = fit["finite"].astype(np.float64) / fit["rows"].astype(np.float64), rmse
+    out["R"], out["t"] = _split(T)
+    if want_history:
+        out["history_used"], out["history_rmse"] = hist_used, hist_rmse
+    if want_index:
+        out["history_index"] = hist_index
     return out

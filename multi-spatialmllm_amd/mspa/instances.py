@@ -175,6 +175,51 @@ class InstanceClouds:
         out[where] = fit["within"].to(torch.float64) / fit["rows"].to(torch.float64)
         return out.reshape(F, L)
 
+    def view_alignment(self, max_distance, voxel_size=None, iterations=30, fused=None) -> dict:
+        """For every (image, label) with rows, the rigid transform that carries this image's cloud of the object onto the object's
+        fused cloud (``by_object(voxel_size)``), by point-to-point ICP from the identity (``cloud_segments.TargetIndex.register``
+        with the cap ``max_distance`` and ``iterations``) -> a dict of device tensors: ``R`` [F, L, 3, 3], ``t`` [F, L, 3], ``angle``
+        [F, L] (the rotation's angle in [0, pi]: 2 atan2(|xyz|, w) of its quaternion, taken from R as atan2(sin, cos)), ``shift``
+        [F, L] (how far the transform moves the segment's centroid), ``fitness``, ``inlier_rmse`` [F, L] float64 -- NaN where the
+        segment is empty -- and ``status`` [F, L] int32 (``cloud_segments.ALIGN_STATUS``; -1 where the segment is empty).  ``angle``
+        and ``shift`` are torch expressions.  It says BY WHICH motion a frame's cloud lies off the object: pose drift, or an object
+        that moved.  The fused cloud contains the frame's own samples, so a frame that dominates its object is pulled towards itself:
+        without a ``voxel_size`` every row finds itself at distance 0 and the answer is the identity exactly; with one, the voxel
+        means are drawn towards the frame by its share of the samples, and the motion reported is short by about that share.
+        ``fused=(rows, offsets, object_ids)`` -- the ``by_object`` of ANOTHER ``InstanceClouds`` (the other frames, an earlier visit, a
+        reference scan) -- replaces the target and has no such pull; a (image, label) whose object it lacks has an empty target and
+        is FEW.  One index over the fused clouds (``cloud_segments.target_index``: one read-back, its ValueError) on top of
+        ``by_object``'s read-back; it needs the rows on the device."""
+        from . import cloud_segments
+        F, L = self.counts.shape
+        dev = self.rows.device
+        nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)      # noqa: E731
+        out = {"R": nan(F * L, 3, 3), "t": nan(F * L, 3), "angle": nan(F * L), "shift": nan(F * L), "fitness": nan(F * L), "inlier_rmse": nan(F * L),
+               "status": torch.full((F * L,), -1, dtype=torch.int32, device=dev)}
+        shaped = lambda: {k: v.reshape((F, L) + tuple(v.shape[1:])) for k, v in out.items()}       # noqa: E731
+        target, target_offsets, object_ids = self.by_object(voxel_size) if fused is None else fused
+        frames, labels = np.nonzero(self.counts[:, 1:] if L > 1 else self.counts[:, :0])
+        labels = labels + 1
+        if len(frames) == 0:
+            return shaped()
+        object_ids = np.asarray(object_ids, dtype=np.int64)
+        target_offsets = np.append(np.asarray(target_offsets, dtype=np.int64), target_offsets[-1])  # one empty segment behind the objects
+        run_of = np.full((max(L, int(object_ids.max(initial=-1)) + 2),), len(object_ids), dtype=np.int64)
+        run_of[object_ids + 1] = np.arange(len(object_ids), dtype=np.int64)
+        pairs = np.stack([frames.astype(np.int64) * L + labels, run_of[labels]], axis=1).astype(np.int64)
+        reg = cloud_segments.target_index(target, target_offsets).register(self.rows, self.offsets, pairs, max_distance=max_distance, iterations=iterations)
+        where, lengths = cloud_segments._upload(pairs[:, 0].copy(), self.counts.reshape(-1), device=dev)
+        R, t = reg["R"], reg["t"]
+        xyz = self.rows[:, :3].to(torch.float64).contiguous()
+        centre = (torch.segment_reduce(xyz, "sum", lengths=lengths, axis=0, unsafe=True) / lengths.to(torch.float64)[:, None]).index_select(0, where)
+        moved = (R @ centre[:, :, None])[:, :, 0] + t
+        sine = 0.5 * torch.sqrt((R[:, 2, 1] - R[:, 1, 2]) ** 2 + (R[:, 0, 2] - R[:, 2, 0]) ** 2 + (R[:, 1, 0] - R[:, 0, 1]) ** 2)
+        cosine = 0.5 * (R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2] - 1.0)
+        out["R"][where], out["t"][where], out["status"][where] = R, t, reg["status"]
+        out["angle"][where], out["shift"][where] = torch.atan2(sine, cosine), torch.linalg.vector_norm(moved - centre, dim=1)
+        out["fitness"][where], out["inlier_rmse"][where] = reg["fitness"], reg["inlier_rmse"]
+        return shaped()
+
     def cleaned_objects(self, nb_neighbors=20, std_ratio=1.0, voxel_size=None, cluster=None, upright=False):
         """``(rows, offsets, object_ids, boxes)``: ``by_object()`` through the same batched cleaning -- per object the rows
         ``ops.remove_statistical_outliers(object_cloud(t), nb_neighbors, std_ratio)`` keeps, back to back, with host ``offsets``

@@ -221,6 +221,40 @@ def compute_point_cloud_distance(source, target):
                                                 np.array([0, target.shape[0]], dtype=np.int64))["distance"]
 
 
+def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration: int = 30):
+    """[n, C >= 3] cloud ``source`` and [m, C >= 3] cloud ``target`` -> a dict: ``transformation`` [4, 4] float64, the rigid transform
+    that carries ``source`` onto ``target`` by point-to-point ICP from ``init`` ([4, 4]; None: the identity), and Open3D's two result
+    fields under it, ``fitness`` (the share of source rows with a target row within ``max_correspondence_distance``) and
+    ``inlier_rmse`` (the root mean square distance of those rows).  The name and the arguments are Open3D's
+    ``pipelines.registration.registration_icp`` with ``TransformationEstimationPointToPoint``; the rule restates it WITHOUT Open3D's
+    relative-change stop -- it runs ``max_iteration`` iterations, from its fixed point on each reproduces the same transform -- and is
+    not checked against Open3D, which is not a dependency.  Every iteration fits the ORIGINAL source rows to their nearest target
+    rows (csrc/cloud_align_core.h: Horn's quaternion by a fixed number of Jacobi sweeps, float64), so no transforms are composed.  It
+    is the one-pair case of ``mspa.cloud_segments.register_segments``: NumPy in gives NumPy out (the host twin of the kernels), a
+    device tensor in gives device tensors out, the same bits either way.  No reference counterpart."""
+    from mspa import cloud_segments
+    one = lambda rows: np.array([0, rows.shape[0]], dtype=np.int64)           # noqa: E731
+    if isinstance(source, torch.Tensor) or isinstance(target, torch.Tensor):
+        source, target = _same_device(source, target)
+        if source.is_cuda:
+            out = cloud_segments.register_segments(source, one(source), target, one(target), max_distance=max_correspondence_distance,
+                                                   iterations=max_iteration, init=None if init is None else torch.as_tensor(init)[None])
+            T = torch.eye(4, dtype=torch.float64, device=source.device)
+            T[:3, :3], T[:3, 3] = out["R"][0], out["t"][0]
+            return {"transformation": T, "fitness": out["fitness"][0], "inlier_rmse": out["inlier_rmse"][0]}
+        host = registration_icp(source.numpy(), target.numpy(), max_correspondence_distance, None if init is None else torch.as_tensor(init).cpu().numpy(),
+                                max_iteration)
+        return {k: torch.as_tensor(v) for k, v in host.items()}
+    source, target = np.asarray(source), np.asarray(target)
+    if isinstance(init, torch.Tensor):
+        init = init.cpu().numpy()
+    out = cloud_segments.register_segments_host(source, one(source), target, one(target), max_distance=max_correspondence_distance,
+                                                iterations=max_iteration, init=None if init is None else np.asarray(init, dtype=np.float64)[None])
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = out["R"][0], out["t"][0]
+    return {"transformation": T, "fitness": out["fitness"][0], "inlier_rmse": out["inlier_rmse"][0]}
+
+
 def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
     """Drop, per axis, the ``int(t * N)`` rows with the smallest and the largest coordinate, and keep the rows that survive on
     all three axes, in ascending row order (OPS:163-208).  Which of several equal coordinates goes is ``np.argsort``'s
