@@ -1254,6 +1254,75 @@ int mspa_cloud_align_fit_host(const double *q_xyz_host, const int64_t *q_offsets
                               double *eigen_host, int64_t *converged_host);
 
 /*
+ * THE K NEAREST ROWS AND THE NORMAL OF EVERY ROW OF A RAGGED BATCH -- csrc/cloud_normals.hip, rule in csrc/cloud_normals_core.h on top of
+ * csrc/cloud_distance_core.h.  The batch is xyz [N, 3] f64 with offsets [S + 1]; 1 <= k <= 64.  The neighbours of a row are the
+ * min(k, n_s) rows of its own segment with the smallest (d2, row), d2 = (dx * dx + dy * dy) + dz * dz, the row itself among them;
+ * with max_distance (finite, > 0; +inf: no cap) only rows with d2 <= max_distance * max_distance.  used [N] int32 is their number.
+ * The neighbour table (nbr_index [N, k] int64, rows of the batch, -1 behind used; nbr_distance [N, k] f64 = sqrt(d2), +inf behind
+ * used) holds them in ascending (d2, row) order: the bits of a brute force.  The fit: the centroid and the six centred sums over the
+ * neighbours in that order, MSPA_CLOUD_NORMALS_SWEEPS cyclic Jacobi sweeps over (0,1) (0,2) (1,2), the normalised column of the
+ * smallest eigenvalue with its first non-zero component positive, negated where a viewpoint of the segment (viewpoints [S, 3], a
+ * non-finite row: none; null: none anywhere) sees it from behind: ((v - p) . n) < 0.  curvature [N] = l0 / ((l0 + l1) + l2).  status
+ * [N] uint8: MSPA_CLOUD_NORMALS_OK; _FEW (used < 3); _DEGENERATE (l1 - l0 <= 2^MSPA_CLOUD_NORMALS_GAP_EXPONENT * (l2 - l0): collinear,
+ * coincident or isotropic neighbours); a row that is not OK has a NaN normal and curvature.  The two output groups -- normal, curvature
+ * and status; nbr_index and nbr_distance -- are null together or not at all, and at least one is asked for.
+ *   mspa_cloud_normals_device  pts_dev, starts_dev [starts_slots], order_dev: mspa_knn_segments_index_device's tables for the same k.
+ *                              One launch, one lane per row, no atomics; the table is a second output of the same walk.  Takes each
+ *                              host table TWICE and checks all arguments before it enqueues anything; nothing is enqueued for N == 0.
+ *                              MSPA_EINVAL for a null pointer where a count is positive, bad offsets, k outside its range, grids that
+ *                              are not grids_host's, a cap outside its domain, too few starts slots or a misaligned buffer.  Every
+ *                              device table entry a lane indexes with is clamped: corrupt device tables give wrong normals, never an
+ *                              access outside the buffers.
+ *   mspa_cloud_normals_host    the same on the CPU through the same headers, from the unsorted rows (non-finite coordinates are
+ *                              MSPA_EINVAL): the device's twin for tests on a machine without a GPU, not a fallback.
+ */
+#define MSPA_CLOUD_NORMALS_OK 0
+#define MSPA_CLOUD_NORMALS_FEW 1
+#define MSPA_CLOUD_NORMALS_DEGENERATE 2
+#define MSPA_CLOUD_NORMALS_SWEEPS 8
+#define MSPA_CLOUD_NORMALS_GAP_EXPONENT (-26)
+int mspa_cloud_normals_device(const double *pts_dev, const int32_t *starts_dev, int64_t starts_slots, const int64_t *order_dev,
+                              const int64_t *offsets_host, int64_t S, int32_t k, const void *grids_host, const int64_t *offsets_dev,
+                              const void *grids_dev, const int64_t *cell_base_dev, double max_distance, const double *viewpoints_dev,
+                              double *normal_dev, double *curvature_dev, int32_t *used_dev, uint8_t *status_dev, int64_t *nbr_index_dev,
+                              double *nbr_distance_dev, mspa_stream_t stream);
+int mspa_cloud_normals_host(const double *xyz_host, const int64_t *offsets_host, int64_t S, int32_t k, double max_distance,
+                            const double *viewpoints_host, double *normal_host, double *curvature_host, int32_t *used_host,
+                            uint8_t *status_host, int64_t *nbr_index_host, double *nbr_distance_host);
+
+/*
+ * ONE LINEARISED POINT-TO-PLANE STEP PER PAIR -- csrc/cloud_align_plane.hip, rule in csrc/cloud_align_plane_core.h on top of
+ * csrc/cloud_align_core.h: what point-to-plane ICP puts in the place of mspa_cloud_align_fit_*.  The batches, pairs, out_offsets, index
+ * and the 12 f64 of a transform are that entry's; t_normals [Nt, 3] f64 are the targets' normals (mspa_cloud_normals_*).  With T = init
+ * of the pair, y = T q; a row is used when its clamped index is >= 0, its query row is finite and its target row's normal is finite.
+ * Per pair: used and the centroid c of the used y; with a = [(y - c) x n, n] and r = (y - p) . n the 21 + 6 + 1 sums of a a^T, a r
+ * and r r (both passes in the order csrc/cloud_segments_core.h states); (A^T A) x = -(A^T r) by a written-out L D L^T; the new rotation
+ * from the unit quaternion of init's R multiplied by the step's (1, x0 / 2, x1 / 2, x2 / 2) and normalised -- max |R^T R - I| stays
+ * within 32 * 2^-53 after any number of steps -- and the translation about c.  status: MSPA_CLOUD_ALIGN_OK; _FEW (fewer than 6 used
+ * rows); _DEGENERATE (a pivot <= 2^MSPA_CLOUD_ALIGN_GAP_EXPONENT * the largest diagonal entry, or not finite: a flat target).  A pair
+ * that is not OK, and a step that is exactly zero, leave with the 12 f64 of init bit for bit.
+ *   mspa_cloud_align_plane_fit_device  index_dev [M], init_dev [P, 12] -> transform_dev [P, 12] (may be init_dev), used_dev [P] int64,
+ *                                      status_dev [P] int32 and, where not null, rmse_dev [P] (sqrt(r r / used) under init, NaN where
+ *                                      nothing is used) and converged_dev [P] int64, in and out, as mspa_cloud_align_fit_device's.
+ *                                      moments_dev [P, 32] f64 is workspace, a buffer of its own.  Two launches: one workgroup of 256
+ *                                      per pair for the sums, one lane per pair for the solve; no atomics.  Takes each host table
+ *                                      TWICE and checks all arguments before it enqueues anything; nothing is enqueued for P == 0;
+ *                                      every device table entry a lane indexes with is clamped.  MSPA_EINVAL as
+ *                                      mspa_cloud_align_fit_device's.
+ *   mspa_cloud_align_plane_fit_host    the same on the CPU through the same header: the device's twin for tests, not a fallback.
+ */
+int mspa_cloud_align_plane_fit_device(const double *q_xyz_dev, const int64_t *q_offsets_host, int64_t Sq, const int64_t *q_offsets_dev,
+                                      const double *t_xyz_dev, const double *t_normals_dev, int64_t Nt, int64_t St, const int64_t *pairs_host,
+                                      const int64_t *pairs_dev, int64_t P, const int64_t *out_offsets_host, const int64_t *out_offsets_dev,
+                                      const int64_t *index_dev, const double *init_dev, int64_t iteration, double *moments_dev,
+                                      double *transform_dev, int64_t *used_dev, int32_t *status_dev, double *rmse_dev, int64_t *converged_dev,
+                                      mspa_stream_t stream);
+int mspa_cloud_align_plane_fit_host(const double *q_xyz_host, const int64_t *q_offsets_host, int64_t Sq, const double *t_xyz_host,
+                                    const double *t_normals_host, int64_t Nt, int64_t St, const int64_t *pairs_host, int64_t P,
+                                    const int64_t *out_offsets_host, const int64_t *index_host, const double *init_host, int64_t iteration,
+                                    double *transform_host, int64_t *used_host, int32_t *status_host, double *rmse_host, int64_t *converged_host);
+
+/*
  * Instance-mask decode ON THE DEVICE (csrc/mask_ingest.hip, rule in csrc/png_unfilter8_core.h): the 8-bit twin of the depth-frame
  * decode above, for ScanNet's `instance-filt/<image>.png` label images (`cv2.imread(path, -1)` per (image, object) in the
  * reference's get_instance_mask).  The inflate in front of the un-filter is mspa_inflate_blocks_device with block_bytes = h * (w + 1).

@@ -24,6 +24,8 @@ RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3     # Pillow's Image.Resampling numbers
 CLOUD_DISTANCE_GRID_K, CLOUD_DISTANCE_MAX_ROWS, CLOUD_DISTANCE_MAX_PAIRS = 1, 1 << 30, 1 << 24   # csrc/cloud_distance_core.h
 CLOUD_ALIGN_OK, CLOUD_ALIGN_FEW, CLOUD_ALIGN_DEGENERATE, CLOUD_ALIGN_SWEEPS, CLOUD_ALIGN_GAP_EXPONENT = 0, 1, 2, 12, -26   # csrc/cloud_align_core.h
 CLOUD_ALIGN_ORTHO_BOUND = 32.0 * 2.0 ** -53    # csrc/cloud_align_core.h: kOrthoBound, the derived bound on max |R^T R - I|
+CLOUD_NORMALS_OK, CLOUD_NORMALS_FEW, CLOUD_NORMALS_DEGENERATE, CLOUD_NORMALS_SWEEPS, CLOUD_NORMALS_GAP_EXPONENT = 0, 1, 2, 8, -26   # csrc/cloud_normals_core.h
+CLOUD_NORMALS_UNIT_BOUND = 8.0 * 2.0 ** -53    # csrc/cloud_normals_core.h: kUnitBound, the derived bound on | |n|^2 - 1 |
 UPRIGHT_IOU_PAIRS, UPRIGHT_IOU_MATRIX = 0, 1   # include/mspa.h: the two launch shapes of mspa_upright_iou_device
 LINKAGE_MAX_POINTS = 2048
 SNAPPY_BLOCK, SNAPPY_SLOT = 65536, 76544   # csrc/snappy_core.h: kBlock, kSlot
@@ -290,6 +292,15 @@ _SIGNATURES = {
     "mspa_cloud_align_transform_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mspa_cloud_align_fit_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_cloud_normals_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mspa_cloud_normals_host": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "mspa_cloud_align_plane_fit_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p]),
+    "mspa_cloud_align_plane_fit_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -21,7 +21,10 @@ csrc/cloud_distance_core.h) compare the clouds of one batch with those of anothe
 point of the segment its pair names, and a per-pair summary of those distances.  ``rigid_fit_segments`` / ``transform_segments`` /
 ``TargetIndex.register`` / ``register_segments`` (csrc/cloud_align.hip, rule in csrc/cloud_align_core.h) say by which rotation and
 translation one cloud lies off another: the rigid fit of matched rows (Kabsch / Horn) per pair, and point-to-point ICP on top of
-``nearest``.
+``nearest``.  ``knn_segments`` / ``normals_segments`` (csrc/cloud_normals.hip, rule in csrc/cloud_normals_core.h) name the k nearest
+rows of every row inside its own segment and fit a plane to them: a unit normal, towards the segment's viewpoint where one is given,
+the surface variation and a status per row.  ``plane_fit_segments`` and ``TargetIndex.register(estimation="point_to_plane")``
+(csrc/cloud_align_plane.hip, rule in csrc/cloud_align_plane_core.h) are point-to-plane ICP on top of the search and those normals.
 """
 from __future__ import annotations
 
@@ -878,7 +881,7 @@ class TargetIndex:
         return out
 
     def register(self, queries, q_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None, sync_every=None,
-                  want_history: bool = False) -> dict:
+                  want_history: bool = False, estimation: str = "point_to_point", normals=None) -> dict:
         """Point-to-point ICP of every pair: a batch ``queries`` [Nq, C >= 3] (device) with host ``q_offsets`` and the host pair table of
         ``nearest`` -> a dict of device tensors: ``R`` [P, 3, 3] and ``t`` [P, 3] float64, the transform that carries pair p's query
         segment onto its target segment; ``status`` [P] int32 and ``used`` [P] int64 of the last fit (``rigid_fit_segments``');
@@ -894,7 +897,14 @@ class TargetIndex:
         zero host synchronisations.  With ``sync_every=n`` instead: ONE read-back of ``converged_at`` (8 P bytes) after every n
         iterations and after the last, ceil(iterations / n) read-backs at most, and the loop ends at the first that shows no -1; the
         result is byte for byte the full loop's, because every pair then sits at its fixed point (``all_converged``: what the last
-        read-back showed)."""
+        read-back showed).
+        ``estimation="point_to_plane"`` with ``normals`` ([Nt, 3] float64 on the device: the normals of the index's targets in their
+        own order, ``normals_segments``') puts ``plane_fit_segments``' step in the fit's place: T_(k+1) is T_k moved by one linearised
+        point-to-plane step (rule in csrc/cloud_align_plane_core.h), its rotation rebuilt from a normalised quaternion every step;
+        ``status`` is then few below 6 used rows and degenerate where the matched normals leave a motion unconstrained (a flat
+        target), and ``history_rmse`` stays the point distances'.  ``converged_at`` is the same rule, but a linearised step need not
+        ever reproduce its transform bit for bit: ``iterations`` is then the stop.  The same searches, launches in the fit's place
+        and read-backs.  The default is the point-to-point loop above, byte for byte, with its launches."""
         xyz = _xyz_of("queries", queries)
         q_off = _offsets(q_offsets, int(xyz.shape[0]))
         St = self.offsets.size - 1
@@ -903,6 +913,9 @@ class TargetIndex:
         K, every = _iterations_of(iterations, sync_every)
         P, M, dev = pairs.shape[0], int(out_offsets[-1]), self.device
         _require(xyz.device == dev, f"queries: on the index's device {dev}, got {xyz.device}")
+        plane = _estimation_of(estimation, normals)
+        if plane:
+            normals = _normals_of(normals, int(self.pts.shape[0]), dev)
         T = _transforms_of(init, P, dev)
         f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)     # noqa: E731
         i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)       # noqa: E731
@@ -917,7 +930,7 @@ class TargetIndex:
         lib = _lib.load()
         tabs = _AlignTables(q_off, pairs, out_offsets, St, dev)
         targets = self.targets()
-        moved, distance, index, moments, T_next = f64(M, 3), f64(M), i64(M), f64(P, 16), f64(P, 12)
+        moved, distance, index, moments, T_next = f64(M, 3), f64(M), i64(M), f64(P, 32 if plane else 16), f64(P, 12)
         summary = {name: (i64(P) if name in FIT_KEYS[:3] else f64(P)) for name in FIT_KEYS}
 
         def search(T_now):
@@ -945,7 +958,10 @@ class TargetIndex:
         done = K
         for k in range(K):
             search(T)
-            tabs.fit(xyz, targets, index, T, k, moments, T_next, out["used"], out["status"], None, out["converged_at"])
+            if plane:
+                tabs.plane_fit(xyz, targets, normals, index, T, k, moments, T_next, out["used"], out["status"], None, out["converged_at"])
+            else:
+                tabs.fit(xyz, targets, index, T, k, moments, T_next, out["used"], out["status"], None, out["converged_at"])
             T, T_next = T_next, T
             if want_history:
                 out["history_used"][k].copy_(out["used"])
@@ -1173,6 +1189,12 @@ class _AlignTables:
             self.pairs.ctypes.data, _ptr(self.pairs_dev), self.P, self.out.ctypes.data, _ptr(self.out_dev), _ptr(index), _ptr(init), iteration,
             _ptr(moments), _ptr(T), _ptr(used), _ptr(status), _ptr(eigen), _ptr(converged), _stream_ptr()))
 
+    def plane_fit(self, xyz, targets, normals, index, init, iteration, moments, T, used, status, rmse=None, converged=None):
+        _lib.check(_lib.load().mspa_cloud_align_plane_fit_device(
+            _ptr(xyz), self.q_off.ctypes.data, self.q_off.size - 1, _ptr(self.q_dev), _ptr(targets), _ptr(normals), int(targets.shape[0]), self.St,
+            self.pairs.ctypes.data, _ptr(self.pairs_dev), self.P, self.out.ctypes.data, _ptr(self.out_dev), _ptr(index), _ptr(init), iteration,
+            _ptr(moments), _ptr(T), _ptr(used), _ptr(status), _ptr(rmse), _ptr(converged), _stream_ptr()))
+
 
 def _index_of(index, M: int, device) -> torch.Tensor:
     _require(isinstance(index, torch.Tensor) and index.device == device and index.dtype == torch.int64 and tuple(index.shape) == (M,),
@@ -1244,11 +1266,12 @@ def _required_cap(max_distance) -> float:
 
 
 def register_segments(queries: torch.Tensor, q_offsets, targets: torch.Tensor, t_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None,
-                      sync_every=None, want_history: bool = False, _grid_k=None) -> dict:
+                      sync_every=None, want_history: bool = False, _grid_k=None, estimation: str = "point_to_point", normals=None) -> dict:
     """``target_index(targets, t_offsets).register(queries, q_offsets, ...)``: point-to-point ICP of every pair's query segment onto
-    its target segment.  ``target_index``' one read-back and its ValueError."""
+    its target segment (``estimation="point_to_plane"`` with the targets' ``normals``: point-to-plane).  ``target_index``' one
+    read-back and its ValueError."""
     return target_index(targets, t_offsets, _grid_k).register(queries, q_offsets, pairs, max_distance=max_distance, iterations=iterations, init=init,
-                                                              sync_every=sync_every, want_history=want_history)
+                                                              sync_every=sync_every, want_history=want_history, estimation=estimation, normals=normals)
 
 
 def _host_rows(name: str, rows) -> np.ndarray:
@@ -1301,13 +1324,16 @@ def transform_segments_host(queries, q_offsets, R, t, pairs=None) -> dict:
 
 
 def register_segments_host(queries, q_offsets, targets, t_offsets, pairs=None, *, max_distance, iterations: int = 30, init=None, sync_every=None,
-                           want_history: bool = False, want_index: bool = False, _grid_k=None) -> dict:
+                           want_history: bool = False, want_index: bool = False, _grid_k=None, estimation: str = "point_to_point", normals=None) -> dict:
     """``register_segments`` on the CPU for NumPy input: the same loop over the host twins, ``nearest_segments_host`` for its searches.
     NumPy arrays out; with ``want_index`` also ``history_index`` [K, M], the correspondences of every iteration.  The device's twin,
     not a fallback."""
     q, t = _host_rows("queries", queries), _host_rows("targets", targets)
     q_off, t_off = _offsets(q_offsets, q.shape[0]), _offsets(t_offsets, t.shape[0])
     St = t_off.size - 1
+    plane = _estimation_of(estimation, normals)
+    if plane:
+        normals = _normals_of(normals, t.shape[0])
     pairs, out_offsets = _pair_tables(q_off, St, pairs)
     cap = _required_cap(max_distance)
     K, every = _iterations_of(iterations, sync_every)
@@ -1328,7 +1354,10 @@ def register_segments_host(queries, q_offsets, targets, t_offsets, pairs=None, *
     done = K
     for k in range(K):
         index, _fit, rmse = search(T)
-        T, out["used"], out["status"], _ = _fit_host(q, q_off, t, St, pairs, out_offsets, index, T, k, False, converged)
+        if plane:
+            T, out["used"], out["status"], _ = _plane_fit_host(q, q_off, t, normals, St, pairs, out_offsets, index, T, k, converged)
+        else:
+            T, out["used"], out["status"], _ = _fit_host(q, q_off, t, St, pairs, out_offsets, index, T, k, False, converged)
         hist_used[k], hist_rmse[k], hist_index[k] = out["used"], rmse, index
         if sync_every is not None and ((k + 1) % every == 0 or k + 1 == K):
             out["all_converged"] = bool((converged != -1).all())
@@ -1345,3 +1374,198 @@ def register_segments_host(queries, q_offsets, targets, t_offsets, pairs=None, *
     if want_index:
         out["history_index"] = hist_index
     return out
+
+
+# ---- the k nearest rows and the normals of a batch (csrc/cloud_normals.hip, rule in csrc/cloud_normals_core.h) ----------------------------
+
+NORMALS_STATUS = {"ok": _lib.CLOUD_NORMALS_OK, "few": _lib.CLOUD_NORMALS_FEW, "degenerate": _lib.CLOUD_NORMALS_DEGENERATE}
+
+
+def _viewpoints_of(viewpoints, S: int, device=None):
+    """``viewpoints`` (None: none anywhere; [S, 3], host or device; a NaN row: none for that segment) -> [S, 3] float64: a device
+    tensor on ``device``, or a NumPy array where ``device`` is None.  Enqueue only: a host array goes up through pinned memory."""
+    if viewpoints is None:
+        return None
+    on_device = isinstance(viewpoints, torch.Tensor) and viewpoints.is_cuda
+    if not on_device:
+        viewpoints = np.asarray(viewpoints.numpy() if isinstance(viewpoints, torch.Tensor) else viewpoints, dtype=np.float64)
+    _require(tuple(viewpoints.shape) == (S, 3), f"viewpoints: [S, 3] with S = {S}, got {list(viewpoints.shape)}")
+    if on_device:
+        _require(device is not None and viewpoints.device == device, "viewpoints: on the rows' device")
+        return viewpoints.to(torch.float64).contiguous()
+    flat = np.ascontiguousarray(viewpoints)
+    return flat if device is None else (_upload(flat, device=device)[0] if S else torch.empty((0, 3), dtype=torch.float64, device=device))
+
+
+def _normals_device(rows, offsets, k, max_distance, viewpoints, want_fit: bool, want_table: bool) -> dict:
+    xyz = _xyz_of("rows", rows)
+    N, dev = int(xyz.shape[0]), xyz.device
+    off = _offsets(offsets, N)
+    k, cap, S = _knn_check(k), _cap_of(max_distance), off.size - 1
+    _require(N <= 1 << 30, f"rows: at most 2^30 rows, got {N}")
+    views = _viewpoints_of(viewpoints, S, dev)
+    out = {"used": torch.empty((N,), dtype=torch.int32, device=dev)}
+    if want_fit:
+        out["normal"] = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        out["curvature"] = torch.empty((N,), dtype=torch.float64, device=dev)
+        out["status"] = torch.empty((N,), dtype=torch.uint8, device=dev)
+    if want_table:
+        out["index"] = torch.empty((N, k), dtype=torch.int64, device=dev)
+        out["distance"] = torch.empty((N, k), dtype=torch.float64, device=dev)
+    if N == 0:
+        return out
+    lib = _lib.load()
+    grids, off_dev, grids_dev, base_dev = _search_tables(xyz, off, k)
+    cell_base = np.zeros((S + 1,), dtype=np.int64)
+    _lib.check(lib.mspa_knn_segments_tables_host(off.ctypes.data, S, k, cell_base.ctypes.data))
+    starts = torch.zeros((int(cell_base[S]) + S,), dtype=torch.int32, device=dev)             # the slots behind a segment's cells are never written
+    pts = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    keys = torch.empty((N,), dtype=torch.int64, device=dev)
+    _lib.check(lib.mspa_knn_segments_cells_device(_ptr(xyz), off.ctypes.data, S, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev),
+                                                  _ptr(base_dev), _ptr(keys), _stream_ptr()))
+    order = torch.sort(keys, stable=True).indices
+    _lib.check(lib.mspa_knn_segments_index_device(_ptr(xyz), off.ctypes.data, S, k, grids.ctypes.data, _ptr(off_dev), _ptr(grids_dev), _ptr(base_dev),
+                                                  _ptr(order), _ptr(pts), _ptr(keys), _ptr(starts), int(starts.numel()), _stream_ptr()))
+    _lib.check(lib.mspa_cloud_normals_device(_ptr(pts), _ptr(starts), int(starts.numel()), _ptr(order), off.ctypes.data, S, k, grids.ctypes.data,
+                                             _ptr(off_dev), _ptr(grids_dev), _ptr(base_dev), cap, _ptr(views), _ptr(out.get("normal")),
+                                             _ptr(out.get("curvature")), _ptr(out["used"]), _ptr(out.get("status")), _ptr(out.get("index")),
+                                             _ptr(out.get("distance")), _stream_ptr()))
+    return out
+
+
+def knn_segments(rows: torch.Tensor, offsets, k: int, max_distance=None):
+    """A batch ``rows`` [N, C >= 3] (device; xyz in front, float64 or a dtype that widens to it exactly) with host ``offsets`` [S + 1]
+    -> ``(index, distance)``: ``index`` [N, k] int64 (device), per row the min(k, n_s) rows of its OWN segment with the smallest
+    ``(d2, row)`` as rows of the batch, in that order, the row itself first among them at distance 0 (Open3D's KNN search), -1 behind
+    them; ``distance`` [N, k] float64, ``sqrt(d2)`` with ``d2 = (dx*dx + dy*dy) + dz*dz``, +inf behind them.  With ``max_distance``
+    (finite, > 0) only rows with ``d2 <= max_distance * max_distance`` count (Open3D's hybrid search).  The rule is
+    csrc/cloud_normals_core.h's; the bits are those of a brute force with ``np.lexsort((row, d2))``.  ``1 <= k <= 64``.  One read-back
+    per call, whatever S is: ``knn_mean_distance_segments``' boxes with the flag that every coordinate is finite; non-finite
+    coordinates raise its ValueError."""
+    out = _normals_device(rows, offsets, k, max_distance, None, False, True)
+    return out["index"], out["distance"]
+
+
+def normals_segments(rows: torch.Tensor, offsets, k: int = 30, max_distance=None, viewpoints=None, want_neighbours: bool = False) -> dict:
+    """A batch ``rows`` [N, C >= 3] (device) with host ``offsets`` [S + 1] -> a dict of device tensors, per row: ``normal`` [N, 3]
+    float64, the unit eigenvector of the smallest eigenvalue of the centred second moments of the row's ``knn_segments`` neighbours
+    (the row itself among them; ``max_distance`` as there); ``curvature`` [N] float64 = l0 / ((l0 + l1) + l2), the surface variation;
+    ``used`` [N] int32, the neighbours found; ``status`` [N] uint8 (``NORMALS_STATUS``: ok, few = fewer than 3 neighbours, degenerate =
+    collinear, coincident or isotropic neighbours: l1 - l0 <= 2^-26 (l2 - l0)).  A row that is not ok has a NaN normal and a NaN
+    curvature.  Sign: the first non-zero component is positive; with ``viewpoints`` ([S, 3], host or device; a NaN row: none for that
+    segment) a normal is negated where ``(v - p) . n < 0``, so it points towards its segment's viewpoint.  With ``want_neighbours``
+    also ``index`` and ``distance`` [N, k], ``knn_segments``' table from the same walk.  The rule is csrc/cloud_normals_core.h's:
+    sequential sums in ascending ``(d2, row)`` order, a fixed number of Jacobi sweeps -- the same bits on every run and in any order
+    of the rows inside a grid cell; rows in a plane ``z = const`` with integer z get (0, 0, 1) and 0.0 exactly.  One read-back per
+    call, whatever S is: ``knn_mean_distance_segments``' boxes with the flag that every coordinate is finite; non-finite coordinates
+    raise its ValueError.  One launch behind the index's."""
+    return _normals_device(rows, offsets, k, max_distance, viewpoints, True, bool(want_neighbours))
+
+
+def _normals_host(rows, offsets, k, max_distance, viewpoints, want_fit: bool, want_table: bool) -> dict:
+    xyz = _host_rows("rows", rows)
+    N = xyz.shape[0]
+    off = _offsets(offsets, N)
+    k, cap, S = _knn_check(k), _cap_of(max_distance), off.size - 1
+    views = _viewpoints_of(viewpoints, S)
+    if not np.isfinite(xyz).all():
+        raise ValueError("mspa.cloud_segments: requirement not met: xyz: finite coordinates")
+    out = {"used": np.zeros((N,), dtype=np.int32)}
+    if want_fit:
+        out.update(normal=np.zeros((N, 3)), curvature=np.zeros((N,)), status=np.zeros((N,), dtype=np.uint8))
+    if want_table:
+        out.update(index=np.zeros((N, k), dtype=np.int64), distance=np.zeros((N, k)))
+    at = lambda name: out[name].ctypes.data if name in out else None               # noqa: E731
+    _lib.check(_lib.load().mspa_cloud_normals_host(xyz.ctypes.data, off.ctypes.data, S, k, cap, views.ctypes.data if views is not None else None,
+                                                   at("normal"), at("curvature"), at("used"), at("status"), at("index"), at("distance")))
+    return out
+
+
+def knn_segments_host(rows, offsets, k: int, max_distance=None):
+    """``knn_segments`` on the CPU for NumPy input, through the same headers (mspa_cloud_normals_host): NumPy arrays out.  The device's
+    twin for tests and for input that has no device, not a fallback."""
+    out = _normals_host(rows, offsets, k, max_distance, None, False, True)
+    return out["index"], out["distance"]
+
+
+def normals_segments_host(rows, offsets, k: int = 30, max_distance=None, viewpoints=None, want_neighbours: bool = False) -> dict:
+    """``normals_segments`` on the CPU for NumPy input, through the same headers (mspa_cloud_normals_host): the same keys, NumPy arrays.
+    The device's twin, not a fallback."""
+    return _normals_host(rows, offsets, k, max_distance, viewpoints, True, bool(want_neighbours))
+
+
+# ---- point-to-plane on top of the two (csrc/cloud_align_plane.hip, rule in csrc/cloud_align_plane_core.h) ------------------------------
+
+def _estimation_of(estimation, normals) -> bool:
+    """True for point-to-plane.  ``normals`` belong to it and to nothing else."""
+    _require(estimation in ("point_to_point", "point_to_plane"), f"estimation: 'point_to_point' or 'point_to_plane', got {estimation!r}")
+    plane = estimation == "point_to_plane"
+    _require(plane == (normals is not None), "normals: the targets' normals [Nt, 3], with estimation='point_to_plane' and only with it")
+    return plane
+
+
+def _normals_of(normals, Nt: int, device=None):
+    """The targets' normals, checked: [Nt, 3] float64, a device tensor on ``device`` or, where ``device`` is None, a NumPy array.  NaN
+    rows are allowed: they constrain nothing."""
+    if device is None:
+        normals = np.ascontiguousarray(normals.cpu().numpy() if isinstance(normals, torch.Tensor) else normals, dtype=np.float64)
+        _require(normals.shape == (Nt, 3), f"normals: [Nt, 3] with Nt = {Nt}, got {list(normals.shape)}")
+        return normals
+    _require(isinstance(normals, torch.Tensor) and normals.device == device and tuple(normals.shape) == (Nt, 3),
+             f"normals: a tensor [Nt, 3] with Nt = {Nt} on the targets' device")
+    return normals.to(torch.float64).contiguous()
+
+
+def plane_fit_segments(queries: torch.Tensor, q_offsets, targets: torch.Tensor, normals: torch.Tensor, index: torch.Tensor, pairs=None,
+                       init=None) -> dict:
+    """One linearised point-to-plane step, pair by pair: a batch ``queries`` [Nq, C >= 3] (device) with host ``q_offsets`` [Sq + 1],
+    ``targets`` [Nt, C >= 3] with their ``normals`` [Nt, 3] (device), ``index`` [M] int64 (device; per output row a row of ``targets``
+    or -1: what ``TargetIndex.nearest`` returns for the rows under ``init``) and the host pair table of ``nearest`` (only its first
+    column is read; None: pair s is query segment s) -> a dict of device tensors ``R`` [P, 3, 3] and ``t`` [P, 3] float64: ``init``
+    ([P, 4, 4] or [P, 3, 4]; None: the identity) moved by the step that minimises, to first order, the sum of squares of
+    ``(y - targets[index]) . normals[index]`` over the used rows, ``y = init q`` (index >= 0, a finite query row, a finite normal);
+    ``used`` [P] int64; ``status`` [P] int32 (``ALIGN_STATUS``: few = fewer than 6 used rows, degenerate = the matched normals leave a
+    motion unconstrained, as a flat target does); ``rmse`` [P], sqrt of the mean squared plane distance under ``init``; ``offsets``
+    [P + 1] host int64.  A pair that is not ok, and a step that is exactly zero, keep ``init`` bit for bit.  The rule is
+    csrc/cloud_align_plane_core.h's: sums in the order csrc/cloud_segments_core.h states, a written-out L D L^T, the rotation rebuilt
+    from a normalised quaternion, so max |R^T R - I| stays within 32 * 2^-53 after any number of steps.  Enqueue only: two launches on
+    the current stream, the host tables go up through pinned memory and nothing is read back."""
+    xyz, tgt = _xyz_of("queries", queries), _xyz_of("targets", targets)
+    q_off = _offsets(q_offsets, int(xyz.shape[0]))
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    P, M, dev = pairs.shape[0], int(out_offsets[-1]), xyz.device
+    _require(tgt.device == dev, "targets: on the queries' device")
+    normals = _normals_of(normals, int(tgt.shape[0]), dev)
+    index = _index_of(index, M, dev)
+    T0 = _transforms_of(init, P, dev)
+    T = torch.empty((P, 12), dtype=torch.float64, device=dev)
+    out = {"used": torch.empty((P,), dtype=torch.int64, device=dev), "status": torch.empty((P,), dtype=torch.int32, device=dev),
+           "rmse": torch.empty((P,), dtype=torch.float64, device=dev), "offsets": out_offsets}
+    if P:
+        moments = torch.empty((P, 32), dtype=torch.float64, device=dev)
+        _AlignTables(q_off, pairs, out_offsets, St, dev).plane_fit(xyz, tgt, normals, index, T0, 0, moments, T, out["used"], out["status"], out["rmse"])
+    out["R"], out["t"] = _split(T)
+    return out
+
+
+def _plane_fit_host(q, q_off, t, normals, St, pairs, out_offsets, index, T0, iteration, converged=None):
+    P = pairs.shape[0]
+    T, used, status, rmse = np.zeros((P, 12)), np.zeros((P,), dtype=np.int64), np.zeros((P,), dtype=np.int32), np.zeros((P,))
+    _lib.check(_lib.load().mspa_cloud_align_plane_fit_host(q.ctypes.data, q_off.ctypes.data, q_off.size - 1, t.ctypes.data, normals.ctypes.data, t.shape[0],
+                                                           St, pairs.ctypes.data, P, out_offsets.ctypes.data, index.ctypes.data, T0.ctypes.data, iteration,
+                                                           T.ctypes.data, used.ctypes.data, status.ctypes.data, rmse.ctypes.data,
+                                                           converged.ctypes.data if converged is not None else None))
+    return T, used, status, rmse
+
+
+def plane_fit_segments_host(queries, q_offsets, targets, normals, index, pairs=None, init=None) -> dict:
+    """``plane_fit_segments`` on the CPU for NumPy input, through the same header (mspa_cloud_align_plane_fit_host): NumPy arrays out.
+    The device's twin for tests and for input that has no device, not a fallback."""
+    q, t = _host_rows("queries", queries), _host_rows("targets", targets)
+    q_off = _offsets(q_offsets, q.shape[0])
+    pairs, out_offsets, St = _fit_pairs(q_off, pairs)
+    normals = _normals_of(normals, t.shape[0])
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    _require(index.shape == (int(out_offsets[-1]),), f"index: int64 [M] with M = {int(out_offsets[-1])}")
+    T, used, status, rmse = _plane_fit_host(q, q_off, t, normals, St, pairs, out_offsets, index, _transforms_of(init, pairs.shape[0]), 0)
+    return {"R": _split(T)[0], "t": _split(T)[1], "used": used, "status": status, "rmse": rmse, "offsets": out_offsets}

@@ -29,8 +29,11 @@ class InstanceClouds:
     the segments' extents (+inf / -inf where empty).  Object ``target_id`` is label ``target_id + 1``, as upstream."""
 
     def __init__(self, image_ids: Sequence, counts: np.ndarray, rows: torch.Tensor, pixel: Optional[torch.Tensor], lo: torch.Tensor,
-                 hi: torch.Tensor, rgb: Optional[torch.Tensor] = None):
+                 hi: torch.Tensor, rgb: Optional[torch.Tensor] = None, *, centres=None):
         self.image_ids = list(image_ids)
+        # ``centres``: [F, 3] host float64, None, or a function without arguments that returns one of the two -- ``build`` passes a
+        # function, so the poses are read only if somebody asks (``normals``)
+        self._centres = centres
         self._frame = {self._key(i): k for k, i in enumerate(self.image_ids)}
         self.counts = np.ascontiguousarray(counts, dtype=np.int64)
         self.n_labels = int(self.counts.shape[1])
@@ -38,6 +41,16 @@ class InstanceClouds:
         np.cumsum(self.counts.reshape(-1), out=self.offsets[1:])
         self.rows, self.pixel, self.lo, self.hi, self.rgb = rows, pixel, lo, hi, rgb
         self.with_color = rows.shape[1] == 6
+
+    @property
+    def centres(self) -> Optional[np.ndarray]:
+        """[F, 3] host float64 or None: each frame's camera centre in the rows' frame, a NaN row where it is not known.  Taken on the
+        first look where ``build`` left a function."""
+        if callable(self._centres):
+            self._centres = self._centres()
+        if self._centres is not None:
+            self._centres = np.ascontiguousarray(self._centres, dtype=np.float64).reshape(len(self.image_ids), 3)
+        return self._centres
 
     @staticmethod
     def _key(image_id):
@@ -97,7 +110,21 @@ class InstanceClouds:
             index = index.index_select(0, of_cleaned)
         shape = self.counts.shape
         return InstanceClouds(self.image_ids, np.diff(offsets).reshape(shape), rows, None if self.pixel is None else self.pixel.index_select(0, index),
-                              lo.reshape(shape + (3,)), hi.reshape(shape + (3,)), None if self.rgb is None else self.rgb.index_select(0, index))
+                              lo.reshape(shape + (3,)), hi.reshape(shape + (3,)), None if self.rgb is None else self.rgb.index_select(0, index),
+                              centres=self._centres)
+
+    def normals(self, k=30, max_distance=None) -> dict:
+        """``cloud_segments.normals_segments`` of every (image, label) at once -> its dict of device tensors over ``rows``: ``normal``
+        [total, 3], ``curvature`` [total], ``used`` [total] int32 and ``status`` [total] uint8 (``cloud_segments.NORMALS_STATUS``); the
+        rows of (frame k, label v) are ``offsets[k * L + v] : offsets[k * L + v + 1]`` as everywhere here.  The neighbours of a row
+        are the ``k`` nearest rows of its OWN (image, object) cloud, within ``max_distance`` where one is given.  A depth frame samples
+        surfaces from its camera centre, so every normal of frame k points towards ``centres[k]`` (the translation of the frame's
+        aligned pose, which ``build`` records); it is unoriented -- first non-zero component positive -- where no centre is known: a
+        NaN row of ``centres``, or an ``InstanceClouds`` made without them.  One read-back (``normals_segments``'), its ValueError; it
+        needs the rows on the device."""
+        from . import cloud_segments
+        views = None if self.centres is None else np.repeat(self.centres, self.n_labels, axis=0)
+        return cloud_segments.normals_segments(self.rows, self.offsets, k, max_distance, views)
 
     def boxes(self) -> torch.Tensor:
         """[F, L, 6] float64 on the device: ``aabb`` of every (image, label) at once, ``[(hi + lo) / 2, hi - lo]``; NaN where the
@@ -288,6 +315,19 @@ def _split_chunk(handler, scene_id, ids, depth, labels, rgb, device):
     return engine.instance_split(labels, out["valid_u8"], out["xyz_f64"], rgb)
 
 
+def _centres(handler, scene_id, ids) -> np.ndarray:
+    """[F, 3]: the camera centre of every posed frame in the clouds' (axis-aligned) frame, the translation of ``A @ E``; a NaN row for a
+    frame without a finite pose."""
+    out = np.full((len(ids), 3), np.nan)
+    A = None
+    for k, i in enumerate(ids):
+        if handler.is_posed_image_valid(scene_id, i):
+            if A is None:
+                A = np.asarray(handler.get_world_to_axis_align_matrix(scene_id), np.float64)
+            out[k] = (A @ np.asarray(handler.get_extrinsic_matrix(scene_id, i, warning=False), np.float64))[:3, 3]
+    return out
+
+
 def _host_composition(handler, scene_id, ids, with_color, device, images) -> InstanceClouds:
     """The same object from the per-object composition the reference writes: get_instance_mask + project_image_to_3d_with_mask
     per (image, label present in the mask)."""
@@ -323,7 +363,7 @@ def _host_composition(handler, scene_id, ids, with_color, device, images) -> Ins
             blocks.append(clouds[v])
     rows = np.concatenate(blocks) if blocks else np.zeros((0, C))
     return InstanceClouds(ids, counts, torch.from_numpy(np.ascontiguousarray(rows.reshape(-1, C))).to(device), None,
-                          torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device))
+                          torch.from_numpy(lo).to(device), torch.from_numpy(hi).to(device), centres=lambda: _centres(handler, scene_id, ids))
 
 
 def build(handler, scene_id, image_ids=None, with_color=False, device="cuda", num_workers=8, max_dense_bytes=1 << 30,
@@ -385,4 +425,4 @@ def build(handler, scene_id, image_ids=None, with_color=False, device="cuda", nu
     else:
         rows, rgb = torch.zeros((0, C), dtype=torch.float64, device=device), None
         pixel = torch.zeros((0,), dtype=torch.int32, device=device)
-    return InstanceClouds(ids, counts, rows, pixel, lo, hi, rgb)
+    return InstanceClouds(ids, counts, rows, pixel, lo, hi, rgb, centres=lambda: _centres(handler, scene_id, ids))

@@ -221,7 +221,8 @@ def compute_point_cloud_distance(source, target):
                                                 np.array([0, target.shape[0]], dtype=np.int64))["distance"]
 
 
-def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration: int = 30):
+def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration: int = 30, estimation: str = "point_to_point",
+                     target_normals=None):
     """[n, C >= 3] cloud ``source`` and [m, C >= 3] cloud ``target`` -> a dict: ``transformation`` [4, 4] float64, the rigid transform
     that carries ``source`` onto ``target`` by point-to-point ICP from ``init`` ([4, 4]; None: the identity), and Open3D's two result
     fields under it, ``fitness`` (the share of source rows with a target row within ``max_correspondence_distance``) and
@@ -231,28 +232,70 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
     not checked against Open3D, which is not a dependency.  Every iteration fits the ORIGINAL source rows to their nearest target
     rows (csrc/cloud_align_core.h: Horn's quaternion by a fixed number of Jacobi sweeps, float64), so no transforms are composed.  It
     is the one-pair case of ``mspa.cloud_segments.register_segments``: NumPy in gives NumPy out (the host twin of the kernels), a
-    device tensor in gives device tensors out, the same bits either way.  No reference counterpart."""
+    device tensor in gives device tensors out, the same bits either way.  ``estimation="point_to_plane"`` is Open3D's
+    ``TransformationEstimationPointToPlane``: every iteration moves the transform by one linearised point-to-plane step against the
+    target's normals (csrc/cloud_align_plane_core.h), ``target_normals`` [m, 3] or, where None, ``estimate_normals(target, 30)``; a
+    target that leaves a motion unconstrained (a single plane) keeps ``init``.  No reference counterpart."""
     from mspa import cloud_segments
     one = lambda rows: np.array([0, rows.shape[0]], dtype=np.int64)           # noqa: E731
+    if estimation not in ("point_to_point", "point_to_plane"):
+        raise ValueError(f"registration_icp: estimation must be 'point_to_point' or 'point_to_plane', got {estimation!r}")
+    if estimation == "point_to_point" and target_normals is not None:
+        raise ValueError("registration_icp: target_normals belong to estimation='point_to_plane'")
+    plane = estimation == "point_to_plane"
     if isinstance(source, torch.Tensor) or isinstance(target, torch.Tensor):
         source, target = _same_device(source, target)
         if source.is_cuda:
+            extra = {}
+            if plane:
+                normals = estimate_normals(target, 30) if target_normals is None else torch.as_tensor(target_normals, dtype=torch.float64).to(target.device)
+                extra = {"estimation": estimation, "normals": normals}
             out = cloud_segments.register_segments(source, one(source), target, one(target), max_distance=max_correspondence_distance,
-                                                   iterations=max_iteration, init=None if init is None else torch.as_tensor(init)[None])
+                                                   iterations=max_iteration, init=None if init is None else torch.as_tensor(init)[None], **extra)
             T = torch.eye(4, dtype=torch.float64, device=source.device)
             T[:3, :3], T[:3, 3] = out["R"][0], out["t"][0]
             return {"transformation": T, "fitness": out["fitness"][0], "inlier_rmse": out["inlier_rmse"][0]}
         host = registration_icp(source.numpy(), target.numpy(), max_correspondence_distance, None if init is None else torch.as_tensor(init).cpu().numpy(),
-                                max_iteration)
+                                max_iteration, estimation, None if target_normals is None else torch.as_tensor(target_normals).cpu().numpy())
         return {k: torch.as_tensor(v) for k, v in host.items()}
     source, target = np.asarray(source), np.asarray(target)
     if isinstance(init, torch.Tensor):
         init = init.cpu().numpy()
+    extra = {}
+    if plane:
+        if isinstance(target_normals, torch.Tensor):
+            target_normals = target_normals.cpu().numpy()
+        extra = {"estimation": estimation, "normals": estimate_normals(target, 30) if target_normals is None else np.asarray(target_normals, dtype=np.float64)}
     out = cloud_segments.register_segments_host(source, one(source), target, one(target), max_distance=max_correspondence_distance,
-                                                iterations=max_iteration, init=None if init is None else np.asarray(init, dtype=np.float64)[None])
+                                                iterations=max_iteration, init=None if init is None else np.asarray(init, dtype=np.float64)[None], **extra)
     T = np.eye(4)
     T[:3, :3], T[:3, 3] = out["R"][0], out["t"][0]
     return {"transformation": T, "fitness": out["fitness"][0], "inlier_rmse": out["inlier_rmse"][0]}
+
+
+def estimate_normals(point_cloud_data, k: int = 30, radius=None, camera_location=None):
+    """[n, C >= 3] cloud -> [n, 3] float64: per row the unit normal of the plane through its ``k`` nearest rows (itself among them;
+    with a ``radius`` only those within it: Open3D's ``KDTreeSearchParamHybrid(radius, max_nn=k)``, without one
+    ``KDTreeSearchParamKNN(k)``), the eigenvector of the smallest eigenvalue of their covariance.  With a ``camera_location`` [3] the
+    normals point towards it (Open3D's ``orient_normals_towards_camera_location``); without one the first non-zero component is
+    positive.  A row with fewer than 3 neighbours, or with collinear, coincident or isotropic ones, has a NaN normal where Open3D
+    leaves an arbitrary one.  The name is Open3D's ``PointCloud.estimate_normals``; the rule restates it and is not checked against
+    Open3D, which is not a dependency.  It is the one-segment case of ``mspa.cloud_segments.normals_segments`` (rule in
+    csrc/cloud_normals_core.h): NumPy in gives NumPy out (the host twin of the kernel), a device tensor in gives a device tensor
+    out, the same bits either way.  No reference counterpart."""
+    from mspa import cloud_segments
+    is_tensor = isinstance(point_cloud_data, torch.Tensor)
+    data = point_cloud_data if is_tensor else np.asarray(point_cloud_data)
+    offsets = np.array([0, int(data.shape[0])], dtype=np.int64)
+    view = None
+    if camera_location is not None:
+        view = camera_location.reshape(1, 3) if isinstance(camera_location, torch.Tensor) else np.asarray(camera_location, dtype=np.float64).reshape(1, 3)
+    if is_tensor and data.is_cuda:
+        return cloud_segments.normals_segments(data, offsets, k, radius, view)["normal"]
+    if isinstance(view, torch.Tensor):
+        view = view.cpu().numpy()
+    out = cloud_segments.normals_segments_host(data.numpy() if is_tensor else data, offsets, k, radius, view)["normal"]
+    return torch.from_numpy(out) if is_tensor else out
 
 
 def remove_truncated_outliers(point_cloud_data, tx: float, ty: float, tz: float):
